@@ -23,7 +23,9 @@ Workload (config.workload):
 
 Output: ONE JSON line on rank 0 (see the driver contract in the task statement) carrying `roofline`
 (dominant blend kernel: algorithmic bytes / HIP-event time / 8 TB/s) and `cpu_baseline` (the CPU oracle
-timed on this box's host cores on a bounded sample).
+timed on this box's host cores on a bounded sample).  With --dump-outputs DIR rank 0 also writes what the last timed step
+computed (image planes, per-Gaussian outputs and gradients) as DIR/<name>.npy; the inputs are seeded, so two builds run
+with the same arguments can be compared array for array.
 """
 import argparse
 import contextlib
@@ -712,6 +714,39 @@ def train_iteration_timing(scenes, scene, cam, bg, settings, W, H, dev, steps, w
     return out
 
 
+DUMP_LIMIT_BYTES = 64_000_000          # --dump-outputs: every array together
+DUMP_MAX_ROWS = 1 << 16                # per-Gaussian arrays: at most this many rows, the same seeded sample in each
+DUMP_IMAGES = ("render", "acc_pixel_size", "depth")
+
+
+def dump_outputs(out_dir, out, pc, P, H, W):
+    """--dump-outputs: what a caller of the timed path receives from one step — the render() result dict and the gradients
+    its backward left on the leaf parameters and on viewspace_points — written as out_dir/<name>.npy in float32 (radii and
+    visibility_filter as their float32 values).  Per-Gaussian arrays keep a fixed seeded sample of DUMP_MAX_ROWS rows when P
+    is larger (the same rows in every array); the image planes stay whole unless the total would pass DUMP_LIMIT_BYTES, and
+    then keep a fixed seeded sample of pixels (the same in every plane).  Returns {name: [full shape, dumped shape]}."""
+    arrays = {k: out[k] for k in DUMP_IMAGES + ("visibility_filter", "radii", "pixel_sizes")}
+    arrays["viewspace_points_grad"] = out["viewspace_points"].grad
+    for n, p_ in zip(pc.LEAVES, pc.parameters()):
+        arrays["grad" + n] = p_.grad
+    arrays = {k: v.detach().to("cpu", torch.float32).numpy() for k, v in arrays.items() if v is not None}
+    shapes = {k: list(a.shape) for k, a in arrays.items()}
+    if P > DUMP_MAX_ROWS:
+        rows = np.sort(np.random.default_rng(0).choice(P, DUMP_MAX_ROWS, replace=False))
+        arrays.update({k: a[rows] for k, a in arrays.items() if k not in DUMP_IMAGES})
+    per_gaussian = sum(a.nbytes for k, a in arrays.items() if k not in DUMP_IMAGES)
+    per_pixel = sum(arrays[k].nbytes for k in DUMP_IMAGES if k in arrays) // (H * W)
+    limit = DUMP_LIMIT_BYTES - 1024 * len(arrays)         # room for the .npy headers
+    if per_gaussian + per_pixel * H * W > limit:
+        n_px = (limit - per_gaussian) // per_pixel
+        px = np.sort(np.random.default_rng(1).choice(H * W, n_px, replace=False))
+        arrays.update({k: arrays[k].reshape(arrays[k].shape[:-2] + (H * W,))[..., px] for k in DUMP_IMAGES if k in arrays})
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(a))
+    return {k: [shapes[k], list(a.shape)] for k, a in arrays.items()}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -730,7 +765,12 @@ def main():
     ap.add_argument("--no-two-view", action="store_true",
                     help="skip the informational two-views-in-flight block (tools/profile_round.sh: its co-resident kernels "
                          "would enter the per-kernel averages of the profile)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32, a "
+                         "fixed seeded sample when larger than 64 MB in all; dump_outputs())")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -901,11 +941,20 @@ def main():
                 out["render"].backward(dL)
                 fb_bucket.all_reduce(average_over=world)
                 return out
+    last_out = {}
+
+    def timed_step(k):
+        out = step(timers.get(k))
+        if k == args.steps - 1:
+            last_out.update(out)
     settle_gc()
     for _ in range(args.warmup):
         step()
-    elapsed = timed_region(lambda k: step(timers.get(k)), args.steps)
+    elapsed = timed_region(timed_step, args.steps)
     dgr._C.set_timer(None)
+    # the last timed step's results, read before any other step can overwrite them
+    dumped = dump_outputs(args.dump_outputs, last_out, pc, P, H, W) if args.dump_outputs and rank == 0 else None
+    last_out.clear()
 
     ms_per_step = 1e3 * elapsed / args.steps
     value = world * (W * H / 1e6) / (elapsed / args.steps)
@@ -1086,6 +1135,10 @@ def main():
                        "the [P,3] dL/drgb factors + all-reduce of the 11 non-SH floats; SH gradient rows rebuilt on "
                        "every rank), complete inside the step" if world > 1 else "")},
     }
+    if dumped is not None:
+        result["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped,
+                                  "what": "the last timed step's results, [full shape, written shape] of each float32 .npy; "
+                                          "larger outputs keep a fixed seeded sample of rows / pixels (dump_outputs())"}
 
     if world == 1 and (P, W, H) == (1_000_000, 1920, 1080):
         # what an N-rank run of the same line WOULD exchange per GPU and step (formula of view_parallel.FactoredGradExchange.bytes_per_step
