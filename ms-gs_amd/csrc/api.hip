@@ -675,8 +675,12 @@ int forward_stage2_impl(const msgs_view_t* view, const msgs_gaussians_t* g, cons
         tm.begin(MSGS_K_SLAB_B);
         uint32_t* offs_b = (uint32_t*)(geom + GL.offs_b);
         HIP_TRY(launch_slab_recount(vp, P, geom, open_bits, open_list, D, D_dev, s));
+        // the recount has consumed the cell ranges stage 1's scan left in offs_b (pad[0] = 1) and left its counts there: this
+        // scan clears pad[0] (block 0, behind the recount in stream order), so that a second stage 2 on this geom — the redo of
+        // a speculative one the view outgrew — recounts without the cell prefilter instead of decoding scan offsets as ranges
         HIP_TRY(exclusive_scan_u32(offs_b, nullptr, offs_b, P, (uint64_t*)(geom + GL.scan_b), &hdr->total_b, s, nullptr, nullptr, 0,
-                                   (const uint32_t*)(geom + GL.nvalid), &hdr->DB, (uint64_t)cap_b, nullptr, heavy_q, &hdr->pad0));
+                                   (const uint32_t*)(geom + GL.nvalid), &hdr->DB, (uint64_t)cap_b, nullptr, heavy_q, &hdr->pad0,
+                                   0xFFFFFFFFu, nullptr, &hdr->pad[0]));
         ZeroJob zjB{nullptr, 0, nullptr, 0};
         const bool sortB_prezeroed = radix_sort_zero_region(cap_b, 0, tbits, scratch + SL.sort, &zjB.p0, &zjB.n0);
         HIP_TRY(launch_emit(vp, P, geom, keys_a, ids_a, cap_b, s, zjB, &hdr->DB, keys16, heavy_q, 2, open_bits));

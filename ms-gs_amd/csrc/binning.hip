@@ -482,7 +482,8 @@ __global__ __launch_bounds__(256) void slab_recount_kernel(ViewParams vp, int P,
     const int n_words = (n_tiles + 31) / 32;
     const bool in_lds = n_words <= SLAB_LDS_WORDS;                             // workgroup-uniform
     // coarse cells: 2^cs x 2^ct tiles each, at most 8 x 8 of them (ViewParams: the same shifts as preprocess_kernel's ranges)
-    const bool ranged = vp.cell_sx >= 0 && hdr->pad[0] == 1u;       // (pad[0]: the scan of THIS forward delivered the ranges)
+    // (pad[0]: stage 1's scan of THIS forward delivered the ranges and no recount has consumed them yet — slab B's scan clears it)
+    const bool ranged = vp.cell_sx >= 0 && hdr->pad[0] == 1u;
     const int cs = vp.cell_sx, ct = vp.cell_sy;
     const bool use_cells = ranged && in_lds && n_open <= 1024u;                // (many open tiles: every cell is set anyway)
     if (threadIdx.x < 2) s_cells[threadIdx.x] = use_cells ? 0u : 0xFFFFFFFFu;

@@ -102,7 +102,7 @@ struct SlabHeader {
     uint32_t n_open;          // tiles in which some pixel was still blending at the end of its slab-A list (blend A, atomics)
     uint32_t pad0;
     uint64_t total_b;         // B's scan total (64-bit twin of DB)
-    uint32_t pad[8];
+    uint32_t pad[8];          // pad[0]: 1 while offs_b holds the cell ranges of stage 1's scan (set by it, cleared by B's scan)
 };
 static_assert(sizeof(SlabHeader) == 64, "SlabHeader layout");
 
@@ -634,7 +634,8 @@ hipError_t exclusive_scan_u32(const uint32_t* in, const uint32_t* gather, uint32
                               const uint32_t* extra = nullptr,    // extra: two device words forwarded with the status
                               uint32_t* zero_word = nullptr,      // zero_word: one device word cleared on behalf of a later launch
                               uint32_t* overflow_flag = nullptr, uint32_t in_mask = 0xFFFFFFFFu, uint32_t* side_out = nullptr,
-                              uint32_t* side_flag = nullptr);    // side_flag: set to 1 when side_out was written // set to 1 when the total exceeds `clamp`
+                              uint32_t* side_flag = nullptr);    // overflow_flag: set to 1 when the total exceeds `clamp`;
+                                                                  // side_flag: set to 1 when side_out is written, to 0 otherwise
 // device-side fill with zeros (sort.hip): an ordinary kernel launch — hipMemsetAsync costs ~10 us of queue latency per
 // call on this runtime (barrier packets around the fill), four of them per step were 3 % of the C3 step
 hipError_t launch_zero(void* ptr, size_t bytes, hipStream_t s);     // ptr and bytes multiples of 4

@@ -89,7 +89,8 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_reduce_kernel(const uint32_
                                                                    uint32_t* __restrict__ side_out, uint32_t* __restrict__ side_flag) {
     __shared__ uint32_t s_wave[4];
     if (n_ptr) n = (int64_t)*n_ptr;
-    if (side_flag && blockIdx.x == 0 && threadIdx.x == 0) *side_flag = 1u;
+    // side_flag: 1 when this scan delivers the side values, 0 when it scans over them (they are counts from here on)
+    if (side_flag && blockIdx.x == 0 && threadIdx.x == 0) *side_flag = side_out ? 1u : 0u;
     const int64_t base = (int64_t)blockIdx.x * SCAN_CHUNK + (int64_t)threadIdx.x * SCAN_ITEMS;
     uint32_t v[SCAN_ITEMS];
     if (gather) {
@@ -426,7 +427,7 @@ hipError_t exclusive_scan_u32(const uint32_t* in, const uint32_t* gather, uint32
     // with a gather the first pass leaves the gathered values in `out` and the second pass scans `out` in place
     const bool stage = gather != nullptr;
     hipLaunchKernelGGL(scan_reduce_kernel, dim3((unsigned)nb), dim3(SCAN_THREADS), 0, s, in, gather, n, partials,
-                       stage ? out : (uint32_t*)nullptr, n_ptr, in_mask, side_out, side_out ? side_flag : (uint32_t*)nullptr);
+                       stage ? out : (uint32_t*)nullptr, n_ptr, in_mask, side_out, side_flag);
     hipLaunchKernelGGL(scan_apply_fused_kernel, dim3((unsigned)nb), dim3(SCAN_THREADS), 0, s,
                        stage ? (const uint32_t*)out : in, out, n, (const uint64_t*)partials, nb, n_ptr, total, status,
                        (volatile uint64_t*)host_mapped, ticket, clamped_total, clamp, extra, zero_word, overflow_flag);

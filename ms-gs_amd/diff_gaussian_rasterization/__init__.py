@@ -294,6 +294,12 @@ class _LRU(dict):
         while len(self) > self.cap:
             super().__delitem__(next(iter(self)))
 
+    def setdefault(self, k, default=None):
+        # (dict.setdefault would insert without the cap)
+        if k not in self:
+            self[k] = default
+        return self[k]
+
 
 _last_instances = _LRU()
 # ... and per (device, W, H, filters) whatever the model size: (instances, P) of the latest forward.  The reference's training loop
@@ -316,6 +322,12 @@ def _instance_guess(key):
     if not 0.8 <= ratio <= 1.25:        # another model altogether (D does not scale with P across scenes): no guess
         return None
     return int(D * ratio) + 1
+
+
+def _capacity(guess):
+    """instances the speculative stage 2 of a call with this guess has room for at least (+12.5 % and a constant margin; the
+    library sizes it from the buffers' bytes, which _bytes may round up); a view with more takes the redo on exact buffers"""
+    return guess + (guess >> 3) + 4096
 
 
 def _note_instances(key, D, guess):
@@ -528,6 +540,7 @@ class _PendingForward:
             _note_info(self.key)
             forward_stats["forwards"] += 1
             if not done.value:                          # first frame of this shape, or the scene grew past the margin
+                # (the redo runs stage 2 again on the same geom: see _forward_impl for what the truncated run left there)
                 forward_stats["non_speculative"] += 1
                 dev, W, H = call.device, call.W, call.H
                 color, acc_ps, depth = self.outs
@@ -586,7 +599,7 @@ def _forward_impl(call, grad_rec=None, backward_follows=False):
         # forward (stage-1 scratch | stage-2 scratch); every part starts on a 256-byte boundary
         n_bin = n_s2 = 0
         if guess is not None:
-            cap = guess + (guess >> 3) + 4096
+            cap = _capacity(guess)
             n_bin, n_s2 = _stage2_bytes(cap, W, H, frac)
         keep = _bytes(_a256(n_geom) + _a256(n_img) + n_bin, dev)
         geom, image = keep[:n_geom], keep[_a256(n_geom):_a256(n_geom) + n_img]
@@ -630,6 +643,11 @@ def _forward_impl(call, grad_rec=None, backward_follows=False):
         del scratch1, scratch2, tmp
         forward_stats["forwards"] += 1
         if not done.value:                              # first frame of this shape, or the scene grew past the margin
+            # Stage 2 again, on the geom a truncated speculative stage 2 (capacity < D) may have written to.  What that run left
+            # there is rewritten or no longer read as input (tests/test_stage2_routes_gpu.py): the SlabHeader counts, the open-tile
+            # bitmap and n_open are reset by slab_split_kernel; the heavy-queue word is cleared before each emit; offs_b /
+            # scan_b are recomputed by slab B's recount and scan; and the flag that marks offs_b as stage 1's cell ranges
+            # (SlabHeader pad[0]) was cleared by the first run's slab B scan, so this run recounts without the cell prefilter.
             forward_stats["non_speculative"] += 1
             nb_, ns_ = _stage2_bytes(D, W, H, frac)
             binning = _bytes(nb_, dev)

@@ -228,3 +228,19 @@ def test_config_c5_stress_4k():
     check_backward(pc, m2, og, "C5", flagged=orc.borderline_gaussians, rtol=TIGHT_RTOL, rtol_by_key=grad_ceilings("C5"),
                    q99_tol=FULL_Q99)
     check_against_truth("C5", pc.seen, cam, st, bg, dL, out, pc, m2, orc, og)
+    # the same view on the product's default slab policy: two priming frames publish D / D_trav, the third runs in depth slabs;
+    # checked against the same oracle run
+    from route_utils import slab_stats
+    prev, dgr.slab_policy = dgr.slab_policy, "adaptive"
+    try:
+        dgr._fb_stats.clear(); dgr._fb_tag_of.clear(); dgr._fb_key_of.clear()      # (no publication of an earlier test)
+        for _ in range(2):
+            hip_render(sc, cam, st, bg)
+        out, pc, m2 = hip_render(sc, cam, st, bg, dL)
+    finally:
+        dgr.slab_policy = prev
+    s = slab_stats(out["render"].grad_fn)
+    assert s["active"] == 1 and s["overflow"] == 0, s
+    check_forward(out, orc, "C5 adaptive slabs")
+    check_backward(pc, m2, og, "C5 adaptive slabs", flagged=orc.borderline_gaussians, rtol=TIGHT_RTOL,
+                   rtol_by_key=grad_ceilings("C5"), q99_tol=FULL_Q99)

@@ -7,6 +7,7 @@ import torch
 
 import scenes
 from parity_utils import PIPE
+from route_utils import non_speculative, reset_forward_state
 
 pytestmark = pytest.mark.gpu
 LEAVES = ("_xyz", "_features_dc", "_features_rest", "_opacity", "_scaling", "_rotation")
@@ -43,11 +44,12 @@ def test_train_views_equals_the_serial_loop_bit_for_bit(share_getters, accumulat
     from synthetic_model import SyntheticGaussians
     sc, cams, dLs = _ball()
     bg = torch.tensor([0.1, 0.2, 0.3], device="cuda")
-    dgr._last_instances.clear()
+    reset_forward_state()
     ref_pc, ref_outs, ref_m2 = _serial_train(sc, cams, dLs, bg)
     for attempt in range(2):                      # first: no guess for this shape yet; second: speculative stage 2
         if attempt == 0:
-            dgr._last_instances.clear()
+            reset_forward_state()
+        n0 = non_speculative()
         pc = SyntheticGaussians(sc, "cuda")
         pipe = ViewPipeline("cuda", n_streams=n_streams)
         kept = []
@@ -65,6 +67,9 @@ def test_train_views_equals_the_serial_loop_bit_for_bit(share_getters, accumulat
             assert torch.equal(vs[i].grad, ref_m2[i]), (attempt, i, "means2D grad")
         for n in LEAVES:
             assert torch.equal(getattr(pc, n).grad, getattr(ref_pc, n).grad), (attempt, n)
+        # attempt 0: the views launched before the first count lands take the first-call route; attempt 1: not every view redoes
+        redone = non_speculative() - n0
+        assert redone >= 1 if attempt == 0 else redone < len(cams), (attempt, redone)
 
 
 def test_render_views_forward_only_and_consume():
@@ -101,12 +106,14 @@ def test_guess_exceeded_inside_the_pipeline_is_redone_at_resolve_time():
     sc, cams, dLs = _ball(n_views=4)
     bg = torch.tensor([0.3, 0.1, 0.0], device="cuda")
     big = dict(ST)
-    dgr._last_instances.clear()
+    reset_forward_state()
     ref_pc, ref_outs, _ = _serial_train(sc, cams, dLs, bg, big)
     D_true = [o["render"].grad_fn.state[3] for o in ref_outs]
-    # a guess 20x too small: every view's speculative stage 2 is truncated and has to be redone
+    # a guess 20x too small: the speculative stage 2 of every view launched before a count has landed (the first two, one per
+    # stream) is truncated and has to be redone
     for k in list(dgr._last_instances):
         dgr._last_instances[k] = max(4096, min(D_true) // 20)
+    n0 = non_speculative()
     pc = SyntheticGaussians(sc, "cuda")
     kept = []
 
@@ -115,6 +122,7 @@ def test_guess_exceeded_inside_the_pipeline_is_redone_at_resolve_time():
         kept.append(pkg)
     ViewPipeline("cuda").train_views(cams, pc, PIPE, bg, bwd, **big)
     torch.cuda.synchronize()
+    assert non_speculative() - n0 >= 2
     for o, r, D in zip(kept, ref_outs, D_true):
         assert o["render"].grad_fn.state.resolve()[3] == D
         for k in OUT_KEYS:

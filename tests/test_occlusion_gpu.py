@@ -12,6 +12,7 @@ import torch
 
 import scenes
 from parity_utils import PIPE
+from route_utils import non_speculative, reset_forward_state
 
 pytestmark = pytest.mark.gpu
 LEAVES = ("_xyz", "_features_dc", "_features_rest", "_opacity", "_scaling", "_rotation")
@@ -37,7 +38,7 @@ def _run(sc, cam, st, bg, dL, occlusion, backward=True, fused=False):
     from synthetic_model import SyntheticGaussians
     prev = dgr._C.lib.msgs_set_occlusion(1 if occlusion else 0)
     try:
-        dgr._last_instances.clear()
+        reset_forward_state()
         pc = SyntheticGaussians(sc, "cuda", requires_grad=backward)
         fn = render_fused if fused else render
         if backward:
@@ -256,7 +257,7 @@ def test_a_view_that_really_closes_blocks_matches_the_oracle():
     dL = scenes.grad_seed(W, H, 5)
     prev = dgr._C.lib.msgs_set_occlusion(1)
     try:
-        dgr._last_instances.clear()
+        reset_forward_state()
         out, pc, m2 = hip_render(sc, cam, PLAIN, bg, dL)
         stats = _stats(out["render"].grad_fn)
     finally:
@@ -282,7 +283,7 @@ def test_two_views_in_flight_on_a_scene_that_closes_blocks():
     bg = torch.tensor([0.4, 0.1, 0.2], device="cuda")
     try:
         prev = dgr._C.lib.msgs_set_occlusion(0)
-        dgr._last_instances.clear()
+        reset_forward_state()
         ref_pc = SyntheticGaussians(sc, "cuda")
         ref, ref_m2 = [], []
         for cam, dL in zip(cams, dLs):
@@ -295,7 +296,8 @@ def test_two_views_in_flight_on_a_scene_that_closes_blocks():
         dgr._C.lib.msgs_set_occlusion(1)
         for attempt in range(2):                  # no guess yet / speculative stage 2 from the cut count
             if attempt == 0:
-                dgr._last_instances.clear()
+                reset_forward_state()
+            n0 = non_speculative()
             pc = SyntheticGaussians(sc, "cuda")
             kept = []
 
@@ -313,6 +315,12 @@ def test_two_views_in_flight_on_a_scene_that_closes_blocks():
                 assert torch.equal(getattr(pc, n).grad, getattr(ref_pc, n).grad), (attempt, n)
             D_on = dgr._resolve(kept[0]["render"].grad_fn.state)[3]
             assert D_on < D_off, (D_on, D_off)
+            # attempt 0: the views launched before the first count lands have no guess; attempt 1: the same camera, every view
+            # fits the cut count its key left
+            if attempt == 0:
+                assert non_speculative() - n0 >= 1
+            else:
+                assert non_speculative() - n0 == 0
     finally:
         dgr._C.lib.msgs_set_occlusion(prev)
 
@@ -366,8 +374,7 @@ def test_the_pass_always_runs_and_the_heavy_queue_hint_follows_what_the_views_cl
     info = (C.c_int64 * 8)()
     key = (0, 3000, W, H, 0, 0)
     # (1) alternating sweep starting on the view that closes nothing: the closing view is cut on every visit
-    dgr._occ_hot.clear()
-    dgr._last_instances.clear()
+    reset_forward_state()
     pc = SyntheticGaussians(walls, "cuda", requires_grad=False)
     prev = dgr._C.lib.msgs_set_occlusion(0)
     with torch.no_grad():
@@ -389,8 +396,7 @@ def test_the_pass_always_runs_and_the_heavy_queue_hint_follows_what_the_views_cl
     assert all(torch.equal(imgs[0], im) for im in imgs[1:])
     assert dgr._occ_hot[key] >= dgr.HEAVY_QUEUE_MEMORY - 1            # the queue stays on for this key
     # (2) a quiet scene: the hint switches the queue off after HEAVY_QUEUE_MEMORY calls, the image does not change
-    dgr._occ_hot.clear()
-    dgr._last_instances.clear()
+    reset_forward_state()
     pc = SyntheticGaussians(quiet, "cuda", requires_grad=False)
     imgs, off = [], []
     with torch.no_grad():

@@ -7,6 +7,7 @@ import torch
 
 import scenes
 from parity_utils import (PIPE, check_backward, check_forward, hip_render, rel_err, small_scene)
+from route_utils import capacity, non_speculative, reset_forward_state
 
 pytestmark = pytest.mark.gpu
 
@@ -299,19 +300,24 @@ def test_forward_capacity_guess_paths_give_identical_results():
     key = (torch.cuda.current_device(), 4000, W, H, 0, 0)     # (device, P, W, H, filter_small, filter_large)
 
     def run(seed_guess):
-        dgr._last_instances.clear()
+        reset_forward_state()
         if seed_guess is not None:
             dgr._last_instances[key] = seed_guess
+        n0 = non_speculative()
         out, pc, m2 = hip_render(sc, cam, ST0, bg, dL)
-        return out, pc, m2, dgr._last_instances[key]
-    ref, pref, mref, D = run(None)
-    assert D > 0
+        return out, pc, m2, dgr._last_instances[key], non_speculative() - n0
+    ref, pref, mref, D, redone = run(None)
+    assert D > 0 and redone == 1                                 # no guess: the two-call path
+    routes = []
     for guess in (1, max(D // 2, 1), D, 10 * D):
-        out, pc, m2, D2 = run(guess)
+        out, pc, m2, D2, redone = run(guess)
+        assert redone == int(capacity(guess) < D), (guess, D, redone)
+        routes.append(redone)
         assert D2 >= D
         for k in ("render", "acc_pixel_size", "depth", "radii", "pixel_sizes"):
             assert torch.equal(out[k], ref[k]), (k, guess)
         assert rel_err(pc._xyz.grad, pref._xyz.grad) <= 1e-4 and rel_err(m2, mref) <= 1e-4
+    assert routes[0] == 1 and routes[-1] == 0, (D, routes)      # both routes taken
 
 
 @pytest.mark.parametrize("W,H", [(203, 117), (120, 67), (43, 29)])

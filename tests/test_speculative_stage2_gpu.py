@@ -6,52 +6,54 @@ import torch
 
 import scenes
 from parity_utils import PIPE, small_scene
+from route_utils import non_speculative, reset_forward_state
 
 pytestmark = pytest.mark.gpu
 LEAVES = ("_xyz", "_features_dc", "_features_rest", "_opacity", "_scaling", "_rotation")
 ST = dict(filter_small=False, filter_large=False, fade_size=1.0)
 
 
-def _run(sc, cam, dL, mod, bg):
+def _run(sc, cam, dL, mod, bg, redo):
+    """one render + backward; `redo`: whether it must take the first-call / redo route (exact buffers) or the speculative one"""
     from gaussian_renderer import render
     from synthetic_model import SyntheticGaussians
     pc = SyntheticGaussians(sc, "cuda")
+    n0 = non_speculative()
     out = render(cam.to("cuda"), pc, PIPE, bg.cuda(), scaling_modifier=mod, **ST)
     out["render"].backward(dL.cuda())
+    assert non_speculative() - n0 == int(redo), (mod, redo)
     D = out["render"].grad_fn.state[3]
     return out, {n: getattr(pc, n).grad.clone() for n in LEAVES}, D
 
 
 def test_guess_exceeded_then_redone_equals_a_fresh_render():
-    import diff_gaussian_rasterization as dgr
     W, H = 400, 300
     sc, cam = small_scene(40000, W, H, 71, scale_k=0.004 * 1920.0 / W * 0.4)
     dL = scenes.grad_seed(W, H, 71)
     bg = torch.tensor([0.1, 0.0, 0.3])
-    dgr._last_instances.clear()
-    a, ga, Da = _run(sc, cam, dL, 0.3, bg)            # first frame: no guess, sequential route
-    b, gb, Db = _run(sc, cam, dL, 0.3, bg)            # guess == D: speculative stage 2 stands
+    reset_forward_state()
+    a, ga, Da = _run(sc, cam, dL, 0.3, bg, True)      # first frame: no guess, sequential route
+    b, gb, Db = _run(sc, cam, dL, 0.3, bg, False)     # guess == D: speculative stage 2 stands
     assert Da == Db and torch.equal(a["render"], b["render"]) and all(torch.equal(ga[n], gb[n]) for n in LEAVES)
-    c, gc, Dc = _run(sc, cam, dL, 1.5, bg)            # footprints 5x larger: D far beyond the 12.5 % margin -> redone
+    c, gc, Dc = _run(sc, cam, dL, 1.5, bg, True)      # footprints 5x larger: D far beyond the 12.5 % margin -> redone
     assert Dc > 1.5 * Db
-    dgr._last_instances.clear()
-    d, gd, Dd = _run(sc, cam, dL, 1.5, bg)            # fresh: exact buffers from the start
+    reset_forward_state()
+    d, gd, Dd = _run(sc, cam, dL, 1.5, bg, True)      # fresh: exact buffers from the start
     assert Dc == Dd
     for k in ("render", "acc_pixel_size", "depth", "radii", "pixel_sizes"):
         assert torch.equal(c[k], d[k]), k
     assert all(torch.equal(gc[n], gd[n]) for n in LEAVES)
-    e, ge, De = _run(sc, cam, dL, 0.3, bg)            # and back: a guess far too large is fine
+    e, ge, De = _run(sc, cam, dL, 0.3, bg, False)     # and back: a guess far too large is fine
     assert De == Da and torch.equal(e["render"], a["render"]) and all(torch.equal(ge[n], ga[n]) for n in LEAVES)
 
 
 def test_nothing_rendered_with_a_stale_guess():
-    import diff_gaussian_rasterization as dgr
     from gaussian_renderer import render
     from synthetic_model import SyntheticGaussians
     W, H = 128, 96
     sc, cam = small_scene(5000, W, H, 72)
     bg = torch.tensor([0.2, 0.4, 0.6])
-    dgr._last_instances.clear()
+    reset_forward_state()
     pc = SyntheticGaussians(sc, "cuda")
     render(cam.to("cuda"), pc, PIPE, bg.cuda(), **ST)                      # sets the guess
     with torch.no_grad():
