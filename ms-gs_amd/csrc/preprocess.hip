@@ -277,19 +277,31 @@ __device__ __forceinline__ void act_scales(const msgs_gaussians_t& g, int i, flo
 #pragma unroll
     for (int k = 0; k < 3; ++k) { const float x = g.scales[3 * i + k]; s[k] = g.raw_params == 1 ? expf(x) : x; }   // torch.exp
 }
-// q = raw / max(||raw||, 1e-12) (torch.nn.functional.normalize); returns the norm used
+// q = raw / max(||raw||, 1e-12) (torch.nn.functional.normalize); returns ||raw|| BEFORE the clamp, so that the backward
+// can tell whether the clamp was active (normalize_backward)
 __device__ __forceinline__ float act_rotation(const msgs_gaussians_t& g, int i, float* q) {
     const float4 q4 = reinterpret_cast<const float4*>(g.rotations)[i];
     q[0] = q4.x; q[1] = q4.y; q[2] = q4.z; q[3] = q4.w;
     if (g.raw_params == 0) return 1.0f;
     if (g.raw_params == 2) {         // chained mode: q is already normalised; the norm comes from the raw quaternion
         const float4 r4 = reinterpret_cast<const float4*>(g.rotations_raw)[i];
-        return fmaxf(sqrtf(r4.x * r4.x + r4.y * r4.y + r4.z * r4.z + r4.w * r4.w), 1e-12f);
+        return sqrtf(r4.x * r4.x + r4.y * r4.y + r4.z * r4.z + r4.w * r4.w);
     }
-    const float n = fmaxf(sqrtf(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]), 1e-12f);
+    const float rn = sqrtf(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+    const float n = fmaxf(rn, 1e-12f);
 #pragma unroll
     for (int k = 0; k < 4; ++k) q[k] = q[k] / n;
-    return n;
+    return rn;
+}
+// dL/draw from dL/dq (in place), q = raw / max(rn, 1e-12) as act_rotation formed it: torch's x / norm.clamp_min(eps) passes
+// no gradient through the norm where the clamp is active (rn < eps; at rn == eps it still does), so there the backward is
+// g / eps, not the projection (g - q (q.g)) / rn.  NaN norms take the projection (fmaxf's result is then eps, but the
+// gradient is NaN either way).
+__device__ __forceinline__ void normalize_backward(const float* q, float rn, float* dq) {
+    const float n = fmaxf(rn, 1e-12f);
+    const float dotq = rn < 1e-12f ? 0.f : q[0] * dq[0] + q[1] * dq[1] + q[2] * dq[2] + q[3] * dq[3];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) dq[k] = (dq[k] - q[k] * dotq) / n;
 }
 
 // SH rows of one wave from the split dc / rest parameters into LDS rows [dc(3) | rest(45)] (= the torch.cat of
@@ -910,12 +922,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void p
             dq[2] = 2.f * (-2.f * y * dR[0][0] + x * dR[0][1] + r * dR[0][2] + x * dR[1][0] + z * dR[1][2] - r * dR[2][0] + z * dR[2][1] - 2.f * y * dR[2][2]);
             dq[3] = 2.f * (-2.f * z * dR[0][0] - r * dR[0][1] + x * dR[0][2] + r * dR[1][0] - 2.f * z * dR[1][1] + y * dR[1][2] + x * dR[2][0] + y * dR[2][1]);
             if (raw) {
-                // through exp: d/d(log s) = s * d/ds;  through normalize: (g - q (q.g)) / ||raw||
+                // through exp: d/d(log s) = s * d/ds;  through normalize: normalize_backward
 #pragma unroll
                 for (int j = 0; j < 3; ++j) dscale[j] = dscale[j] * sact[j];
-                const float dotq = r * dq[0] + x * dq[1] + y * dq[2] + z * dq[3];
-                dq[0] = (dq[0] - r * dotq) / qnorm; dq[1] = (dq[1] - x * dotq) / qnorm;
-                dq[2] = (dq[2] - y * dotq) / qnorm; dq[3] = (dq[3] - z * dotq) / qnorm;
+                const float qv[4] = {r, x, y, z};
+                normalize_backward(qv, qnorm, dq);
             }
         }
     }
