@@ -271,8 +271,8 @@ int msgs_forward_stage2(const msgs_view_t* view, const msgs_gaussians_t* g,
  * msgs_backward called with msgs_grads_t.scratch_is_clear = 1 saves the fill launch. */
 
 /* ---- backward -------------------------------------------------------------------------------- */
-/* dL_dcolor is [3,H,W].  acc_pixel_size / depth / pixel_sizes carry no gradient (they never
- * enter the reference's loss, /root/reference/train.py:205-216). */
+/* dL_dcolor is [3,H,W].  acc_pixel_size / depth / pixel_sizes carry no gradient here (they never
+ * enter the reference's loss, /root/reference/train.py:205-216); msgs_backward_with_depth adds the depth map's. */
 int msgs_backward(const msgs_view_t* view, const msgs_gaussians_t* g,
                   const int32_t* radii,
                   const void* geom, size_t geom_bytes,
@@ -283,6 +283,23 @@ int msgs_backward(const msgs_view_t* view, const msgs_gaussians_t* g,
                   void* scratch, size_t scratch_bytes,
                   const msgs_grads_t* grads,
                   const msgs_timing_t* timing, void* stream);
+
+/* msgs_backward_with_depth: msgs_backward plus the gradient of the depth map (D_p = sum_i z_i alpha_i T_i,
+ * no background term).  dL_ddepth is [H,W] float32, NULL = none — then exactly msgs_backward (same kernels, same bits).
+ * Non-NULL: the depth variants of the blend-backward and per-Gaussian kernels run; depth's share z_i dL/dD enters
+ * dL/dalpha (-> opacity, conic, mean2D and everything behind them) and dL/dz_i = sum_p dL/dD alpha_i T_i reaches dL/dmeans3D
+ * through the view matrix.  acc_pixel_size, radii and pixel_sizes stay without gradient.  In the verification mode
+ * (msgs_set_deterministic) the scratch buffer must hold msgs_backward_scratch_bytes_deterministic_depth(P, D) bytes. */
+int msgs_backward_with_depth(const msgs_view_t* view, const msgs_gaussians_t* g,
+                             const int32_t* radii,
+                             const void* geom, size_t geom_bytes,
+                             int64_t num_instances,
+                             const void* binning, size_t binning_bytes,
+                             const void* image_state, size_t image_bytes,
+                             const float* dL_dcolor, const float* dL_ddepth,
+                             void* scratch, size_t scratch_bytes,
+                             const msgs_grads_t* grads,
+                             const msgs_timing_t* timing, void* stream);
 
 /* msgs_backward_per_gaussian: the per-Gaussian half of msgs_backward ALONE (2-D covariance backward, projection, SH,
  * scale / quaternion chain — upstream's computeCov2DCUDA + preprocessCUDA backward, SURVEY 2.2 K8 + K9) on per-Gaussian
@@ -348,6 +365,8 @@ int msgs_blend_lane_stats(const msgs_view_t* view, const void* geom, size_t geom
 int msgs_set_deterministic(int32_t on);
 int msgs_get_deterministic(void);
 size_t msgs_backward_scratch_bytes_deterministic(int32_t P, int64_t D);
+/* the same for msgs_backward_with_depth with a non-NULL dL_ddepth (ten sums per tile entry instead of nine) */
+size_t msgs_backward_scratch_bytes_deterministic_depth(int32_t P, int64_t D);
 
 /* Which of the two blend-backward kernels msgs_backward launches: 0 (default) = by tile count (one wave per tile from
  * 4096 tiles up, four waves per tile below), 1 | 2 = force one — for the parity tests and A/B measurements.  Initial

@@ -111,6 +111,7 @@ size_t msgs_backward_scratch_bytes(int32_t P) {
     return align256(GRAD_REC_BYTES * (size_t)(P > 0 ? P : 1));
 }
 size_t msgs_backward_scratch_bytes_deterministic(int32_t P, int64_t D) { return DetScratch(P, D).total; }
+size_t msgs_backward_scratch_bytes_deterministic_depth(int32_t P, int64_t D) { return DetScratch(P, D, DET_INST_FLOATS_DEPTH).total; }
 
 static std::atomic<int> g_deterministic{[] { const char* e = getenv("MSGS_DETERMINISTIC"); return (e && e[0] == '1') ? 1 : 0; }()};
 int msgs_set_deterministic(int32_t on) { return g_deterministic.exchange(on ? 1 : 0); }
@@ -712,6 +713,14 @@ int msgs_backward(const msgs_view_t* view, const msgs_gaussians_t* g, const int3
                   size_t geom_bytes, int64_t D, const void* binning_v, size_t binning_bytes, const void* image_v,
                   size_t image_bytes, const float* dL_dcolor, void* scratch_v, size_t scratch_bytes,
                   const msgs_grads_t* grads, const msgs_timing_t* timing, void* stream) {
+    return msgs_backward_with_depth(view, g, radii, geom_v, geom_bytes, D, binning_v, binning_bytes, image_v, image_bytes,
+                                    dL_dcolor, nullptr, scratch_v, scratch_bytes, grads, timing, stream);
+}
+
+int msgs_backward_with_depth(const msgs_view_t* view, const msgs_gaussians_t* g, const int32_t* radii, const void* geom_v,
+                             size_t geom_bytes, int64_t D, const void* binning_v, size_t binning_bytes, const void* image_v,
+                             size_t image_bytes, const float* dL_dcolor, const float* dL_ddepth, void* scratch_v,
+                             size_t scratch_bytes, const msgs_grads_t* grads, const msgs_timing_t* timing, void* stream) {
     int rc = check_inputs(view, g);
     if (rc) return rc;
     if (!grads || !dL_dcolor) return MSGS_ERR_INVALID_ARG;
@@ -721,7 +730,9 @@ int msgs_backward(const msgs_view_t* view, const msgs_gaussians_t* g, const int3
     const bool det = g_deterministic.load() != 0;
     if (geom_bytes < msgs_geom_bytes(P) || binning_bytes < msgs_binning_bytes(D, W, H) ||
         image_bytes < msgs_image_bytes(W, H) ||
-        scratch_bytes < (det ? msgs_backward_scratch_bytes_deterministic(P, D) : msgs_backward_scratch_bytes(P)))
+        scratch_bytes < (det ? (dL_ddepth ? msgs_backward_scratch_bytes_deterministic_depth(P, D)
+                                          : msgs_backward_scratch_bytes_deterministic(P, D))
+                             : msgs_backward_scratch_bytes(P)))
         return MSGS_ERR_CAPACITY;
     if (g->shs && !g->raw_params && !grads->dL_dshs) return MSGS_ERR_INVALID_ARG;
     // raw modes: either both SH gradient tensors, or neither plus dL_dcolors (factored SH gradient, msgs.h)
@@ -763,19 +774,19 @@ int msgs_backward(const msgs_view_t* view, const msgs_gaussians_t* g, const int3
     if (det)      // grad_rec is the first region of the deterministic scratch layout
         HIP_TRY(launch_blend_backward_det(vp, P, geom, (const uint32_t*)(binning + BL.ids), D,
                                           (const uint2*)(binning + BL.ranges), (const float*)(image + IL.final_T),
-                                          (const uint32_t*)(image + IL.n_contrib), dL_dcolor, (char*)scratch_v, s));
+                                          (const uint32_t*)(image + IL.n_contrib), dL_dcolor, (char*)scratch_v, s, dL_ddepth));
     else
         HIP_TRY(launch_blend_backward(vp, geom, (const uint32_t*)(binning + BL.ids), (const uint2*)(binning + BL.ranges),
                                       (const float*)(image + IL.final_T), (const uint32_t*)(image + IL.n_contrib),
-                                      dL_dcolor, grad_rec, s, (const uint32_t*)(image + IL.tile_order)));
+                                      dL_dcolor, grad_rec, s, (const uint32_t*)(image + IL.tile_order), dL_ddepth));
     tm.end(MSGS_K_BLEND_BWD);
     if ((rc = debug_sync(view, s))) return rc;
 
     tm.begin(MSGS_K_PREPROCESS_BWD);
-    if (det)      // the nine TEXTBOOK sums per Gaussian ([P, 9] doubles) as they are
-        HIP_TRY(launch_preprocess_backward(vp, *g, radii, geom, grad_rec, *grads, s, true));
+    if (det)      // the nine TEXTBOOK sums per Gaussian ([P, 9] doubles; [P, 10] with depth) as they are
+        HIP_TRY(launch_preprocess_backward(vp, *g, radii, geom, grad_rec, *grads, s, true, dL_ddepth != nullptr));
     else
-        HIP_TRY(launch_preprocess_backward(vp, *g, radii, geom, grad_rec, *grads, s));
+        HIP_TRY(launch_preprocess_backward(vp, *g, radii, geom, grad_rec, *grads, s, false, dL_ddepth != nullptr));
     tm.end(MSGS_K_PREPROCESS_BWD);
     return debug_sync(view, s);
 }

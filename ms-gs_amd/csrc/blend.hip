@@ -531,18 +531,64 @@ __device__ __forceinline__ float row_reduce_scatter9(const BwdSums& v) {
 __device__ __forceinline__ uint32_t row_reduce_component(int l) {
     return (l & 2) ? 8u : (uint32_t)(4 * ((l >> 3) & 1) + 2 * ((l >> 2) & 1) + (l & 1));
 }
+// Depth variant (ten sums, the tenth = sum alpha T dL/dD): v0..v7 as in row_reduce_scatter9; v8 and v9 share the lanes
+// whose bit 1 is set — the first exchange (lane parity) sends v9 from even lanes and v8 from odd ones, so the even lanes
+// all-reduce v8 and the odd lanes v9 with the same three row steps that follow.  Two selects more than row_reduce_scatter9,
+// still one value per lane: lane l holds component comp(l) for (l & 2) == 0, component 8 + (l & 1) otherwise.
+__device__ __forceinline__ float row_reduce_scatter10(const BwdSums& v, float v9) {
+    float a0, a1, a2, a3, b0, b1, t8, keep, send, c, k89, s89;
+    const uint64_t odd = 0xAAAAAAAAAAAAAAAAull, bit1 = 0xCCCCCCCCCCCCCCCCull;
+    asm volatile(
+        "s_nop 1\n\t"
+        "v_cndmask_b32_e64 %[s89], %[v9], %[v8], %[odd]\n\t"
+        "v_cndmask_b32_e64 %[k89], %[v8], %[v9], %[odd]\n\t"
+        "v_add_f32_dpp %[a0], %[v0], %[v0] row_ror:8 row_mask:0xf bank_mask:0xf\n\t"
+        "v_add_f32_dpp %[a1], %[v1], %[v1] row_ror:8 row_mask:0xf bank_mask:0xf\n\t"
+        "v_add_f32_dpp %[a2], %[v2], %[v2] row_ror:8 row_mask:0xf bank_mask:0xf\n\t"
+        "v_add_f32_dpp %[a3], %[v3], %[v3] row_ror:8 row_mask:0xf bank_mask:0xf\n\t"
+        "v_add_f32_dpp %[a0], %[v4], %[v4] row_ror:8 row_mask:0xf bank_mask:0xc\n\t"
+        "v_add_f32_dpp %[a1], %[v5], %[v5] row_ror:8 row_mask:0xf bank_mask:0xc\n\t"
+        "v_add_f32_dpp %[a2], %[v6], %[v6] row_ror:8 row_mask:0xf bank_mask:0xc\n\t"
+        "v_add_f32_dpp %[a3], %[v7], %[v7] row_ror:8 row_mask:0xf bank_mask:0xc\n\t"
+        "v_add_f32_dpp %[t8], %[s89], %[k89] quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+        "v_add_f32_dpp %[b0], %[a0], %[a0] row_half_mirror row_mask:0xf bank_mask:0xf\n\t"
+        "v_add_f32_dpp %[b1], %[a1], %[a1] row_half_mirror row_mask:0xf bank_mask:0xf\n\t"
+        "v_add_f32_dpp %[b0], %[a2], %[a2] row_half_mirror row_mask:0xf bank_mask:0xa\n\t"
+        "v_add_f32_dpp %[b1], %[a3], %[a3] row_half_mirror row_mask:0xf bank_mask:0xa\n\t"
+        "v_add_f32_dpp %[t8], %[t8], %[t8] quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+        "v_cndmask_b32_e64 %[send], %[b1], %[b0], %[odd]\n\t"
+        "v_cndmask_b32_e64 %[keep], %[b0], %[b1], %[odd]\n\t"
+        "v_add_f32_dpp %[t8], %[t8], %[t8] row_ror:4 row_mask:0xf bank_mask:0xf\n\t"
+        "v_add_f32_dpp %[c], %[send], %[keep] quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+        "s_nop 0\n\t"
+        "v_add_f32_dpp %[t8], %[t8], %[t8] row_ror:8 row_mask:0xf bank_mask:0xf\n\t"
+        "v_add_f32_dpp %[c], %[c], %[c] quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+        "v_cndmask_b32_e64 %[c], %[c], %[t8], %[bit1]"
+        : [a0] "=&v"(a0), [a1] "=&v"(a1), [a2] "=&v"(a2), [a3] "=&v"(a3), [b0] "=&v"(b0), [b1] "=&v"(b1),
+          [t8] "=&v"(t8), [keep] "=&v"(keep), [send] "=&v"(send), [c] "=&v"(c), [k89] "=&v"(k89), [s89] "=&v"(s89)
+        : [v0] "v"(v.v0), [v1] "v"(v.v1), [v2] "v"(v.v2), [v3] "v"(v.v3), [v4] "v"(v.v4), [v5] "v"(v.v5),
+          [v6] "v"(v.v6), [v7] "v"(v.v7), [v8] "v"(v.v8), [v9] "v"(v9), [odd] "s"(odd), [bit1] "s"(bit1));
+    return c;
+}
+// component (0..9) that lane l of a row delivers after row_reduce_scatter10
+__device__ __forceinline__ uint32_t row_reduce_component10(int l) {
+    return (l & 2) ? 8u + (uint32_t)(l & 1) : (uint32_t)(4 * ((l >> 3) & 1) + 2 * ((l >> 2) & 1) + (l & 1));
+}
 // Per-pixel backward state and the walk over one wave's compacted entry list (back to front) — shared by the
 // four-waves-per-tile kernel (CROSS_ROW: the pixels of an 8x8 quadrant fill the wave, the four 16-lane rows are added
 // with v_permlane16/32_swap) and the fine-grained kernel (the sixteen pixels of a 4x4 sub-block live in row 0: the row
 // reduction is the whole reduction).  Same arithmetic per pixel in the same order in both.
+// DEPTH (the depth variants, msgs_backward_with_depth): the depth map is a fourth channel with colour z (s_z) and no
+// background — its share z dL/dD enters g_i (so S and dL/dalpha), and a tenth sum alpha T dL/dD = dL/dz goes to record slot 9.
 struct BwdPix {
-    float T, S, dL0, dL1, dL2;
+    float T, S, dL0, dL1, dL2, dLd;
     uint32_t last;
 };
-template <bool CROSS_ROW>
+template <bool CROSS_ROW, bool DEPTH = false>
 __device__ __forceinline__ void backward_walk(const uint16_t* lp, int cnt, int base, const float4* s_r0, const float4* s_r1,
                                               const float2* s_b, const uint32_t* s_id, float pxf, float pyf, BwdPix& st,
-                                              bool alane, uint32_t aoff, grad_acc_t* __restrict__ grad_rec) {
+                                              bool alane, uint32_t aoff, grad_acc_t* __restrict__ grad_rec,
+                                              const float* s_z = nullptr) {
     for (int j = cnt - 1; j >= 0; --j) {
         const int e = lp[j];
         const float4 r0 = s_r0[e], r1 = s_r1[e];
@@ -562,14 +608,18 @@ __device__ __forceinline__ void backward_walk(const uint16_t* lp, int cnt, int b
         const float Tn = st.T * inv;
         st.T = Tn;
         const float dch = alpha_m * Tn;
-        const float sm = fmaf(cb, st.dL2, fmaf(r1.w, st.dL1, r1.z * st.dL0)) - st.S;
+        float gi = fmaf(cb, st.dL2, fmaf(r1.w, st.dL1, r1.z * st.dL0));
+        if constexpr (DEPTH) gi = fmaf(s_z[e], st.dLd, gi);
+        const float sm = gi - st.S;
         const float dL_dalpha = sm * Tn;
         st.S = fmaf(alpha_m, sm, st.S);
         const float q = a_m * dL_dalpha;                       // Q6: gradient passes the 0.99 clamp
         const BwdSums v = {q * dx, q * dy, q * ev.dxx, q * ev.dxy, q * ev.dyy, q, dch * st.dL0, dch * st.dL1, dch * st.dL2};
         // rows by DPP; the four rows with v_permlane16/32_swap (in this latency-bound regime they beat ds_bpermute,
-        // profiles/r1_notes.md); scalar record address, one atomic instruction from nine lanes
-        const float rowv = row_reduce_scatter9(v);
+        // profiles/r1_notes.md); scalar record address, one atomic instruction from nine (depth: ten) lanes
+        float rowv;
+        if constexpr (DEPTH) rowv = row_reduce_scatter10(v, dch * st.dLd);
+        else rowv = row_reduce_scatter9(v);
         const float outv = CROSS_ROW ? cross_row_allreduce(rowv) : rowv;
         const uint32_t gid = __builtin_amdgcn_readfirstlane(s_id[e]);
         grad_acc_t* gdst = grad_rec + (size_t)gid * GRAD_REC_FLOATS;
@@ -581,15 +631,21 @@ __device__ __forceinline__ void backward_walk(const uint16_t* lp, int cnt, int b
 // in preprocess_backward_kernel):
 //   [0] sum q dx  [1] sum q dy  [2] sum q dx dx   [3] sum q dx dy   [4] sum q dy dy   [5] sum q
 //   [6..8] sum alpha T dL/dC_c                     with q = alpha_raw * dL/dalpha
+//   [9]    sum alpha T dL/dD  (= dL/dz; depth variant only)
+// CH = 3: the colour backward (the default); CH = 4: colour + depth (msgs_backward_with_depth), dL_ddepth [H,W] read
+template <int CH>
 __global__ __launch_bounds__(256) void blend_backward_kernel(ViewParams vp, const GaussRec* __restrict__ rec,
                                                              const uint32_t* __restrict__ ids,
                                                              const uint2* __restrict__ ranges,
                                                              const float* __restrict__ final_T,
                                                              const uint32_t* __restrict__ n_contrib,
                                                              const float* __restrict__ dL_dcolor,
-                                                             grad_acc_t* __restrict__ grad_rec) {
+                                                             grad_acc_t* __restrict__ grad_rec,
+                                                             const float* __restrict__ dL_ddepth) {
+    constexpr bool DEPTH = CH == 4;
     __shared__ float4 s_r0[BATCH], s_r1[BATCH];
     __shared__ float2 s_b[BATCH];                          // {blue, sign_test_bound}
+    __shared__ float s_z[DEPTH ? BATCH : 1];               // view depth (depth variant)
     __shared__ uint32_t s_id[BATCH];
     __shared__ uint32_t s_mask[BATCH];
     __shared__ uint16_t s_list[4][BATCH];
@@ -614,6 +670,7 @@ __global__ __launch_bounds__(256) void blend_backward_kernel(ViewParams vp, cons
     st.last = inside ? n_contrib[pix] : 0u;
     st.dL0 = st.dL1 = st.dL2 = 0.f;
     if (inside) { st.dL0 = dL_dcolor[pix]; st.dL1 = dL_dcolor[N + pix]; st.dL2 = dL_dcolor[2 * N + pix]; }
+    st.dLd = (DEPTH && inside) ? dL_ddepth[pix] : 0.f;
 
     const uint32_t wave_last = wave_max_u32(st.last);
     if (lane == 0) s_wmax[w] = wave_last;
@@ -625,8 +682,9 @@ __global__ __launch_bounds__(256) void blend_backward_kernel(ViewParams vp, cons
     // S_{i-1} = S_i + alpha_i (g_i - S_i): the three per-channel recurrences of the textbook form collapse into one
     // scalar, and starting it at bg . dL/dC absorbs the separate background term (-T_final bg.dL / (1 - alpha_i)).
     st.S = vp.bg[0] * st.dL0 + vp.bg[1] * st.dL1 + vp.bg[2] * st.dL2;
-    const bool alane = lane < 16 && (!(lane & 2) || lane == 2);        // the nine lanes that issue the per-entry atomics
-    const uint32_t aoff = row_reduce_component(lane);
+    // the nine lanes that issue the per-entry atomics (depth: ten, lane 3 delivers component 9)
+    const bool alane = DEPTH ? lane < 16 && (!(lane & 2) || lane == 2 || lane == 3) : lane < 16 && (!(lane & 2) || lane == 2);
+    const uint32_t aoff = DEPTH ? row_reduce_component10(lane) : row_reduce_component(lane);
 
     const int nb = ((int)tile_last + BATCH - 1) / BATCH;
     for (int b = nb - 1; b >= 0; --b) {
@@ -638,6 +696,7 @@ __global__ __launch_bounds__(256) void blend_backward_kernel(ViewParams vp, cons
             const float4 r0 = rec[id].r0, r1 = rec[id].r1;
             const float4 r2 = rec[id].r2;
             s_r0[tid] = doubled_w(r0); s_r1[tid] = r1; s_b[tid] = make_float2(r2.x, sign_test_bound(r1.y)); s_id[tid] = id;
+            if constexpr (DEPTH) s_z[tid] = r2.y;
             s_mask[tid] = quadrant_mask(r0, r1.x, r2.w, tx0, ty0);
         }
         __syncthreads();
@@ -650,7 +709,7 @@ __global__ __launch_bounds__(256) void blend_backward_kernel(ViewParams vp, cons
             if (hit) s_list[w][cnt + __popcll(bal & lt_mask)] = (uint16_t)e;
             cnt += __popcll(bal);
         }
-        backward_walk<true>(s_list[w], cnt, base, s_r0, s_r1, s_b, s_id, pxf, pyf, st, alane, aoff, grad_rec);
+        backward_walk<true, DEPTH>(s_list[w], cnt, base, s_r0, s_r1, s_b, s_id, pxf, pyf, st, alane, aoff, grad_rec, s_z);
     }
 }
 
@@ -658,19 +717,22 @@ __global__ __launch_bounds__(256) void blend_backward_kernel(ViewParams vp, cons
 // sub-block (lanes 0..15), WAVES per workgroup, 16 / WAVES workgroups per tile; same per-pixel arithmetic in the same order as
 // blend_backward_kernel; one atomic per (sub-block, Gaussian, component).  A workgroup walks the tile's list back from the last
 // entry ITS pixels blended.
-template <int WAVES, int SB = 4>
+template <int WAVES, int SB = 4, int CH = 3>
 __global__ __launch_bounds__(64 * WAVES) void blend_backward_fine_kernel(ViewParams vp, const GaussRec* __restrict__ rec,
                                                              const uint32_t* __restrict__ ids,
                                                              const uint2* __restrict__ ranges,
                                                              const float* __restrict__ final_T,
                                                              const uint32_t* __restrict__ n_contrib,
                                                              const float* __restrict__ dL_dcolor,
-                                                             grad_acc_t* __restrict__ grad_rec) {
+                                                             grad_acc_t* __restrict__ grad_rec,
+                                                             const float* __restrict__ dL_ddepth) {
+    constexpr bool DEPTH = CH == 4;
     constexpr int PER_ROW = TILE / SB, NSB = PER_ROW * PER_ROW, LANES = SB * SB;
     constexpr int T = 64 * WAVES, G = NSB / WAVES;
     constexpr int R = (BATCH + T - 1) / T;               // records a thread stages per batch
     __shared__ float4 s_r0[BATCH], s_r1[BATCH];
     __shared__ float2 s_b[BATCH];                          // {blue, sign_test_bound}
+    __shared__ float s_z[DEPTH ? BATCH : 1];               // view depth (depth variant)
     __shared__ float s_tau[BATCH];
     __shared__ uint32_t s_id[BATCH];
     __shared__ uint16_t s_list[WAVES][BATCH];
@@ -695,6 +757,7 @@ __global__ __launch_bounds__(64 * WAVES) void blend_backward_fine_kernel(ViewPar
     st.last = inside ? n_contrib[pix] : 0u;
     st.dL0 = st.dL1 = st.dL2 = 0.f;
     if (inside) { st.dL0 = dL_dcolor[pix]; st.dL1 = dL_dcolor[N + pix]; st.dL2 = dL_dcolor[2 * N + pix]; }
+    st.dLd = (DEPTH && inside) ? dL_ddepth[pix] : 0.f;
 
     const uint32_t wave_last = wave_max_u32(st.last);
     if (lane == 0) s_wmax[w] = wave_last;
@@ -708,8 +771,9 @@ __global__ __launch_bounds__(64 * WAVES) void blend_backward_fine_kernel(ViewPar
     // S_{i-1} = S_i + alpha_i (g_i - S_i): the three per-channel recurrences of the textbook form collapse into one
     // scalar, and starting it at bg . dL/dC absorbs the separate background term (-T_final bg.dL / (1 - alpha_i)).
     st.S = vp.bg[0] * st.dL0 + vp.bg[1] * st.dL1 + vp.bg[2] * st.dL2;
-    const bool alane = lane < 16 && (!(lane & 2) || lane == 2);        // the nine lanes that issue the per-entry atomics
-    const uint32_t aoff = row_reduce_component(lane);
+    // the nine lanes that issue the per-entry atomics (depth: ten, lane 3 delivers component 9)
+    const bool alane = DEPTH ? lane < 16 && (!(lane & 2) || lane == 2 || lane == 3) : lane < 16 && (!(lane & 2) || lane == 2);
+    const uint32_t aoff = DEPTH ? row_reduce_component10(lane) : row_reduce_component(lane);
 
     const int nb = ((int)grp_last + BATCH - 1) / BATCH;
     // register prefetch of the next (nearer) batch, as in blend_forward_fine_kernel
@@ -736,6 +800,7 @@ __global__ __launch_bounds__(64 * WAVES) void blend_backward_fine_kernel(ViewPar
             if (e < n) {
                 s_r0[e] = doubled_w(p0[k]); s_r1[e] = p1[k]; s_b[e] = make_float2(p2[k].x, sign_test_bound(p1[k].y)); s_id[e] = pid[k];
                 s_tau[e] = p2[k].w;
+                if constexpr (DEPTH) s_z[e] = p2[k].y;
             }
         }
         if (b > 0) fetch(base - BATCH);
@@ -757,7 +822,7 @@ __global__ __launch_bounds__(64 * WAVES) void blend_backward_fine_kernel(ViewPar
             if (hit) s_list[w][cnt + __popcll(bal & lt_mask)] = (uint16_t)e;
             cnt += __popcll(bal);
         }
-        backward_walk<false>(s_list[w], cnt, base, s_r0, s_r1, s_b, s_id, pxf, pyf, st, alane, aoff, grad_rec);
+        backward_walk<false, DEPTH>(s_list[w], cnt, base, s_r0, s_r1, s_b, s_id, pxf, pyf, st, alane, aoff, grad_rec, s_z);
     }
 }
 
@@ -779,7 +844,7 @@ __device__ __forceinline__ void wave_fence() {
 }
 
 struct BwdQuad {
-    float T, S, dL0, dL1, dL2;       // S: see blend_backward_kernel
+    float T, S, dL0, dL1, dL2, dLd;  // S: see blend_backward_kernel; dLd: dL/dD (depth variant)
     uint32_t last;
 };
 
@@ -788,8 +853,11 @@ struct BwdQuad {
 // quadrant hit masks already removed the quadrants the record cannot touch)
 // (returns the lanes that contributed as a scalar mask: three ballots of direct comparisons and scalar ANDs — a ballot
 //  of a derived bool costs two VALU instructions, and the caller only needs "any lane?")
+// (DEPTH: z is the entry's view depth and v9 the tenth sum, see backward_walk)
+template <bool DEPTH = false>
 __device__ __forceinline__ uint64_t bwd_quad_step(BwdQuad& s, BwdSums& v, const float4& r0, const float4& r1, float cb,
-                                                  float bound, float dx, float dy, uint32_t pos0) {
+                                                  float bound, float dx, float dy, uint32_t pos0, float z = 0.f,
+                                                  float* v9 = nullptr) {
     const PairEval ev = eval_pair(r0.z, r0.w, r1.x, r1.y, dx, dy);
     const float a_raw = __builtin_amdgcn_exp2f(ev.p);
     // alpha = min(0.99, a_raw) >= 1/255  <=>  a_raw >= 1/255
@@ -804,7 +872,9 @@ __device__ __forceinline__ uint64_t bwd_quad_step(BwdQuad& s, BwdSums& v, const 
     const float Tn = s.T * inv;
     s.T = Tn;
     const float dch = alpha_m * Tn;
-    const float sm = fmaf(cb, s.dL2, fmaf(r1.w, s.dL1, r1.z * s.dL0)) - s.S;
+    float gi = fmaf(cb, s.dL2, fmaf(r1.w, s.dL1, r1.z * s.dL0));
+    if constexpr (DEPTH) gi = fmaf(z, s.dLd, gi);
+    const float sm = gi - s.S;
     const float dL_dalpha = sm * Tn;
     s.S = fmaf(alpha_m, sm, s.S);
     const float qq = a_m * dL_dalpha;                         // Q6: gradient passes the 0.99 clamp
@@ -812,6 +882,7 @@ __device__ __forceinline__ uint64_t bwd_quad_step(BwdQuad& s, BwdSums& v, const 
     v.v2 = fmaf(qq, ev.dxx, v.v2); v.v3 = fmaf(qq, ev.dxy, v.v3); v.v4 = fmaf(qq, ev.dyy, v.v4);
     v.v5 += qq;
     v.v6 = fmaf(dch, s.dL0, v.v6); v.v7 = fmaf(dch, s.dL1, v.v7); v.v8 = fmaf(dch, s.dL2, v.v8);
+    if constexpr (DEPTH) *v9 = fmaf(dch, s.dLd, *v9);
     return validm;
 }
 
@@ -825,7 +896,9 @@ __global__ void trace_set_kernel(unsigned long long* p) { g_tile_trace = p; }
 // COUNT = true (diagnostic replica, msgs_blend_lane_stats): nothing is reduced or written; grad_out receives four counters —
 // (tile, entry) visits, (quadrant, entry) evaluations (each 64 lanes), lanes that contributed, visits with a contribution.
 // (The verification mode — msgs_set_deterministic — does not run this kernel: literal.hip restates the reference's loop.)
-template <bool COUNT = false>
+// CH = 4 (colour + depth): the depth channel of backward_walk, with z in the free slot of s_bi.  (CH is an int, not a second
+// bool: tools/isa_mix.py looks for this kernel by a mangled name, which a second bool parameter would start to match.)
+template <bool COUNT = false, int CH = 3>
 __global__ __launch_bounds__(64) void blend_backward_tile_kernel(ViewParams vp, const GaussRec* __restrict__ rec,
                                                                  const uint32_t* __restrict__ ids,
                                                                  const uint2* __restrict__ ranges,
@@ -833,10 +906,12 @@ __global__ __launch_bounds__(64) void blend_backward_tile_kernel(ViewParams vp, 
                                                                  const uint32_t* __restrict__ n_contrib,
                                                                  const float* __restrict__ dL_dcolor,
                                                                  void* __restrict__ grad_out,
-                                                                 const uint32_t* __restrict__ tile_order) {
+                                                                 const uint32_t* __restrict__ tile_order,
+                                                                 const float* __restrict__ dL_ddepth) {
+    constexpr bool DEPTH = CH == 4;
     __shared__ float4 s_r0[WB], s_r1[WB];
-    __shared__ float4 s_bi[WB];                            // {blue, sign_test_bound, id bits, -}: 16-byte stride like s_r0 / s_r1, so one
-                                                           // address register serves every LDS read of an entry
+    __shared__ float4 s_bi[WB];                            // {blue, sign_test_bound, id bits, - | depth}: 16-byte stride like s_r0 /
+                                                           // s_r1, so one address register serves every LDS read of an entry
     const int num_tiles = vp.gx * vp.gy;
     const int lane = threadIdx.x;
     // launch order: heaviest tiles first inside every XCD's contiguous run (launch_tile_order) when the forward left a valid
@@ -870,6 +945,7 @@ __global__ __launch_bounds__(64) void blend_backward_tile_kernel(ViewParams vp, 
             s.dL0 = (inside && !COUNT) ? dL_dcolor[pix] : 0.f;
             s.dL1 = (inside && !COUNT) ? dL_dcolor[N + pix] : 0.f;
             s.dL2 = (inside && !COUNT) ? dL_dcolor[2 * N + pix] : 0.f;
+            s.dLd = (DEPTH && inside) ? dL_ddepth[pix] : 0.f;
             s.S = vp.bg[0] * s.dL0 + vp.bg[1] * s.dL1 + vp.bg[2] * s.dL2;
             s.T = Tf;
             return __builtin_amdgcn_readfirstlane(wave_max_u32(s.last));
@@ -877,8 +953,9 @@ __global__ __launch_bounds__(64) void blend_backward_tile_kernel(ViewParams vp, 
         ql0 = init(q0, 0); ql1 = init(q1, 1); ql2 = init(q2, 2); ql3 = init(q3, 3);
     }
     const uint32_t tile_last = max(max(ql0, ql1), max(ql2, ql3));
-    const bool alane = lane < 16 && (!(lane & 2) || lane == 2);         // the nine lanes that issue the per-entry atomics
-    const uint32_t aoff = row_reduce_component(lane);
+    // the nine lanes that issue the per-entry atomics (depth: ten, lane 3 delivers component 9)
+    const bool alane = DEPTH ? lane < 16 && (!(lane & 2) || lane == 2 || lane == 3) : lane < 16 && (!(lane & 2) || lane == 2);
+    const uint32_t aoff = DEPTH ? row_reduce_component10(lane) : row_reduce_component(lane);
     const int xrow16 = (lane ^ 16) << 2, xrow32 = (lane ^ 32) << 2;     // ds_bpermute byte addresses of the partner lanes
 
     const int nb = ((int)tile_last + WB - 1) / WB;
@@ -892,7 +969,7 @@ __global__ __launch_bounds__(64) void blend_backward_tile_kernel(ViewParams vp, 
         const int base = b * WB;
         const int n = min(WB, (int)tile_last - base);
         wave_fence();
-        s_r0[lane] = doubled_w(n0); s_r1[lane] = n1; s_bi[lane] = make_float4(n2.x, sign_test_bound(n1.y), __uint_as_float(nid), 0.f);
+        s_r0[lane] = doubled_w(n0); s_r1[lane] = n1; s_bi[lane] = make_float4(n2.x, sign_test_bound(n1.y), __uint_as_float(nid), DEPTH ? n2.y : 0.f);
         // quadrant hit masks of the batch as four 64-bit ballots; a record beyond the last blended entry of a
         // quadrant cannot matter to that quadrant
         const uint32_t mymask = lane < n ? quadrant_mask(n0, n1.x, n2.w, tx0, ty0) : 0u;
@@ -915,6 +992,7 @@ __global__ __launch_bounds__(64) void blend_backward_tile_kernel(ViewParams vp, 
             const float cb = bl.x;
             const float dx = r0.x - bxf, dy = r0.y - byf;
             BwdSums v = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+            float v9 = 0.f;                                // depth variant: the tenth sum
             uint64_t any = 0;
             if constexpr (COUNT) {
                 uint64_t m;
@@ -926,17 +1004,28 @@ __global__ __launch_bounds__(64) void blend_backward_tile_kernel(ViewParams vp, 
                 if (any) cnt_hits += 1u;
                 continue;
             }
-            if (h0 & bit) any |= bwd_quad_step(q0, v, r0, r1, cb, bl.y, dx, dy, pos0);
-            if (h1 & bit) any |= bwd_quad_step(q1, v, r0, r1, cb, bl.y, dx - 8.0f, dy, pos0);
-            if (h2 & bit) any |= bwd_quad_step(q2, v, r0, r1, cb, bl.y, dx, dy - 8.0f, pos0);
-            if (h3 & bit) any |= bwd_quad_step(q3, v, r0, r1, cb, bl.y, dx - 8.0f, dy - 8.0f, pos0);
+            if constexpr (DEPTH) {
+                const float z = s_bi[e].w;                 // the entry's view depth
+                if (h0 & bit) any |= bwd_quad_step<true>(q0, v, r0, r1, cb, bl.y, dx, dy, pos0, z, &v9);
+                if (h1 & bit) any |= bwd_quad_step<true>(q1, v, r0, r1, cb, bl.y, dx - 8.0f, dy, pos0, z, &v9);
+                if (h2 & bit) any |= bwd_quad_step<true>(q2, v, r0, r1, cb, bl.y, dx, dy - 8.0f, pos0, z, &v9);
+                if (h3 & bit) any |= bwd_quad_step<true>(q3, v, r0, r1, cb, bl.y, dx - 8.0f, dy - 8.0f, pos0, z, &v9);
+            } else {
+                if (h0 & bit) any |= bwd_quad_step(q0, v, r0, r1, cb, bl.y, dx, dy, pos0);
+                if (h1 & bit) any |= bwd_quad_step(q1, v, r0, r1, cb, bl.y, dx - 8.0f, dy, pos0);
+                if (h2 & bit) any |= bwd_quad_step(q2, v, r0, r1, cb, bl.y, dx, dy - 8.0f, pos0);
+                if (h3 & bit) any |= bwd_quad_step(q3, v, r0, r1, cb, bl.y, dx - 8.0f, dy - 8.0f, pos0);
+            }
             if (any == 0) continue;                        // no lane contributed: nothing to reduce
             // ---- one 64-lane reduction per (tile, Gaussian): rows by DPP (row_reduce_scatter9), then the four rows
             // through the LDS crossbar (ds_bpermute lane ^ 16, lane ^ 32: two adds on the VALU; v_permlane16/32_swap are
-            // multi-cycle there).  Lanes 0,1,4,5,8,9,12,13 then hold components 0..7 and lane 2 component 8: one atomic
-            // instruction; the record id is wave-uniform (scalar address arithmetic).
+            // multi-cycle there).  Lanes 0,1,4,5,8,9,12,13 then hold components 0..7 and lane 2 component 8 (depth: lane 3
+            // component 9): one atomic instruction; the record id is wave-uniform (scalar address arithmetic).
             {
-                const float outv = cross_row_allreduce_bperm(row_reduce_scatter9(v), xrow16, xrow32);
+                float rowv;
+                if constexpr (DEPTH) rowv = row_reduce_scatter10(v, v9);
+                else rowv = row_reduce_scatter9(v);
+                const float outv = cross_row_allreduce_bperm(rowv, xrow16, xrow32);
                 // (record id through v_readlane of a register copy and a scalar-base atomic — no 64-bit VALU multiply-add —
                 //  were measured: no difference, 357..382 us for all four combinations)
                 const uint32_t gid = __builtin_amdgcn_readfirstlane(__float_as_uint(s_bi[e].z));
@@ -953,7 +1042,7 @@ __global__ __launch_bounds__(64) void blend_backward_tile_kernel(ViewParams vp, 
         }
     }
 #if defined(MSGS_TRACE_TILES)
-    if (!COUNT && g_tile_trace && lane == 0) {
+    if (!COUNT && !DEPTH && g_tile_trace && lane == 0) {
         unsigned hw, xcc;
         asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
         asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
@@ -1032,10 +1121,10 @@ static void launch_fine_fwd(int tiles, hipStream_t s, Args... args) {
     constexpr int NSB = (TILE / SB) * (TILE / SB);
     hipLaunchKernelGGL((blend_forward_fine_kernel<WAVES, SB>), dim3(tiles * (NSB / WAVES)), dim3(64 * WAVES), 0, s, args...);
 }
-template <int WAVES, int SB = 4, class... Args>
+template <int WAVES, int SB = 4, int CH = 3, class... Args>
 static void launch_fine_bwd(int tiles, hipStream_t s, Args... args) {
     constexpr int NSB = (TILE / SB) * (TILE / SB);
-    hipLaunchKernelGGL((blend_backward_fine_kernel<WAVES, SB>), dim3(tiles * (NSB / WAVES)), dim3(64 * WAVES), 0, s, args...);
+    hipLaunchKernelGGL((blend_backward_fine_kernel<WAVES, SB, CH>), dim3(tiles * (NSB / WAVES)), dim3(64 * WAVES), 0, s, args...);
 }
 static bool use_fine(int tiles, int max_tiles) {
     const int g = g_granularity.load();
@@ -1188,13 +1277,17 @@ bool forward_uses_quadrant_kernel(int tiles) { return tiles > 0 && !use_fine(til
 
 hipError_t launch_blend_backward(const ViewParams& vp, const char* geom, const uint32_t* ids, const uint2* ranges,
                                  const float* final_T, const uint32_t* n_contrib, const float* dL_dcolor,
-                                 grad_acc_t* grad_rec, hipStream_t s, const uint32_t* tile_order) {
+                                 grad_acc_t* grad_rec, hipStream_t s, const uint32_t* tile_order, const float* dL_ddepth) {
     const int tiles = vp.gx * vp.gy;
     if (tiles == 0) return hipSuccess;
     const GaussRec* rec = reinterpret_cast<const GaussRec*>(geom);
+    // dL_ddepth != nullptr: the depth variants of the same three kernels (same route choice, record slot 9 = dL/dz)
     if (g_granularity.load() == 2 || (g_bwd_gen.load() == 0 && use_fine(tiles, FINE_MAX_TILES_BWD))) {
         const FineShape f = fine_shape(tiles);
-#define MSGS_FINE_BWD(WAVES, SB) launch_fine_bwd<WAVES, SB>(tiles, s, vp, rec, ids, ranges, final_T, n_contrib, dL_dcolor, grad_rec)
+#define MSGS_FINE_BWD(WAVES, SB) (dL_ddepth ? launch_fine_bwd<WAVES, SB, 4>(tiles, s, vp, rec, ids, ranges, final_T, n_contrib, \
+                                                                            dL_dcolor, grad_rec, dL_ddepth)                         \
+                                            : launch_fine_bwd<WAVES, SB, 3>(tiles, s, vp, rec, ids, ranges, final_T, n_contrib,    \
+                                                                            dL_dcolor, grad_rec, (const float*)nullptr))
         if (f.sb == 1) {
             if (f.g >= 64) MSGS_FINE_BWD(4, 1); else if (f.g == 32) MSGS_FINE_BWD(8, 1); else MSGS_FINE_BWD(16, 1);
         } else if (f.sb == 2) {
@@ -1206,12 +1299,18 @@ hipError_t launch_blend_backward(const ViewParams& vp, const char* geom, const u
         }
 #undef MSGS_FINE_BWD
     }
+    else if (!bwd_v1(tiles) && dL_ddepth)
+        hipLaunchKernelGGL((blend_backward_tile_kernel<false, 4>), dim3(tiles), dim3(64), 0, s, vp, rec, ids, ranges, final_T,
+                           n_contrib, dL_dcolor, (void*)grad_rec, tile_order, dL_ddepth);
     else if (!bwd_v1(tiles))
-        hipLaunchKernelGGL(blend_backward_tile_kernel<false>, dim3(tiles), dim3(64), 0, s, vp, rec, ids, ranges, final_T,
-                           n_contrib, dL_dcolor, grad_rec, tile_order);
+        hipLaunchKernelGGL((blend_backward_tile_kernel<false, 3>), dim3(tiles), dim3(64), 0, s, vp, rec, ids, ranges, final_T,
+                           n_contrib, dL_dcolor, (void*)grad_rec, tile_order, (const float*)nullptr);
+    else if (dL_ddepth)
+        hipLaunchKernelGGL(blend_backward_kernel<4>, dim3(tiles), dim3(256), 0, s, vp, rec, ids, ranges, final_T,
+                           n_contrib, dL_dcolor, grad_rec, dL_ddepth);
     else
-        hipLaunchKernelGGL(blend_backward_kernel, dim3(tiles), dim3(256), 0, s, vp, rec, ids, ranges, final_T,
-                           n_contrib, dL_dcolor, grad_rec);
+        hipLaunchKernelGGL(blend_backward_kernel<3>, dim3(tiles), dim3(256), 0, s, vp, rec, ids, ranges, final_T,
+                           n_contrib, dL_dcolor, grad_rec, (const float*)nullptr);
     return hipGetLastError();
 }
 
@@ -1221,6 +1320,8 @@ hipError_t launch_blend_backward(const ViewParams& vp, const char* geom, const u
 // entries are added in ascending entry position (= ascending tile id) by one thread.  Bitwise reproducible run to run.
 // ---------------------------------------------------------------------------------------------
 namespace {
+// NF sums per entry and per Gaussian: DET_INST_FLOATS, or DET_INST_FLOATS_DEPTH with a depth gradient (the tenth: dL/dz)
+template <int NF>
 __global__ __launch_bounds__(256) void det_reduce_kernel(const uint32_t* __restrict__ gid_sorted,
                                                          const uint32_t* __restrict__ entry_of, int64_t D,
                                                          const double* __restrict__ inst_grad,
@@ -1232,25 +1333,25 @@ __global__ __launch_bounds__(256) void det_reduce_kernel(const uint32_t* __restr
     // the per-tile sums of one Gaussian are added in DOUBLE (exact for any realistic tile count): the deterministic mode
     // is the verification mode, and a Gaussian that covers hundreds of tiles otherwise loses ~1e-6 of its sums to float32
     // accumulation, which the conic -> covariance chain of K8 amplifies by the squared aspect ratio
-    double acc[DET_INST_FLOATS];
+    double acc[NF];
 #pragma unroll
-    for (int c = 0; c < DET_INST_FLOATS; ++c) acc[c] = 0.0;
+    for (int c = 0; c < NF; ++c) acc[c] = 0.0;
     for (int64_t k = q; k < D && gid_sorted[k] == g; ++k) {
-        const double* src = inst_grad + (size_t)entry_of[k] * DET_INST_FLOATS;
+        const double* src = inst_grad + (size_t)entry_of[k] * NF;
 #pragma unroll
-        for (int c = 0; c < DET_INST_FLOATS; ++c) acc[c] += src[c];
+        for (int c = 0; c < NF; ++c) acc[c] += src[c];
     }
     grad_acc_t* dst = grad_rec + (size_t)g * rec_stride;
 #pragma unroll
-    for (int c = 0; c < DET_INST_FLOATS; ++c) dst[c] = (grad_acc_t)acc[c];
+    for (int c = 0; c < NF; ++c) dst[c] = (grad_acc_t)acc[c];
 }
 }  // namespace
 
-DetScratch::DetScratch(int64_t P, int64_t D) {
+DetScratch::DetScratch(int64_t P, int64_t D, int nf) {
     const int64_t n = D > 0 ? D : 1;
     size_t o = 0;
     grad_rec = o;  o = align256(o + GRAD_REC_BYTES * (size_t)(P > 0 ? P : 1));
-    inst_grad = o; o = align256(o + sizeof(double) * DET_INST_FLOATS * (size_t)n);
+    inst_grad = o; o = align256(o + sizeof(double) * nf * (size_t)n);
     keys = o;      o = align256(o + 4 * (size_t)n);
     keys_s = o;    o = align256(o + 4 * (size_t)n);
     entry = o;     o = align256(o + 4 * (size_t)n);
@@ -1260,19 +1361,20 @@ DetScratch::DetScratch(int64_t P, int64_t D) {
 
 hipError_t launch_blend_backward_det(const ViewParams& vp, int P, const char* geom, const uint32_t* ids, int64_t D,
                                      const uint2* ranges, const float* final_T, const uint32_t* n_contrib,
-                                     const float* dL_dcolor, char* scratch, hipStream_t s) {
+                                     const float* dL_dcolor, char* scratch, hipStream_t s, const float* dL_ddepth) {
     const int tiles = vp.gx * vp.gy;
     if (tiles == 0 || D <= 0) return hipSuccess;
-    const DetScratch L(P, D);
+    const int nf = dL_ddepth ? DET_INST_FLOATS_DEPTH : DET_INST_FLOATS;
+    const DetScratch L(P, D, nf);
     grad_acc_t* grad_rec = (grad_acc_t*)(scratch + L.grad_rec);
     double* inst = (double*)(scratch + L.inst_grad);
     uint32_t* keys = (uint32_t*)(scratch + L.keys);
     uint32_t* keys_s = (uint32_t*)(scratch + L.keys_s);
     uint32_t* entry = (uint32_t*)(scratch + L.entry);
-    hipError_t e = launch_zero(inst, sizeof(double) * DET_INST_FLOATS * (size_t)D, s);
+    hipError_t e = launch_zero(inst, sizeof(double) * nf * (size_t)D, s);
     if (e != hipSuccess) return e;
-    // the reference's per-pixel backward restated literally (literal.hip): nine double sums per tile entry
-    e = launch_blend_backward_literal(vp, geom, P, ids, ranges, final_T, n_contrib, dL_dcolor, inst, s);
+    // the reference's per-pixel backward restated literally (literal.hip): nine (ten) double sums per tile entry
+    e = launch_blend_backward_literal(vp, geom, P, ids, ranges, final_T, n_contrib, dL_dcolor, inst, s, dL_ddepth);
     if (e != hipSuccess) return e;
     e = hipMemcpyAsync(keys, ids, 4 * (size_t)D, hipMemcpyDeviceToDevice, s);      // the sort clobbers its input
     if (e != hipSuccess) return e;
@@ -1280,10 +1382,16 @@ hipError_t launch_blend_backward_det(const ViewParams& vp, int P, const char* ge
     while (bits < 32 && ((int64_t)1 << bits) < P) ++bits;
     e = radix_sort_pairs(keys, nullptr, keys_s, entry, D, 0, bits, scratch + L.sort, s);   // stable: entries ascending
     if (e != hipSuccess) return e;
-    // ... added per Gaussian in ascending tile order: [P, 9] packed doubles, the textbook sums the per-Gaussian backward takes
+    // ... added per Gaussian in ascending tile order: [P, 9] ([P, 10]) packed doubles, the textbook sums the per-Gaussian
+    // backward takes (GRAD_REC_BYTES per Gaussian holds ten)
     static_assert(sizeof(grad_acc_t) == 8, "the verification mode's sums are doubles");
-    hipLaunchKernelGGL(det_reduce_kernel, dim3((unsigned)((D + 255) / 256)), dim3(256), 0, s, keys_s, entry, D, inst,
-                       grad_rec, DET_INST_FLOATS);
+    static_assert(DET_INST_FLOATS_DEPTH <= GRAD_REC_FLOATS, "the [P, 10] sums fit the grad_rec region");
+    if (dL_ddepth)
+        hipLaunchKernelGGL(det_reduce_kernel<DET_INST_FLOATS_DEPTH>, dim3((unsigned)((D + 255) / 256)), dim3(256), 0, s, keys_s,
+                           entry, D, inst, grad_rec, DET_INST_FLOATS_DEPTH);
+    else
+        hipLaunchKernelGGL(det_reduce_kernel<DET_INST_FLOATS>, dim3((unsigned)((D + 255) / 256)), dim3(256), 0, s, keys_s, entry, D, inst,
+                           grad_rec, DET_INST_FLOATS);
     return hipGetLastError();
 }
 
@@ -1297,7 +1405,7 @@ hipError_t launch_blend_backward_lane_stats(const ViewParams& vp, const char* ge
     if (tiles)
         hipLaunchKernelGGL(blend_backward_tile_kernel<true>, dim3(tiles), dim3(64), 0, s, vp,
                            reinterpret_cast<const GaussRec*>(geom), ids, ranges, final_T, n_contrib, (const float*)nullptr, (void*)out4,
-                           (const uint32_t*)nullptr);
+                           (const uint32_t*)nullptr, (const float*)nullptr);
     return hipGetLastError();
 }
 

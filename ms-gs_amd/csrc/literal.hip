@@ -116,7 +116,10 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
 
 // The textbook backward per pixel; the nine float32 products of every (pixel, entry) pair enter DOUBLE sums over the tile's 256
 // pixels — lanes of a wave in a fixed butterfly, the four waves in order — stored at inst_grad[range.x + position][0..8].
+// DEPTH (a depth gradient, msgs_backward_with_depth): the depth map restated as a fourth channel — its own accum_rec /
+// last_color with colour z and no background term — and a tenth product dchannel_dcolor dL/dD (= dL/dz), [0..9] per entry.
 constexpr int LBB = 32;             // entries per backward batch (4 waves x 9 doubles each in LDS)
+template <bool DEPTH>
 __global__ __launch_bounds__(LB) void blend_backward_literal_kernel(ViewParams vp, const GaussRec* __restrict__ rec,
                                                                     const float4* __restrict__ litrec,
                                                                     const uint32_t* __restrict__ ids,
@@ -124,11 +127,13 @@ __global__ __launch_bounds__(LB) void blend_backward_literal_kernel(ViewParams v
                                                                     const float* __restrict__ final_T,
                                                                     const uint32_t* __restrict__ n_contrib,
                                                                     const float* __restrict__ dL_dcolor,
-                                                                    double* __restrict__ inst_grad) {
+                                                                    double* __restrict__ inst_grad,
+                                                                    const float* __restrict__ dL_ddepth) {
+    constexpr int NF = DEPTH ? DET_INST_FLOATS_DEPTH : DET_INST_FLOATS;
     __shared__ float2 s_xy[LBB];
     __shared__ float4 s_con[LBB];
-    __shared__ float4 s_col[LBB];
-    __shared__ double s_part[LBB][4][9];
+    __shared__ float4 s_col[LBB];                           // r, g, b, - | depth
+    __shared__ double s_part[LBB][4][NF];
     __shared__ uint32_t s_wmax[4];
     const int tile = blockIdx.x;
     const int tx = tile % vp.gx, ty = tile / vp.gx;
@@ -145,6 +150,8 @@ __global__ __launch_bounds__(LB) void blend_backward_literal_kernel(ViewParams v
     float dL_dpixel[3] = {0.f, 0.f, 0.f};
     if (inside) { dL_dpixel[0] = dL_dcolor[pix]; dL_dpixel[1] = dL_dcolor[N + pix]; dL_dpixel[2] = dL_dcolor[2 * N + pix]; }
     float accum_rec[3] = {0.f, 0.f, 0.f}, last_color[3] = {0.f, 0.f, 0.f}, last_alpha = 0.f;
+    const float dL_dD = (DEPTH && inside) ? dL_ddepth[pix] : 0.f;
+    float accum_rec_d = 0.f, last_depth = 0.f;
     const float ddelx_dx = 0.5f * vp.W, ddely_dy = 0.5f * vp.H;
     const float bg[3] = {vp.bg[0], vp.bg[1], vp.bg[2]};
 
@@ -162,12 +169,12 @@ __global__ __launch_bounds__(LB) void blend_backward_literal_kernel(ViewParams v
             const float4 r0 = rec[id].r0, r1 = rec[id].r1, r2 = rec[id].r2;
             s_xy[tid] = make_float2(r0.x, r0.y);
             s_con[tid] = litrec[id];
-            s_col[tid] = make_float4(r1.z, r1.w, r2.x, 0.f);
+            s_col[tid] = make_float4(r1.z, r1.w, r2.x, DEPTH ? r2.y : 0.f);
         }
         __syncthreads();
         for (int e = n - 1; e >= 0; --e) {                          // back to front
             const uint32_t j = (uint32_t)(lo + e);                  // 0-based position in the tile's list
-            float v[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+            float v[NF] = {};
             if (j < last) {
                 const float4 con = s_con[e];
                 const float dx = s_xy[e].x - pxf, dy = s_xy[e].y - pyf;
@@ -188,6 +195,11 @@ __global__ __launch_bounds__(LB) void blend_backward_literal_kernel(ViewParams v
                             dL_dalpha += (rgb[c] - accum_rec[c]) * dL_dpixel[c];
                             dcol[c] = dchannel_dcolor * dL_dpixel[c];
                         }
+                        if constexpr (DEPTH) {
+                            accum_rec_d = last_alpha * last_depth + (1.f - last_alpha) * accum_rec_d;
+                            last_depth = s_col[e].w;
+                            dL_dalpha += (s_col[e].w - accum_rec_d) * dL_dD;
+                        }
                         dL_dalpha *= T;
                         last_alpha = alpha;
                         float bg_dot = 0.f;
@@ -205,19 +217,20 @@ __global__ __launch_bounds__(LB) void blend_backward_literal_kernel(ViewParams v
                         v[4] = -0.5f * gdy * dy * dL_dG;
                         v[5] = G * dL_dalpha;
                         v[6] = dcol[0]; v[7] = dcol[1]; v[8] = dcol[2];
+                        if constexpr (DEPTH) v[9] = dchannel_dcolor * dL_dD;
                     }
                 }
             }
 #pragma unroll
-            for (int k = 0; k < 9; ++k) {
+            for (int k = 0; k < NF; ++k) {
                 const double t = wave_sum_f64((double)v[k]);
                 if (lane == 0) s_part[e][wv][k] = t;
             }
         }
         __syncthreads();
-        for (int q = tid; q < n * 9; q += LB) {
-            const int e = q / 9, k = q - 9 * e;
-            inst_grad[((size_t)range.x + lo + e) * DET_INST_FLOATS + k] = ((s_part[e][0][k] + s_part[e][1][k]) + s_part[e][2][k]) + s_part[e][3][k];
+        for (int q = tid; q < n * NF; q += LB) {
+            const int e = q / NF, k = q - NF * e;
+            inst_grad[((size_t)range.x + lo + e) * NF + k] = ((s_part[e][0][k] + s_part[e][1][k]) + s_part[e][2][k]) + s_part[e][3][k];
         }
     }
 }
@@ -238,12 +251,19 @@ hipError_t launch_blend_forward_literal(const ViewParams& vp, const char* geom, 
 
 hipError_t launch_blend_backward_literal(const ViewParams& vp, const char* geom, int P, const uint32_t* ids, const uint2* ranges,
                                          const float* final_T, const uint32_t* n_contrib, const float* dL_dcolor, double* inst_grad,
-                                         hipStream_t s) {
+                                         hipStream_t s, const float* dL_ddepth) {
     const int tiles = vp.gx * vp.gy;
     if (tiles == 0) return hipSuccess;
     const GeomLayout L(P > 0 ? P : 1);
-    hipLaunchKernelGGL(blend_backward_literal_kernel, dim3(tiles), dim3(LB), 0, s, vp, reinterpret_cast<const GaussRec*>(geom + L.rec),
-                       reinterpret_cast<const float4*>(geom + L.litrec), ids, ranges, final_T, n_contrib, dL_dcolor, inst_grad);
+    if (dL_ddepth) {
+        hipLaunchKernelGGL(blend_backward_literal_kernel<true>, dim3(tiles), dim3(LB), 0, s, vp,
+                           reinterpret_cast<const GaussRec*>(geom + L.rec), reinterpret_cast<const float4*>(geom + L.litrec), ids,
+                           ranges, final_T, n_contrib, dL_dcolor, inst_grad, dL_ddepth);
+        return hipGetLastError();
+    }
+    hipLaunchKernelGGL(blend_backward_literal_kernel<false>, dim3(tiles), dim3(LB), 0, s, vp, reinterpret_cast<const GaussRec*>(geom + L.rec),
+                       reinterpret_cast<const float4*>(geom + L.litrec), ids, ranges, final_T, n_contrib, dL_dcolor, inst_grad,
+                       (const float*)nullptr);
     return hipGetLastError();
 }
 

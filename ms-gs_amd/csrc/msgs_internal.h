@@ -31,7 +31,8 @@ struct __attribute__((aligned(32))) BinRec { float4 q0, q1; };
 
 // Per-Gaussian 2-D gradient record accumulated by the blend backward: 10 accumulators.
 //   [0] sum q dx  [1] sum q dy  [2] sum q dx^2  [3] sum q dx dy  [4] sum q dy^2  [5] sum q  [6..8] dL/drgb
-//   [9] pad, with q = alpha_raw dL/dalpha; preprocess_backward_kernel turns [0..5] into
+//   [9] sum alpha T dL/dD = dL/dz (depth variants only, msgs_backward_with_depth; else unused), with q = alpha_raw dL/dalpha;
+//   preprocess_backward_kernel turns [0..5] into
 //   dL/dmean2D (NDC-ish units), dL/dconic (A, B-half, C) and dL/dopacity with per-Gaussian factors.
 // The accumulators are DOUBLES (80-byte records, global_atomic_add_f64): the per-tile float32 sums of a Gaussian are
 // then added exactly, whatever the order the tiles' atomics arrive in — the default backward is reproducible to the
@@ -40,14 +41,15 @@ struct __attribute__((aligned(32))) BinRec { float4 q0, q1; };
 // -DMSGS_GRAD_REC_F32 builds the float32 variant (48-byte records) for A/B measurements.
 #if defined(MSGS_GRAD_REC_F32)
 typedef float grad_acc_t;
-constexpr int GRAD_REC_FLOATS = 12;     // accumulators per record (9 used)
+constexpr int GRAD_REC_FLOATS = 12;     // accumulators per record (9 used, 10 with depth)
 #else
 typedef double grad_acc_t;
-constexpr int GRAD_REC_FLOATS = 10;     // accumulators per record (9 used)
+constexpr int GRAD_REC_FLOATS = 10;     // accumulators per record (9 used, 10 with depth)
 #endif
 constexpr uint32_t TILE_ORDER_MAGIC = 0x4C505431u;
 constexpr size_t GRAD_REC_BYTES = sizeof(grad_acc_t) * GRAD_REC_FLOATS;
 constexpr int DET_INST_FLOATS = 9;      // per tile entry in deterministic mode: the nine K7 sums (DOUBLES)
+constexpr int DET_INST_FLOATS_DEPTH = 10;   // ... with a depth gradient: the tenth is dL/dz
 
 __host__ __device__ inline size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
 
@@ -596,14 +598,14 @@ int get_occlusion();
 int occlusion_block_log2(int gx, int gy);  // log2(tiles per side of a cover block) for a gx x gy grid (4 x 4 tiles unless the grid has more than 2048 such blocks)
 hipError_t launch_preprocess_backward(const ViewParams& vp, const msgs_gaussians_t& g, const int32_t* radii,
                                       const char* geom, const grad_acc_t* grad_rec, const msgs_grads_t& grads,
-                                      hipStream_t s, bool textbook = false);
+                                      hipStream_t s, bool textbook = false, bool depth = false);
 // literal.hip: the verification mode (msgs_set_deterministic) — the reference's blend loops restated literally
 hipError_t launch_blend_forward_literal(const ViewParams& vp, const char* geom, int P, const uint32_t* ids, const uint2* ranges,
                                         float* out_color, float* out_ps, float* out_depth, float* final_T, uint32_t* n_contrib,
                                         uint32_t* order_flag, hipStream_t s);
 hipError_t launch_blend_backward_literal(const ViewParams& vp, const char* geom, int P, const uint32_t* ids, const uint2* ranges,
                                          const float* final_T, const uint32_t* n_contrib, const float* dL_dcolor, double* inst_grad,
-                                         hipStream_t s);
+                                         hipStream_t s, const float* dL_ddepth = nullptr);
 hipError_t launch_sh_grad_from_views(int P, int n_views, int deg, const float* means3D, const float* campos,
                                      int64_t campos_stride, const float* drgb, int64_t drgb_stride, float scale,
                                      float* d_dc, float* d_rest, hipStream_t s);
@@ -662,14 +664,15 @@ hipError_t launch_ranges(const uint32_t* keys, int64_t D, uint2* ranges, int num
                          bool pre_zeroed = false, const uint32_t* D_dev = nullptr, bool keys16 = false, uint32_t base = 0);
 int set_backward_generation(int gen);     // blend.hip: 0 = by tile count, 1 | 2 = forced; returns the previous value
 int set_blend_granularity(int mode);      // blend.hip: 0 = by tile count, 1 = coarse, 2 = fine (16 waves per tile)
-// blend.hip, deterministic backward: scratch = [grad_rec | inst_grad | sort buffers]
+// blend.hip, deterministic backward: scratch = [grad_rec | inst_grad | sort buffers]; nf sums per tile entry (DET_INST_FLOATS,
+// DET_INST_FLOATS_DEPTH with a depth gradient)
 struct DetScratch {
     size_t grad_rec, inst_grad, keys, keys_s, entry, sort, total;
-    DetScratch(int64_t P, int64_t D);
+    DetScratch(int64_t P, int64_t D, int nf = DET_INST_FLOATS);
 };
 hipError_t launch_blend_backward_det(const ViewParams& vp, int P, const char* geom, const uint32_t* ids, int64_t D,
                                      const uint2* ranges, const float* final_T, const uint32_t* n_contrib,
-                                     const float* dL_dcolor, char* scratch, hipStream_t s);
+                                     const float* dL_dcolor, char* scratch, hipStream_t s, const float* dL_ddepth = nullptr);
 
 // epilogue.hip
 hipError_t launch_adam(const msgs_adam_tensor_t* tensors, int n, int64_t step, double beta1, double beta2, double eps,
@@ -714,7 +717,8 @@ hipError_t launch_forward_feedback(const unsigned long long* dtrav, const SlabHe
                                    const uint32_t* D_dev, uint32_t tag, uint64_t ticket, uint64_t* host_mapped, hipStream_t s);
 hipError_t launch_blend_backward(const ViewParams& vp, const char* geom, const uint32_t* ids, const uint2* ranges,
                                  const float* final_T, const uint32_t* n_contrib, const float* dL_dcolor,
-                                 grad_acc_t* grad_rec, hipStream_t s, const uint32_t* tile_order = nullptr);
+                                 grad_acc_t* grad_rec, hipStream_t s, const uint32_t* tile_order = nullptr,
+                                 const float* dL_ddepth = nullptr);   // non-null: the depth variants (record slot 9 = dL/dz)
 // heaviest-first launch order of the one-wave-per-tile backward from the forward's per-tile traversal lengths
 hipError_t launch_tile_order(const ViewParams& vp, const uint32_t* tile_last, uint32_t* tile_order, hipStream_t s);
 hipError_t launch_blend_lane_stats(const ViewParams& vp, const char* geom, const uint32_t* ids, const uint2* ranges,

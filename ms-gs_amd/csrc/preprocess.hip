@@ -719,7 +719,9 @@ __global__ __launch_bounds__(256) void preprocess_kernel(ViewParams vp, msgs_gau
 // ADAM = true (msgs_grads_t::adam_in_backward; raw mode 1, staged SH rows, no accumulate, not factored): the raw-parameter
 // gradients are not stored — every Gaussian's parameters and moments take their Adam step here, with the gradient still in
 // registers / LDS (zero for a Gaussian that was not rendered).
-template <bool TEXTBOOK, bool ADAM>
+// DEPTH = true (msgs_backward_with_depth): the record's slot 9 holds dL/dz (the textbook sums:
+// [P, 10]), and dL/dmeans3D gains dL/dz (V[2], V[6], V[10]) — z = view depth, the third row of the view matrix.
+template <bool TEXTBOOK, bool ADAM, bool DEPTH = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void preprocess_backward_kernel(ViewParams vp, msgs_gaussians_t g,
                                                                   const int32_t* __restrict__ radii,
                                                                   const char* __restrict__ geom,
@@ -772,10 +774,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void p
         // structure (double accumulators, one cast)
         float4 ga, gb, gc;
         if constexpr (TEXTBOOK) {
-            const double* gr = reinterpret_cast<const double*>(grad_rec) + (size_t)i * 9;
+            const double* gr = reinterpret_cast<const double*>(grad_rec) + (size_t)i * (DEPTH ? DET_INST_FLOATS_DEPTH : 9);
             ga = make_float4((float)gr[0], (float)gr[1], (float)gr[2], (float)gr[3]);
             gb = make_float4((float)gr[4], (float)gr[5], (float)gr[6], (float)gr[7]);
-            gc = make_float4((float)gr[8], 0.f, 0.f, 0.f);
+            gc = make_float4((float)gr[8], DEPTH ? (float)gr[9] : 0.f, 0.f, 0.f);
         } else {
             const grad_acc_t* gr = grad_rec + (size_t)i * GRAD_REC_FLOATS;
             grad_acc_t t[GRAD_REC_FLOATS];
@@ -787,7 +789,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void p
             }
             ga = make_float4((float)t[0], (float)t[1], (float)t[2], (float)t[3]);
             gb = make_float4((float)t[4], (float)t[5], (float)t[6], (float)t[7]);
-            gc = make_float4((float)t[8], 0.f, 0.f, 0.f);
+            gc = make_float4((float)t[8], DEPTH ? (float)t[9] : 0.f, 0.f, 0.f);
         }
         // blend_backward_kernel accumulates [sum q dx, sum q dy, sum q dx^2, sum q dx dy, sum q dy^2, sum q]
         // with q = alpha_raw dL/dalpha; the per-Gaussian constant factors are applied here (blend.hip).
@@ -893,6 +895,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void p
             for (int j = 0; j < 3; ++j)
                 dmean[j] += (cm.M[4 * j + 0] * m_w - cm.M[4 * j + 3] * mul1) * g2x +
                             (cm.M[4 * j + 1] * m_w - cm.M[4 * j + 3] * mul2) * g2y;
+        }
+        // ---- view-depth backward (z = V[2] x + V[6] y + V[10] z + V[14]; gc.y = dL/dz) ----
+        if constexpr (DEPTH) {
+#pragma unroll
+            for (int j = 0; j < 3; ++j) dmean[j] += cm.V[4 * j + 2] * gc.y;
         }
         // ---- 3-D covariance backward ----
         if (!g.cov3D_precomp) {
@@ -1207,14 +1214,14 @@ hipError_t launch_preprocess(const ViewParams& vp, const msgs_gaussians_t& g, in
 
 hipError_t launch_preprocess_backward(const ViewParams& vp, const msgs_gaussians_t& g, const int32_t* radii,
                                       const char* geom, const grad_acc_t* grad_rec, const msgs_grads_t& grads,
-                                      hipStream_t s, bool textbook) {
+                                      hipStream_t s, bool textbook, bool depth) {
     if (g.P == 0) return hipSuccess;
     // textbook: grad_rec holds [P, 9] doubles — the TEXTBOOK 2-D gradients (msgs_backward_per_gaussian; the verification mode)
     static_assert(sizeof(grad_acc_t) == 8, "the textbook sums are doubles");
     const msgs_adam_in_backward_t* aib = grads.adam_in_backward;
     if (g.raw_params != 0 && grads.dL_dfeatures_dc == nullptr && !aib) {          // factored SH gradient: the factors first
         hipLaunchKernelGGL(sh_factor_kernel, dim3((g.P + 255) / 256), dim3(256), 0, s, g.P, radii, geom, grad_rec,
-                           textbook ? 9 : GRAD_REC_FLOATS, grads.dL_dcolors);
+                           textbook ? (depth ? DET_INST_FLOATS_DEPTH : 9) : GRAD_REC_FLOATS, grads.dL_dcolors);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
         if (grads.factors_ready) {
@@ -1238,7 +1245,13 @@ hipError_t launch_preprocess_backward(const ViewParams& vp, const msgs_gaussians
         ad.a = adam_scalars(aib->step, aib->beta1, aib->beta2, aib->eps);
     }
     const dim3 grid((g.P + 255) / 256), block(256);
-    if (textbook && aib) hipLaunchKernelGGL((preprocess_backward_kernel<true, true>), grid, block, 0, s, vp, g, radii, geom, grad_rec, grads, ad);
+    if (depth) {             // record slot 9 = dL/dz (msgs_backward_with_depth)
+        if (textbook && aib) hipLaunchKernelGGL((preprocess_backward_kernel<true, true, true>), grid, block, 0, s, vp, g, radii, geom, grad_rec, grads, ad);
+        else if (textbook) hipLaunchKernelGGL((preprocess_backward_kernel<true, false, true>), grid, block, 0, s, vp, g, radii, geom, grad_rec, grads, ad);
+        else if (aib) hipLaunchKernelGGL((preprocess_backward_kernel<false, true, true>), grid, block, 0, s, vp, g, radii, geom, grad_rec, grads, ad);
+        else hipLaunchKernelGGL((preprocess_backward_kernel<false, false, true>), grid, block, 0, s, vp, g, radii, geom, grad_rec, grads, ad);
+    }
+    else if (textbook && aib) hipLaunchKernelGGL((preprocess_backward_kernel<true, true>), grid, block, 0, s, vp, g, radii, geom, grad_rec, grads, ad);
     else if (textbook) hipLaunchKernelGGL((preprocess_backward_kernel<true, false>), grid, block, 0, s, vp, g, radii, geom, grad_rec, grads, ad);
     else if (aib) hipLaunchKernelGGL((preprocess_backward_kernel<false, true>), grid, block, 0, s, vp, g, radii, geom, grad_rec, grads, ad);
     else hipLaunchKernelGGL((preprocess_backward_kernel<false, false>), grid, block, 0, s, vp, g, radii, geom, grad_rec, grads, ad);

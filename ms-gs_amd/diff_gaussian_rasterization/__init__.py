@@ -214,9 +214,11 @@ class _Call:
         self.view_ref, self.g_ref = C.byref(self.view), C.byref(self.g)
 
 
-def _backward_scratch(P, D, dev):
+def _backward_scratch(P, D, dev, depth=False):
     lib = _C.lib
     if lib.msgs_get_deterministic():
+        if depth:
+            return _bytes(lib.msgs_backward_scratch_bytes_deterministic_depth(P, D), dev)
         return _bytes(lib.msgs_backward_scratch_bytes_deterministic(P, D), dev)
     return _bytes(lib.msgs_backward_scratch_bytes(P), dev)
 
@@ -250,7 +252,7 @@ def _alloc_grad_records(ctx, P, dev):
     return ctx.grad_rec
 
 
-def _take_backward_scratch(ctx, P, D, dev):
+def _take_backward_scratch(ctx, P, D, dev, depth=False):
     """(scratch, is_clear): the buffer the forward cleared, once; any later backward through the same graph
     (retain_graph) gets a fresh one that msgs_backward clears itself"""
     if bool(_C.lib.msgs_get_deterministic()) != bool(getattr(ctx, "det", False)):
@@ -260,7 +262,18 @@ def _take_backward_scratch(ctx, P, D, dev):
     ctx.grad_rec = None
     if rec is not None and not _C.lib.msgs_get_deterministic():
         return rec, 1
-    return _backward_scratch(P, D, dev), 0
+    return _backward_scratch(P, D, dev, depth), 0
+
+
+def _call_backward(lib, call, ctx, geom, binning, image, D, dL, dL_ddepth, scratch, grads, stream):
+    """msgs_backward, or msgs_backward_with_depth when the loss used the depth map (dL_ddepth: contiguous float32 [H,W])"""
+    args = (call.view_ref, call.g_ref, _ptr(ctx.radii), _ptr(geom), geom.numel(), D, _ptr(binning), binning.numel(),
+            _ptr(image), image.numel(), _ptr(dL))
+    tail = (_ptr(scratch), scratch.numel(), C.byref(grads), _C.timer_ptr(), stream)
+    if dL_ddepth is None:
+        _C.check(lib.msgs_backward(*args, *tail), "msgs_backward")
+    else:
+        _C.check(lib.msgs_backward_with_depth(*args, _ptr(dL_ddepth), *tail), "msgs_backward_with_depth")
 
 
 def set_deterministic(on=True):
@@ -679,7 +692,7 @@ class _RasterizeGaussians(torch.autograd.Function):
             ctx.dev = dev
             outs = (color, torch.zeros(H, W, device=dev), torch.zeros(H, W, device=dev),
                     torch.zeros(0, dtype=torch.int32, device=dev), torch.zeros(0, device=dev))
-            ctx.mark_non_differentiable(*outs[1:])
+            ctx.mark_non_differentiable(outs[1], *outs[3:])     # (depth stays differentiable: zero gradients)
             ctx.set_materialize_grads(False)
             return outs
         ctx.empty = False
@@ -692,8 +705,8 @@ class _RasterizeGaussians(torch.autograd.Function):
         ctx.radii = radii
         ctx.shapes = (means2D.shape, opacities.shape)
         _save_inputs(ctx, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp)
-        ctx.mark_non_differentiable(acc_ps, depth, radii, pixel_sizes)
-        ctx.set_materialize_grads(False)      # no zero-filled gradients for the four non-differentiable outputs
+        ctx.mark_non_differentiable(acc_ps, radii, pixel_sizes)     # depth is differentiable
+        ctx.set_materialize_grads(False)      # grad_depth is None unless the loss used the depth map: then the colour-only path
         return color, acc_ps, depth, radii, pixel_sizes
 
     @staticmethod
@@ -718,13 +731,11 @@ class _RasterizeGaussians(torch.autograd.Function):
             g_scales = torch.empty(P, 3, dtype=torch.float32, device=dev) if call.scales is not None else None
             g_rot = torch.empty(P, 4, dtype=torch.float32, device=dev) if call.rot is not None else None
             g_cov = torch.empty(P, 6, dtype=torch.float32, device=dev) if call.cov is not None else None
-            scratch, is_clear = _take_backward_scratch(ctx, P, D, dev)
+            dLd = _f32c(grad_depth) if grad_depth is not None else None
+            scratch, is_clear = _take_backward_scratch(ctx, P, D, dev, dLd is not None)
             grads = _C.Grads(_ptr(g_means3D), _ptr(g_means2D), _ptr(g_sh), _ptr(g_col), _ptr(g_opac),
                              _ptr(g_scales), _ptr(g_rot), _ptr(g_cov), None, None, None, is_clear)
-            _C.check(lib.msgs_backward(call.view_ref, call.g_ref, _ptr(ctx.radii), _ptr(geom),
-                                       geom.numel(), D, _ptr(binning), binning.numel(), _ptr(image),
-                                       image.numel(), _ptr(dL), _ptr(scratch), scratch.numel(), C.byref(grads),
-                                       _C.timer_ptr(), stream), "msgs_backward")
+            _call_backward(lib, call, ctx, geom, binning, image, D, dL, dLd, scratch, grads, stream)
         m2_shape, op_shape = ctx.shapes
         # occ_multiplier / dc_delta / pixel-size inputs / masks receive no gradient (DESIGN.md SPEC M5)
         return (g_means3D, g_means2D.view(m2_shape) if g_means2D.shape == m2_shape else g_means2D,
@@ -928,8 +939,8 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
         ctx.shapes = (means2D.shape, features_dc.shape, features_rest.shape, opacity_raw.shape)
         _snapshot_sinks(ctx, (xyz, features_dc, features_rest, opacity_raw, scaling_raw, rotation_raw))
         _save_inputs(ctx, xyz, features_dc, features_rest, opacity_raw, scaling_raw, rotation_raw)
-        ctx.mark_non_differentiable(acc_ps, depth, radii, pixel_sizes)
-        ctx.set_materialize_grads(False)      # no zero-filled gradients for the four non-differentiable outputs
+        ctx.mark_non_differentiable(acc_ps, radii, pixel_sizes)     # depth is differentiable
+        ctx.set_materialize_grads(False)      # grad_depth is None unless the loss used the depth map: then the colour-only path
         return color, acc_ps, depth, radii, pixel_sizes
 
     @staticmethod
@@ -974,15 +985,13 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
                 if factor is None:
                     g_dc, g_rest = _grad_out(kdc, dc_shape, dev), _grad_out(krest, rest_shape, dev)
                 g_opac, g_scal, g_rot = _grad_out(kop, op_shape, dev), _grad_out(ksc, (P, 3), dev), _grad_out(krot, (P, 4), dev)
-            scratch, is_clear = _take_backward_scratch(ctx, P, D, dev)
+            dLd = _f32c(grad_depth) if grad_depth is not None else None
+            scratch, is_clear = _take_backward_scratch(ctx, P, D, dev, dLd is not None)
             grads = _C.Grads(_ptr(g_xyz), _ptr(g_m2), None, _ptr(factor), _ptr(g_opac), _ptr(g_scal), _ptr(g_rot), None,
                              _ptr(g_dc), _ptr(g_rest),
                              C.c_void_p(ready.cuda_event) if (factor is not None and ready is not None) else None,
                              is_clear, acc_flag, ev_wait, ev_rec, C.addressof(adam) if adam is not None else None)
-            _C.check(lib.msgs_backward(call.view_ref, call.g_ref, _ptr(ctx.radii), _ptr(geom),
-                                       geom.numel(), D, _ptr(binning), binning.numel(), _ptr(image),
-                                       image.numel(), _ptr(dL), _ptr(scratch), scratch.numel(), C.byref(grads),
-                                       _C.timer_ptr(), stream), "msgs_backward")
+            _call_backward(lib, call, ctx, geom, binning, image, D, dL, dLd, scratch, grads, stream)
             if adam is not None:
                 step_opt.commit_step_in_backward(ctx.leaves)
         if accum is not None or adam is not None:   # the leaf gradients live in the accumulator / were consumed by the step
@@ -1010,8 +1019,8 @@ class _RasterizeGaussiansChained(torch.autograd.Function):
         _snapshot_sinks(ctx, (xyz, features_dc, features_rest, opacity_raw, scaling_raw, rotation_raw))
         _save_inputs(ctx, xyz, features_dc, features_rest, opacity_raw, scaling_raw, rotation_raw, shs, opacities,
                      scales, rotations)
-        ctx.mark_non_differentiable(acc_ps, depth, radii, pixel_sizes)
-        ctx.set_materialize_grads(False)      # no zero-filled gradients for the four non-differentiable outputs
+        ctx.mark_non_differentiable(acc_ps, radii, pixel_sizes)     # depth is differentiable
+        ctx.set_materialize_grads(False)      # grad_depth is None unless the loss used the depth map: then the colour-only path
         return color, acc_ps, depth, radii, pixel_sizes
 
     @staticmethod

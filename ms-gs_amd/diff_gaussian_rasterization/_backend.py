@@ -115,6 +115,8 @@ def _load():
     lib.msgs_get_deterministic.argtypes = []
     lib.msgs_backward_scratch_bytes_deterministic.restype = sz
     lib.msgs_backward_scratch_bytes_deterministic.argtypes = [C.c_int32, C.c_int64]
+    lib.msgs_backward_scratch_bytes_deterministic_depth.restype = sz
+    lib.msgs_backward_scratch_bytes_deterministic_depth.argtypes = [C.c_int32, C.c_int64]
     lib.msgs_set_backward_generation.restype = C.c_int
     lib.msgs_set_backward_generation.argtypes = [C.c_int32]
     lib.msgs_set_blend_granularity.restype = C.c_int
@@ -147,6 +149,9 @@ def _load():
     lib.msgs_backward.restype = C.c_int
     lib.msgs_backward.argtypes = [C.POINTER(View), C.POINTER(Gaussians), vp, vp, sz, C.c_int64, vp, sz, vp, sz,
                                   vp, vp, sz, C.POINTER(Grads), C.POINTER(Timing), vp]
+    lib.msgs_backward_with_depth.restype = C.c_int
+    lib.msgs_backward_with_depth.argtypes = [C.POINTER(View), C.POINTER(Gaussians), vp, vp, sz, C.c_int64, vp, sz, vp, sz,
+                                             vp, vp, vp, sz, C.POINTER(Grads), C.POINTER(Timing), vp]
     lib.msgs_backward_per_gaussian.restype = C.c_int
     lib.msgs_backward_per_gaussian.argtypes = [C.POINTER(View), C.POINTER(Gaussians), vp, vp, sz, vp, C.POINTER(Grads), vp]
     lib.msgs_sh_grad_from_views.restype = C.c_int
@@ -209,7 +214,8 @@ EXPORTS = ("msgs_abi_version", "msgs_error_string", "msgs_geom_bytes", "msgs_sta
            "msgs_blend_lane_stats", "msgs_backward_per_gaussian",
            "msgs_status_create", "msgs_status_destroy", "msgs_forward_launch", "msgs_forward_finish",
            "msgs_set_occlusion", "msgs_occlusion_stats", "msgs_forward_info", "msgs_binning_bytes_slab",
-           "msgs_stage2_scratch_bytes_slab", "msgs_slab_stats")
+           "msgs_stage2_scratch_bytes_slab", "msgs_slab_stats", "msgs_backward_with_depth",
+           "msgs_backward_scratch_bytes_deterministic_depth")
 
 
 def check(rc, where):
