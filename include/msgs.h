@@ -301,6 +301,30 @@ int msgs_backward_with_depth(const msgs_view_t* view, const msgs_gaussians_t* g,
                              const msgs_grads_t* grads,
                              const msgs_timing_t* timing, void* stream);
 
+/* msgs_backward_with_camera: msgs_backward_with_depth plus the gradients of the camera: dL_dviewmatrix [16],
+ * dL_dprojmatrix [16] and dL_dcampos [3], float32 device pointers in the layout of msgs_view_t's viewmatrix / projmatrix /
+ * campos, each NULL = not wanted.  All three NULL: exactly msgs_backward_with_depth (same kernels, same bits).  Otherwise the
+ * camera variant of the per-Gaussian kernel writes one row of double partial sums per workgroup to camera_scratch
+ * (>= msgs_camera_grad_scratch_bytes(P)) and two small launches add the rows in a fixed partition and order: no atomics, the
+ * same bits on every run.  The camera outputs are always overwritten (also under grads->accumulate), with 0 where an entry never enters
+ * the computation (viewmatrix column 3: flat 3, 7, 11, 15; projmatrix column 2: flat 2, 6, 10, 14) and for P = 0.  Culling,
+ * radii, tile assignment, sort order, filter weights and pixel sizes are constants; tanfovx / tanfovy and bg get no
+ * gradient.  Not with grads->adam_in_backward (MSGS_ERR_INVALID_ARG). */
+int msgs_backward_with_camera(const msgs_view_t* view, const msgs_gaussians_t* g,
+                              const int32_t* radii,
+                              const void* geom, size_t geom_bytes,
+                              int64_t num_instances,
+                              const void* binning, size_t binning_bytes,
+                              const void* image_state, size_t image_bytes,
+                              const float* dL_dcolor, const float* dL_ddepth,
+                              void* scratch, size_t scratch_bytes,
+                              const msgs_grads_t* grads,
+                              float* dL_dviewmatrix, float* dL_dprojmatrix, float* dL_dcampos,
+                              void* camera_scratch, size_t camera_scratch_bytes,
+                              const msgs_timing_t* timing, void* stream);
+/* bytes of msgs_backward_with_camera's camera_scratch for P Gaussians (no clearing needed) */
+size_t msgs_camera_grad_scratch_bytes(int32_t P);
+
 /* msgs_backward_per_gaussian: the per-Gaussian half of msgs_backward ALONE (2-D covariance backward, projection, SH,
  * scale / quaternion chain — upstream's computeCov2DCUDA + preprocessCUDA backward, SURVEY 2.2 K8 + K9) on per-Gaussian
  * 2-D gradients supplied by the caller instead of the blend backward's sums: sums2d [P,9] DOUBLES (device) =

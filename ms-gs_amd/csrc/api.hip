@@ -707,6 +707,14 @@ int forward_stage2_impl(const msgs_view_t* view, const msgs_gaussians_t* g, cons
 }
 }  // namespace
 
+namespace {
+// msgs_backward_with_depth (cam = NULL) and msgs_backward_with_camera
+int backward_impl(const msgs_view_t* view, const msgs_gaussians_t* g, const int32_t* radii, const void* geom_v,
+                  size_t geom_bytes, int64_t D, const void* binning_v, size_t binning_bytes, const void* image_v,
+                  size_t image_bytes, const float* dL_dcolor, const float* dL_ddepth, void* scratch_v, size_t scratch_bytes,
+                  const msgs_grads_t* grads, const CameraGrads* cam, const msgs_timing_t* timing, void* stream);
+}  // namespace
+
 extern "C" {
 
 int msgs_backward(const msgs_view_t* view, const msgs_gaussians_t* g, const int32_t* radii, const void* geom_v,
@@ -721,11 +729,50 @@ int msgs_backward_with_depth(const msgs_view_t* view, const msgs_gaussians_t* g,
                              size_t geom_bytes, int64_t D, const void* binning_v, size_t binning_bytes, const void* image_v,
                              size_t image_bytes, const float* dL_dcolor, const float* dL_ddepth, void* scratch_v,
                              size_t scratch_bytes, const msgs_grads_t* grads, const msgs_timing_t* timing, void* stream) {
+    return backward_impl(view, g, radii, geom_v, geom_bytes, D, binning_v, binning_bytes, image_v, image_bytes, dL_dcolor,
+                         dL_ddepth, scratch_v, scratch_bytes, grads, nullptr, timing, stream);
+}
+
+size_t msgs_camera_grad_scratch_bytes(int32_t P) { return camera_grad_rows_bytes(P); }
+
+int msgs_backward_with_camera(const msgs_view_t* view, const msgs_gaussians_t* g, const int32_t* radii, const void* geom_v,
+                              size_t geom_bytes, int64_t D, const void* binning_v, size_t binning_bytes, const void* image_v,
+                              size_t image_bytes, const float* dL_dcolor, const float* dL_ddepth, void* scratch_v,
+                              size_t scratch_bytes, const msgs_grads_t* grads, float* dL_dviewmatrix, float* dL_dprojmatrix,
+                              float* dL_dcampos, void* camera_scratch, size_t camera_scratch_bytes,
+                              const msgs_timing_t* timing, void* stream) {
+    if (!dL_dviewmatrix && !dL_dprojmatrix && !dL_dcampos)
+        return msgs_backward_with_depth(view, g, radii, geom_v, geom_bytes, D, binning_v, binning_bytes, image_v, image_bytes,
+                                        dL_dcolor, dL_ddepth, scratch_v, scratch_bytes, grads, timing, stream);
+    int rc = check_inputs(view, g);
+    if (rc) return rc;
+    if (!grads || grads->adam_in_backward) return MSGS_ERR_INVALID_ARG;      // out of scope: refused, not silently wrong
+    if (g->P > 0 && !camera_scratch) return MSGS_ERR_INVALID_ARG;
+    if (g->P > 0 && camera_scratch_bytes < msgs_camera_grad_scratch_bytes(g->P)) return MSGS_ERR_CAPACITY;
+    CameraGrads cam{dL_dviewmatrix, dL_dprojmatrix, dL_dcampos, (double*)camera_scratch};
+    return backward_impl(view, g, radii, geom_v, geom_bytes, D, binning_v, binning_bytes, image_v, image_bytes, dL_dcolor,
+                         dL_ddepth, scratch_v, scratch_bytes, grads, &cam, timing, stream);
+}
+}  // extern "C"
+
+namespace {
+int backward_impl(const msgs_view_t* view, const msgs_gaussians_t* g, const int32_t* radii, const void* geom_v,
+                  size_t geom_bytes, int64_t D, const void* binning_v, size_t binning_bytes, const void* image_v,
+                  size_t image_bytes, const float* dL_dcolor, const float* dL_ddepth, void* scratch_v, size_t scratch_bytes,
+                  const msgs_grads_t* grads, const CameraGrads* cam, const msgs_timing_t* timing, void* stream) {
     int rc = check_inputs(view, g);
     if (rc) return rc;
     if (!grads || !dL_dcolor) return MSGS_ERR_INVALID_ARG;
     const int P = g->P, W = view->image_width, H = view->image_height;
-    if (P == 0) return MSGS_OK;
+    if (P == 0) {
+        if (cam) {                      // no Gaussian: zero camera gradients (always overwritten)
+            hipStream_t s0 = (hipStream_t)stream;
+            if (cam->dL_dviewmatrix) HIP_TRY(hipMemsetAsync(cam->dL_dviewmatrix, 0, 16 * sizeof(float), s0));
+            if (cam->dL_dprojmatrix) HIP_TRY(hipMemsetAsync(cam->dL_dprojmatrix, 0, 16 * sizeof(float), s0));
+            if (cam->dL_dcampos) HIP_TRY(hipMemsetAsync(cam->dL_dcampos, 0, 3 * sizeof(float), s0));
+        }
+        return MSGS_OK;
+    }
     if (!radii || !geom_v || !binning_v || !image_v || !scratch_v) return MSGS_ERR_INVALID_ARG;
     const bool det = g_deterministic.load() != 0;
     if (geom_bytes < msgs_geom_bytes(P) || binning_bytes < msgs_binning_bytes(D, W, H) ||
@@ -784,12 +831,15 @@ int msgs_backward_with_depth(const msgs_view_t* view, const msgs_gaussians_t* g,
 
     tm.begin(MSGS_K_PREPROCESS_BWD);
     if (det)      // the nine TEXTBOOK sums per Gaussian ([P, 9] doubles; [P, 10] with depth) as they are
-        HIP_TRY(launch_preprocess_backward(vp, *g, radii, geom, grad_rec, *grads, s, true, dL_ddepth != nullptr));
+        HIP_TRY(launch_preprocess_backward(vp, *g, radii, geom, grad_rec, *grads, s, true, dL_ddepth != nullptr, cam));
     else
-        HIP_TRY(launch_preprocess_backward(vp, *g, radii, geom, grad_rec, *grads, s, false, dL_ddepth != nullptr));
+        HIP_TRY(launch_preprocess_backward(vp, *g, radii, geom, grad_rec, *grads, s, false, dL_ddepth != nullptr, cam));
     tm.end(MSGS_K_PREPROCESS_BWD);
     return debug_sync(view, s);
 }
+}  // namespace
+
+extern "C" {
 
 int msgs_backward_per_gaussian(const msgs_view_t* view, const msgs_gaussians_t* g, const int32_t* radii,
                                const void* geom_v, size_t geom_bytes, const double* sums2d, const msgs_grads_t* grads,

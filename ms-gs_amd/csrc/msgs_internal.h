@@ -333,6 +333,23 @@ struct AdamInBackward {
     AdamScalars a;
 };
 
+// Camera gradients (msgs_backward_with_camera): the CAMERA variants of the per-Gaussian backward write one
+// row of CAM_PARTIALS double partial sums per workgroup (stride CAM_ROW) — [0..11] dL/dV[4j + k], [12..23] dL/dPM[4j + {0,1,3}],
+// j = 0..3 and k = 0..2, [24..26] dL/dcampos — and camera_finish_kernel adds the rows (two passes, fixed partition and order).
+constexpr int CAM_PARTIALS = 27;
+constexpr int CAM_ROW = 32;
+struct CamPartials {
+    double* rows;
+};
+// where the camera gradients go (each float pointer NULL = not wanted; rows: msgs_camera_grad_scratch_bytes)
+struct CameraGrads {
+    float* dL_dviewmatrix;      // [16]
+    float* dL_dprojmatrix;      // [16]
+    float* dL_dcampos;          // [3]
+    double* rows;
+};
+size_t camera_grad_rows_bytes(int P);
+
 #if defined(__HIPCC__)
 
 __device__ __forceinline__ void adam_update(float& p, float g, float& m, float& v, float nss, const AdamScalars& a) {
@@ -598,7 +615,8 @@ int get_occlusion();
 int occlusion_block_log2(int gx, int gy);  // log2(tiles per side of a cover block) for a gx x gy grid (4 x 4 tiles unless the grid has more than 2048 such blocks)
 hipError_t launch_preprocess_backward(const ViewParams& vp, const msgs_gaussians_t& g, const int32_t* radii,
                                       const char* geom, const grad_acc_t* grad_rec, const msgs_grads_t& grads,
-                                      hipStream_t s, bool textbook = false, bool depth = false);
+                                      hipStream_t s, bool textbook = false, bool depth = false,
+                                      const CameraGrads* camera = nullptr);   // non-null: the CAMERA variants + camera_finish_kernel
 // literal.hip: the verification mode (msgs_set_deterministic) — the reference's blend loops restated literally
 hipError_t launch_blend_forward_literal(const ViewParams& vp, const char* geom, int P, const uint32_t* ids, const uint2* ranges,
                                         float* out_color, float* out_ps, float* out_depth, float* final_T, uint32_t* n_contrib,

@@ -15,6 +15,8 @@
 // are bit-reproducible against the CPU oracle.
 #include "msgs_internal.h"
 
+#include <type_traits>
+
 #pragma clang fp contract(off)
 
 namespace msgs {
@@ -710,6 +712,28 @@ __global__ __launch_bounds__(256) void preprocess_kernel(ViewParams vp, msgs_gau
 // ---------------------------------------------------------------------------------------------
 // K8 + K9
 // ---------------------------------------------------------------------------------------------
+// camera gradients (CAMERA variants only: the default variants keep their LDS size): the four waves' partial sums
+__device__ __forceinline__ double (&camera_lds())[4][CAM_PARTIALS] {
+    __shared__ double s[4][CAM_PARTIALS];
+    return s;
+}
+
+// ... and every thread's dL/d(p - campos)
+__device__ __forceinline__ float (&camera_dir_lds())[3][256] {
+    __shared__ float s[3][256];
+    return s;
+}
+
+// sum over the 64 lanes in a fixed butterfly (every lane ends with the same bits)
+__device__ __forceinline__ double wave_sum_f64(double v) {
+    for (int off = 32; off > 0; off >>= 1) {
+        const unsigned long long u = (unsigned long long)__double_as_longlong(v);
+        const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)u, off), hi = (unsigned)__shfl_xor((int)(unsigned)(u >> 32), off);
+        v += __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+    }
+    return v;
+}
+
 // (held to 96 registers = 5 waves per SIMD: measured 116 us with the compiler's 102 registers / 4 waves, 112 us with 5 waves and
 //  one spilled register, 125 us with 6 waves and 22 spills; 121 us before the rows were staged in two runs)
 // TEXTBOOK = true (msgs_backward_per_gaussian, the K8 + K9 isolation entry of the parity tests): grad_rec is NOT this
@@ -721,12 +745,20 @@ __global__ __launch_bounds__(256) void preprocess_kernel(ViewParams vp, msgs_gau
 // registers / LDS (zero for a Gaussian that was not rendered).
 // DEPTH = true (msgs_backward_with_depth): the record's slot 9 holds dL/dz (the textbook sums:
 // [P, 10]), and dL/dmeans3D gains dL/dz (V[2], V[6], V[10]) — z = view depth, the third row of the view matrix.
-template <bool TEXTBOOK, bool ADAM, bool DEPTH = false>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void preprocess_backward_kernel(ViewParams vp, msgs_gaussians_t g,
+// CAMERA = true (msgs_backward_with_camera, ADAM = false only): the workgroup's share of dL/dviewmatrix,
+// dL/dprojmatrix and dL/dcampos — 27 DOUBLE partial sums over its rendered Gaussians, in a fixed order per wave (below) and
+// the four waves in order through LDS — goes to row blockIdx.x of the camera scratch (`ad` is then a CamPartials);
+// camera_finish_kernel adds the rows.  Per lane only the factors live: dL/dt, dL/dh_{0,1,3}, (J dT) and p; the outer
+// products with ph = (p, 1) are formed at reduction time.
+// (the CAMERA variants are held to 4 waves per SIMD instead: at 5 their SH section spills)
+template <bool TEXTBOOK, bool ADAM, bool DEPTH = false, bool CAMERA = false>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CAMERA ? 4 : 5))) void preprocess_backward_kernel(ViewParams vp, msgs_gaussians_t g,
                                                                   const int32_t* __restrict__ radii,
                                                                   const char* __restrict__ geom,
                                                                   const grad_acc_t* __restrict__ grad_rec,
-                                                                  msgs_grads_t grads, AdamInBackward ad) {
+                                                                  msgs_grads_t grads,
+                                                                  std::conditional_t<CAMERA, CamPartials, AdamInBackward> ad) {
+    static_assert(!(CAMERA && ADAM), "camera gradients are not offered with the optimizer step in the backward");
     // 32 rows per wave: the SH rows of a wave's 64 Gaussians pass through LDS in two runs of 32 (below).  25 KB per workgroup
     // instead of 50: the kernel is latency-bound and its time follows the occupancy (measured at C3 with 1 / 2 / 3 workgroups
     // per CU: 252 / 147 / 121 us)
@@ -766,6 +798,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void p
     }
     uint32_t fl = 0;
     float p[3] = {0.f, 0.f, 0.f};
+    // CAMERA: dL/dt (view-space point), dL/dh_{0,1,3} (clip-space point) and (J dT)[c][k] = dL/dWr through T = J Wr (the
+    // un-normalised SH direction gradient dL/d(p - campos) goes to LDS where colour_backward forms it)
+    float cdt[3] = {0.f, 0.f, 0.f}, cdh[3] = {0.f, 0.f, 0.f}, cjt[9] = {};
 
     if (rendered) {
         Cam cm;
@@ -884,6 +919,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void p
                               (2 * vp.fy * c2.ty_c) * tz3 * dJ12;
 #pragma unroll
             for (int j = 0; j < 3; ++j) dmean[j] += V[4 * j + 0] * dtx + V[4 * j + 1] * dty + V[4 * j + 2] * dtz;
+            if constexpr (CAMERA) {
+                // J exactly as compute_cov2d formed it; T[r][c] = sum_k J[r][k] V[4c + k]
+                const float J00 = vp.fx / c2.tz, J02 = -(vp.fx * c2.tx_c) / (c2.tz * c2.tz);
+                const float J11 = vp.fy / c2.tz, J12 = -(vp.fy * c2.ty_c) / (c2.tz * c2.tz);
+                cdt[0] = dtx; cdt[1] = dty; cdt[2] = DEPTH ? dtz + gc.y : dtz;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    cjt[3 * c + 0] = J00 * dT0[c];
+                    cjt[3 * c + 1] = J11 * dT1[c];
+                    cjt[3 * c + 2] = J02 * dT0[c] + J12 * dT1[c];
+                }
+            }
         }
         // ---- projection backward ----
         {
@@ -895,6 +942,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void p
             for (int j = 0; j < 3; ++j)
                 dmean[j] += (cm.M[4 * j + 0] * m_w - cm.M[4 * j + 3] * mul1) * g2x +
                             (cm.M[4 * j + 1] * m_w - cm.M[4 * j + 3] * mul2) * g2y;
+            if constexpr (CAMERA) { cdh[0] = m_w * g2x; cdh[1] = m_w * g2y; cdh[2] = -(mul1 * g2x + mul2 * g2y); }
         }
         // ---- view-depth backward (z = V[2] x + V[6] y + V[10] z + V[14]; gc.y = dL/dz) ----
         if constexpr (DEPTH) {
@@ -936,6 +984,46 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void p
                 normalize_backward(qv, qnorm, dq);
             }
         }
+    }
+    // CAMERA: the 24 V / PM sums of this wave now, so that no camera factor stays live across the SH section.  The 18
+    // factors of the 64 lanes pass through the wave's (still unused) LDS rows; lane l < 48 then forms sum l % 24 over the
+    // lanes 32 (l / 24) .. + 31 in order, in double, and lane l < 24 adds its partner's half: [3j + k] = sum ph_j dL/dt_k
+    // (+ (J dT)[j][k] for j < 3), [12 + 3j + k] = sum ph_j dL/dh_{0,1,3}[k], ph = (p, 1).  No register array to unroll.
+    if constexpr (CAMERA) {
+        double(&s_cam)[4][CAM_PARTIALS] = camera_lds();
+        float* F = s_rows[wv];
+        if (live != 0) {                                                   // wave-uniform
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                F[(0 + k) * 64 + lane] = p[k];
+                F[(3 + k) * 64 + lane] = cdt[k];
+                F[(6 + k) * 64 + lane] = cdh[k];
+            }
+#pragma unroll
+            for (int k = 0; k < 9; ++k) F[(9 + k) * 64 + lane] = cjt[k];
+            wave_lds_fence();
+            const int m = lane % 24, half = lane / 24;
+            const int j = (m % 12) / 3, k = m % 3;
+            const float* fa = F + (m < 12 ? 3 + k : 6 + k) * 64;           // dL/dt_k | dL/dh_k
+            const float* fp = F + (j < 3 ? j : 0) * 64;                    // p_j (j = 3: ph_3 = 1)
+            const float* fj = F + (9 + 3 * (j < 3 ? j : 0) + k) * 64;     // (J dT)[j][k]
+            const bool pj = j < 3, wj = m < 12 && j < 3;
+            double acc = 0.0;
+            if (half < 2) {
+                const int l0 = 32 * half;
+#pragma unroll 8
+                for (int l = l0; l < l0 + 32; ++l) {
+                    const float a = fa[l], b = fp[l], c = fj[l];              // (read unconditionally: no branch per lane)
+                    acc += (pj ? (double)b : 1.0) * (double)a + (wj ? (double)c : 0.0);
+                }
+            }
+            const double other = __shfl(acc, (lane + 24) & 63);
+            if (lane < 24) s_cam[wv][lane] = acc + other;
+        } else if (lane < 24) {
+            s_cam[wv][lane] = 0.0;
+        }
+        float(&s_dir)[3][256] = camera_dir_lds();                          // (lanes not rendered: 0)
+        s_dir[0][threadIdx.x] = 0.f; s_dir[1][threadIdx.x] = 0.f; s_dir[2][threadIdx.x] = 0.f;
     }
     // ---- colour backward (the last contribution to dL/dmean) ----
     // sh: this Gaussian's 48 (or 3K) coefficients, dsh: where their gradient goes (the same LDS row when staged; nullptr = the
@@ -990,6 +1078,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void p
             dmean[0] += (ddir[0] - x * dotv) / len;
             dmean[1] += (ddir[1] - y * dotv) / len;
             dmean[2] += (ddir[2] - z * dotv) / len;
+            if constexpr (CAMERA) {       // to LDS at once: no register stays live across the SH section
+                float(&s_dir)[3][256] = camera_dir_lds();
+                s_dir[0][threadIdx.x] = (ddir[0] - x * dotv) / len;
+                s_dir[1][threadIdx.x] = (ddir[1] - y * dotv) / len;
+                s_dir[2][threadIdx.x] = (ddir[2] - z * dotv) / len;
+            }
         }
     };
     const bool do_colour = !g.colors_precomp;                 // wave-uniform
@@ -1037,6 +1131,24 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void p
         float* dsh = grads.dL_dshs && in_range ? grads.dL_dshs + (size_t)3 * K * i : nullptr;
         if (rendered) colour_backward(g.shs + (size_t)3 * K * i, dsh);
         else if (dsh) for (int k = 0; k < 3 * K; ++k) dsh[k] = 0.f;
+    }
+    if constexpr (CAMERA) {
+        // campos enters as p - campos: its gradient is minus the direction gradient (a butterfly per wave).  Then the four
+        // waves in order -> one row
+        double(&s_cam)[4][CAM_PARTIALS] = camera_lds();
+        float(&s_dir)[3][256] = camera_dir_lds();
+        const bool any = live != 0 && do_colour;                            // wave-uniform
+        wave_lds_fence();
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const double v = any ? -wave_sum_f64((double)s_dir[k][threadIdx.x]) : 0.0;
+            if (lane == 0) s_cam[wv][24 + k] = v;
+        }
+        __syncthreads();
+        if (threadIdx.x < CAM_PARTIALS) {
+            const int m = threadIdx.x;
+            ad.rows[(size_t)blockIdx.x * CAM_ROW + m] = ((s_cam[0][m] + s_cam[1][m]) + s_cam[2][m]) + s_cam[3][m];
+        }
     }
     if (!in_range) return;
 
@@ -1184,6 +1296,64 @@ __global__ __launch_bounds__(256) void sh_grad_from_views_kernel(int P, int n_vi
         coop_store_split_rows(s_rows[wv], d_dc, d_rest, i, in_range, wave_first, nrow, ~0ull, 48, lane, lane);
 }
 
+// The camera gradients from the CAMERA variants' rows, in two passes of this kernel (one pass for small P): workgroup b sums
+// the rows [b chunk, (b + 1) chunk) and writes one row to `out` (pass 1, CAM_SUM_GROUPS workgroups) — or, with out = NULL, the
+// float outputs (pass 2, one workgroup over those rows).  A single workgroup over all rows is bound by one CU's load rate
+// (19 us for the 1 MB of rows at C3).  Inside a workgroup: thread t loads columns 2 (t % 16) and 2 (t % 16) + 1 of the rows
+// t / 16, t / 16 + 64, ... (16-byte loads, 16 in flight) and adds them in row order; the 64 row groups then meet in a fixed
+// pairwise tree in LDS.  Double throughout, rounded to float once; a fixed partition and order, no atomics: the same bits on
+// every run.
+constexpr int CAM_FINISH_THREADS = 1024;
+constexpr int CAM_SUM_GROUPS = 64;
+__global__ __launch_bounds__(CAM_FINISH_THREADS) void camera_finish_kernel(const double* __restrict__ rows, int nrows, int chunk,
+                                                                            double* __restrict__ out, float* __restrict__ dV,
+                                                                            float* __restrict__ dPM, float* __restrict__ dcp) {
+    constexpr int PAIRS = CAM_ROW / 2, GROUPS = CAM_FINISH_THREADS / PAIRS, U = 16;
+    __shared__ double2 s_sum[GROUPS][PAIRS];
+    const int q = threadIdx.x % PAIRS, grp = threadIdx.x / PAIRS;
+    const int first = blockIdx.x * chunk, n = min(chunk, nrows - first);          // (n <= 0: a zero row)
+    const double2* r2 = reinterpret_cast<const double2*>(rows) + (size_t)first * PAIRS;
+    double2 acc = make_double2(0.0, 0.0);
+    int r = grp;
+    for (; r + (U - 1) * GROUPS < n; r += U * GROUPS) {
+        double2 v[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) v[u] = r2[(size_t)(r + u * GROUPS) * PAIRS + q];
+#pragma unroll
+        for (int u = 0; u < U; ++u) { acc.x += v[u].x; acc.y += v[u].y; }
+    }
+    for (; r < n; r += GROUPS) {
+        const double2 v = r2[(size_t)r * PAIRS + q];
+        acc.x += v.x; acc.y += v.y;
+    }
+    s_sum[grp][q] = acc;
+    __syncthreads();
+#pragma unroll
+    for (int h = GROUPS / 2; h > 0; h >>= 1) {
+        if (grp < h) {
+            const double2 o = s_sum[grp + h][q];
+            s_sum[grp][q] = make_double2(s_sum[grp][q].x + o.x, s_sum[grp][q].y + o.y);
+        }
+        __syncthreads();
+    }
+    if (out) {
+        if (threadIdx.x < PAIRS) reinterpret_cast<double2*>(out)[(size_t)blockIdx.x * PAIRS + threadIdx.x] = s_sum[0][threadIdx.x];
+        return;
+    }
+    if (threadIdx.x >= 35) return;
+    const int t = threadIdx.x;
+    auto total = [&](int m) { return (float)((m & 1) ? s_sum[0][m >> 1].y : s_sum[0][m >> 1].x); };
+    if (t < 16) {                                           // V[4j + k]: column 3 never enters (t = (p, 1) V, k < 3)
+        const int j = t >> 2, k = t & 3;
+        if (dV) dV[t] = k < 3 ? total(3 * j + k) : 0.f;
+    } else if (t < 32) {                                    // PM[4j + k]: column 2 never enters (h_2 is not used)
+        const int f = t - 16, j = f >> 2, k = f & 3;
+        if (dPM) dPM[f] = k == 2 ? 0.f : total(12 + 3 * j + (k == 3 ? 2 : k));
+    } else if (dcp) {
+        dcp[t - 32] = total(24 + (t - 32));
+    }
+}
+
 __global__ void mark_visible_kernel(int P, const float* __restrict__ means3D, const float* __restrict__ V,
                                     uint8_t* __restrict__ present) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1198,6 +1368,11 @@ __global__ void mark_visible_kernel(int P, const float* __restrict__ means3D, co
 }
 
 }  // namespace
+
+// one row of CAM_ROW doubles per workgroup of the per-Gaussian backward, then the CAM_SUM_GROUPS rows of the first sum pass
+size_t camera_grad_rows_bytes(int P) {
+    return align256(sizeof(double) * CAM_ROW * (size_t)(((P > 0 ? P : 1) + 255) / 256)) + sizeof(double) * CAM_ROW * CAM_SUM_GROUPS;
+}
 
 hipError_t launch_preprocess(const ViewParams& vp, const msgs_gaussians_t& g, int32_t* radii, float* pixel_sizes,
                              char* geom, hipStream_t s, ZeroJob zj, uint32_t* heavy_list, uint32_t* heavy_count, uint32_t* heavy_blk,
@@ -1214,7 +1389,7 @@ hipError_t launch_preprocess(const ViewParams& vp, const msgs_gaussians_t& g, in
 
 hipError_t launch_preprocess_backward(const ViewParams& vp, const msgs_gaussians_t& g, const int32_t* radii,
                                       const char* geom, const grad_acc_t* grad_rec, const msgs_grads_t& grads,
-                                      hipStream_t s, bool textbook, bool depth) {
+                                      hipStream_t s, bool textbook, bool depth, const CameraGrads* camera) {
     if (g.P == 0) return hipSuccess;
     // textbook: grad_rec holds [P, 9] doubles — the TEXTBOOK 2-D gradients (msgs_backward_per_gaussian; the verification mode)
     static_assert(sizeof(grad_acc_t) == 8, "the textbook sums are doubles");
@@ -1245,6 +1420,30 @@ hipError_t launch_preprocess_backward(const ViewParams& vp, const msgs_gaussians
         ad.a = adam_scalars(aib->step, aib->beta1, aib->beta2, aib->eps);
     }
     const dim3 grid((g.P + 255) / 256), block(256);
+    if (camera) {            // camera gradients (msgs_backward_with_camera; never with the optimizer step, api.hip refuses it)
+        if (aib) return hipErrorInvalidValue;
+        const CamPartials cp{camera->rows};
+        if (textbook && depth) hipLaunchKernelGGL((preprocess_backward_kernel<true, false, true, true>), grid, block, 0, s, vp, g, radii, geom, grad_rec, grads, cp);
+        else if (textbook) hipLaunchKernelGGL((preprocess_backward_kernel<true, false, false, true>), grid, block, 0, s, vp, g, radii, geom, grad_rec, grads, cp);
+        else if (depth) hipLaunchKernelGGL((preprocess_backward_kernel<false, false, true, true>), grid, block, 0, s, vp, g, radii, geom, grad_rec, grads, cp);
+        else hipLaunchKernelGGL((preprocess_backward_kernel<false, false, false, true>), grid, block, 0, s, vp, g, radii, geom, grad_rec, grads, cp);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess && grads.accumulated) e = hipEventRecord((hipEvent_t)grads.accumulated, s);
+        if (e != hipSuccess) return e;
+        const int nrows = (int)grid.x;
+        const double* rows = camera->rows;
+        if (nrows > 4 * CAM_SUM_GROUPS) {        // pass 1: CAM_SUM_GROUPS rows behind the K9 rows (camera_grad_rows_bytes)
+            double* part = camera->rows + align256(sizeof(double) * CAM_ROW * (size_t)nrows) / sizeof(double);
+            const int chunk = (nrows + CAM_SUM_GROUPS - 1) / CAM_SUM_GROUPS;
+            hipLaunchKernelGGL(camera_finish_kernel, dim3(CAM_SUM_GROUPS), dim3(CAM_FINISH_THREADS), 0, s, rows, nrows, chunk, part,
+                               (float*)nullptr, (float*)nullptr, (float*)nullptr);
+            rows = part;
+        }
+        const int n2 = rows == camera->rows ? nrows : CAM_SUM_GROUPS;
+        hipLaunchKernelGGL(camera_finish_kernel, dim3(1), dim3(CAM_FINISH_THREADS), 0, s, rows, n2, n2, (double*)nullptr,
+                           camera->dL_dviewmatrix, camera->dL_dprojmatrix, camera->dL_dcampos);
+        return hipGetLastError();
+    }
     if (depth) {             // record slot 9 = dL/dz (msgs_backward_with_depth)
         if (textbook && aib) hipLaunchKernelGGL((preprocess_backward_kernel<true, true, true>), grid, block, 0, s, vp, g, radii, geom, grad_rec, grads, ad);
         else if (textbook) hipLaunchKernelGGL((preprocess_backward_kernel<true, false, true>), grid, block, 0, s, vp, g, radii, geom, grad_rec, grads, ad);

@@ -265,15 +265,69 @@ def _take_backward_scratch(ctx, P, D, dev, depth=False):
     return _backward_scratch(P, D, dev, depth), 0
 
 
-def _call_backward(lib, call, ctx, geom, binning, image, D, dL, dL_ddepth, scratch, grads, stream):
-    """msgs_backward, or msgs_backward_with_depth when the loss used the depth map (dL_ddepth: contiguous float32 [H,W])"""
+def _call_backward(lib, call, ctx, geom, binning, image, D, dL, dL_ddepth, scratch, grads, stream, camera=None):
+    """msgs_backward, or msgs_backward_with_depth when the loss used the depth map (dL_ddepth: contiguous float32 [H,W]), or
+    msgs_backward_with_camera when camera gradients are wanted (camera: _CameraGrads)"""
     args = (call.view_ref, call.g_ref, _ptr(ctx.radii), _ptr(geom), geom.numel(), D, _ptr(binning), binning.numel(),
             _ptr(image), image.numel(), _ptr(dL))
     tail = (_ptr(scratch), scratch.numel(), C.byref(grads), _C.timer_ptr(), stream)
-    if dL_ddepth is None:
+    if camera is not None:
+        cs = camera.scratch
+        _C.check(lib.msgs_backward_with_camera(*args, _ptr(dL_ddepth), *tail[:3], _ptr(camera.dV), _ptr(camera.dPM),
+                                               _ptr(camera.dcp), _ptr(cs), cs.numel(), *tail[3:]),
+                 "msgs_backward_with_camera")
+    elif dL_ddepth is None:
         _C.check(lib.msgs_backward(*args, *tail), "msgs_backward")
     else:
         _C.check(lib.msgs_backward_with_depth(*args, _ptr(dL_ddepth), *tail), "msgs_backward_with_depth")
+
+
+# Camera gradients (DESIGN.md 2, M8).  autograd does not look inside the settings NamedTuple, so when grad mode is on and
+# one of its viewmatrix / projmatrix / campos requires grad, those three tensors also go to the autograd Function as extra
+# trailing inputs; the backward then returns their gradients (in each tensor's own shape, dtype and device).  Otherwise
+# nothing is added and the call is exactly the one without camera gradients.
+def _camera_inputs(rs):
+    if not torch.is_grad_enabled():
+        return ()
+    cam = (rs.viewmatrix, rs.projmatrix, rs.campos)
+    return cam if any(torch.is_tensor(t) and t.requires_grad for t in cam) else ()
+
+
+def _note_camera(ctx, camera):
+    """forward: which camera inputs want a gradient (ctx.camera: () or three (shape, dtype, device) | None)"""
+    if not camera:
+        ctx.camera = ()
+        return
+    want = ctx.needs_input_grad[-3:]
+    ctx.camera = tuple((t.shape, t.dtype, t.device) if w else None for t, w in zip(camera, want))
+
+
+def _refuse_camera_with(camera):
+    """the optimizer step inside the backward and the view-parallel exchange of the SH factors do not offer camera
+    gradients: refused before anything is launched"""
+    if not camera:
+        return
+    if getattr(_step_in_backward, "opt", None) is not None:
+        raise ValueError("camera gradients (a viewmatrix / projmatrix / campos that requires grad) cannot be combined with "
+                         "set_optimizer_in_backward")
+    if _sinks.sh_factor[0] is not None:
+        raise ValueError("camera gradients (a viewmatrix / projmatrix / campos that requires grad) cannot be combined with "
+                         "the factored SH gradient of the view-parallel exchange")
+
+
+class _CameraGrads:
+    """float32 outputs of msgs_backward_with_camera (None = not wanted) and its scratch"""
+
+    def __init__(self, ctx, P, dev):
+        vm, pm, cp = ctx.camera
+        self.dV = torch.empty(16, dtype=torch.float32, device=dev) if vm is not None else None
+        self.dPM = torch.empty(16, dtype=torch.float32, device=dev) if pm is not None else None
+        self.dcp = torch.empty(3, dtype=torch.float32, device=dev) if cp is not None else None
+        self.scratch = _bytes(_C.lib.msgs_camera_grad_scratch_bytes(P), dev)
+
+    def grads(self, ctx):
+        return tuple(None if m is None else g.view(m[0]).to(device=m[2], dtype=m[1])
+                     for g, m in zip((self.dV, self.dPM, self.dcp), ctx.camera))
 
 
 def set_deterministic(on=True):
@@ -676,7 +730,8 @@ def _forward_impl(call, grad_rec=None, backward_follows=False):
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                max_pixel_sizes, min_pixel_sizes, occ_multiplier, dc_delta, base_mask, raster_settings):
+                max_pixel_sizes, min_pixel_sizes, occ_multiplier, dc_delta, base_mask, raster_settings, *camera):
+        _note_camera(ctx, camera)
         if means3D.shape[0] == 0:
             # nothing to rasterize: background image, no native call (every per-Gaussian tensor is empty,
             # which upstream's convention cannot tell apart from "not provided")
@@ -712,7 +767,8 @@ class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_color, grad_acc_ps, grad_depth, grad_radii, grad_pixel_sizes):
         if ctx.empty:
-            return tuple(torch.zeros(s, device=ctx.dev) for s in ctx.in_shapes) + (None,) * 6
+            cam = tuple(None if m is None else torch.zeros(m[0], dtype=m[1], device=m[2]) for m in ctx.camera)
+            return tuple(torch.zeros(s, device=ctx.dev) for s in ctx.in_shapes) + (None,) * 6 + cam
         _check_saved(ctx)
         call = ctx.call
         if grad_color is None:
@@ -735,12 +791,13 @@ class _RasterizeGaussians(torch.autograd.Function):
             scratch, is_clear = _take_backward_scratch(ctx, P, D, dev, dLd is not None)
             grads = _C.Grads(_ptr(g_means3D), _ptr(g_means2D), _ptr(g_sh), _ptr(g_col), _ptr(g_opac),
                              _ptr(g_scales), _ptr(g_rot), _ptr(g_cov), None, None, None, is_clear)
-            _call_backward(lib, call, ctx, geom, binning, image, D, dL, dLd, scratch, grads, stream)
+            cam = _CameraGrads(ctx, P, dev) if ctx.camera else None
+            _call_backward(lib, call, ctx, geom, binning, image, D, dL, dLd, scratch, grads, stream, cam)
         m2_shape, op_shape = ctx.shapes
         # occ_multiplier / dc_delta / pixel-size inputs / masks receive no gradient (DESIGN.md SPEC M5)
         return (g_means3D, g_means2D.view(m2_shape) if g_means2D.shape == m2_shape else g_means2D,
                 g_sh, g_col, g_opac.view(op_shape), g_scales, g_rot, g_cov,
-                None, None, None, None, None, None)
+                None, None, None, None, None, None) + (cam.grads(ctx) if cam is not None else ())
 
 
 # Gradient sinks (view-parallel training): a trainer that exchanges gradients through one flat bucket registers, per leaf
@@ -928,9 +985,11 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, xyz, means2D, features_dc, features_rest, opacity_raw, scaling_raw, rotation_raw,
-                max_pixel_sizes, min_pixel_sizes, occ_multiplier, dc_delta, base_mask, raster_settings):
+                max_pixel_sizes, min_pixel_sizes, occ_multiplier, dc_delta, base_mask, raster_settings, *camera):
         if xyz.shape[0] == 0:
             raise ValueError("rasterize_gaussians_raw: empty model")
+        _refuse_camera_with(camera)
+        _note_camera(ctx, camera)
         call = _Call(raster_settings, xyz, None, None, opacity_raw, scaling_raw, rotation_raw, None,
                      _opt(max_pixel_sizes), _opt(min_pixel_sizes), _opt(occ_multiplier), _opt(dc_delta),
                      _opt(base_mask), raw_features=(features_dc, features_rest))
@@ -991,12 +1050,14 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
                              _ptr(g_dc), _ptr(g_rest),
                              C.c_void_p(ready.cuda_event) if (factor is not None and ready is not None) else None,
                              is_clear, acc_flag, ev_wait, ev_rec, C.addressof(adam) if adam is not None else None)
-            _call_backward(lib, call, ctx, geom, binning, image, D, dL, dLd, scratch, grads, stream)
+            cam = _CameraGrads(ctx, P, dev) if ctx.camera else None
+            _call_backward(lib, call, ctx, geom, binning, image, D, dL, dLd, scratch, grads, stream, cam)
             if adam is not None:
                 step_opt.commit_step_in_backward(ctx.leaves)
+        g_cam = cam.grads(ctx) if cam is not None else ()
         if accum is not None or adam is not None:   # the leaf gradients live in the accumulator / were consumed by the step
-            return (None, g_m2.view(m2_shape), None, None, None, None, None, None, None, None, None, None, None)
-        return (g_xyz, g_m2.view(m2_shape), g_dc, g_rest, g_opac, g_scal, g_rot, None, None, None, None, None, None)
+            return (None, g_m2.view(m2_shape), None, None, None, None, None, None, None, None, None, None, None) + g_cam
+        return (g_xyz, g_m2.view(m2_shape), g_dc, g_rest, g_opac, g_scal, g_rot, None, None, None, None, None, None) + g_cam
 
 
 class _RasterizeGaussiansChained(torch.autograd.Function):
@@ -1009,7 +1070,9 @@ class _RasterizeGaussiansChained(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xyz, means2D, features_dc, features_rest, opacity_raw, scaling_raw, rotation_raw,
                 shs, opacities, scales, rotations, max_pixel_sizes, min_pixel_sizes, occ_multiplier, dc_delta, base_mask,
-                raster_settings):
+                raster_settings, *camera):
+        _refuse_camera_with(camera)
+        _note_camera(ctx, camera)
         call = _Call(raster_settings, xyz, _opt(shs), None, opacities, scales, rotations, None,
                      _opt(max_pixel_sizes), _opt(min_pixel_sizes), _opt(occ_multiplier), _opt(dc_delta),
                      _opt(base_mask), raw_features=(features_dc, features_rest), rotations_raw=rotation_raw)
@@ -1025,8 +1088,8 @@ class _RasterizeGaussiansChained(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_color, grad_acc_ps, grad_depth, grad_radii, grad_pixel_sizes):
-        return _RasterizeGaussiansRaw.backward(ctx, grad_color, grad_acc_ps, grad_depth, grad_radii,
-                                               grad_pixel_sizes)[:7] + (None,) * 10
+        g = _RasterizeGaussiansRaw.backward(ctx, grad_color, grad_acc_ps, grad_depth, grad_radii, grad_pixel_sizes)
+        return g[:7] + (None,) * 10 + g[13:]            # (camera gradients, when asked for, at the end)
 
 
 # Recognition of the reference's getters (scene/gaussian_model.py:127-153) in the autograd graph of the arguments of
@@ -1117,7 +1180,7 @@ def rasterize_gaussians_raw(xyz, means2D, features_dc, features_rest, opacity_ra
     _note_grad_mode()
     return _RasterizeGaussiansRaw.apply(xyz, means2D, features_dc, features_rest, opacity_raw, scaling_raw,
                                         rotation_raw, max_pixel_sizes, min_pixel_sizes, occ_multiplier, dc_delta,
-                                        base_mask, raster_settings)
+                                        base_mask, raster_settings, *_camera_inputs(raster_settings))
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
@@ -1125,7 +1188,7 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
     _note_grad_mode()
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
                                      cov3Ds_precomp, max_pixel_sizes, min_pixel_sizes, occ_multiplier, dc_delta,
-                                     base_mask, raster_settings)
+                                     base_mask, raster_settings, *_camera_inputs(raster_settings))
 
 
 class GaussianRasterizer(nn.Module):
@@ -1213,7 +1276,8 @@ class GaussianRasterizer(nn.Module):
                 return _RasterizeGaussiansChained.apply(
                     means3D, means2D, *leaves, shs.detach() if _chain_reads_cat else empty, opacities.detach(), scales.detach(),
                     rotations.detach(),
-                    o(max_pixel_sizes), o(min_pixel_sizes), o(occ_multiplier), o(dc_delta), o(base_mask), rs)
+                    o(max_pixel_sizes), o(min_pixel_sizes), o(occ_multiplier), o(dc_delta), o(base_mask), rs,
+                    *_camera_inputs(rs))
         return rasterize_gaussians(
             means3D, means2D,
             shs if shs is not None else empty,

@@ -152,6 +152,11 @@ def _load():
     lib.msgs_backward_with_depth.restype = C.c_int
     lib.msgs_backward_with_depth.argtypes = [C.POINTER(View), C.POINTER(Gaussians), vp, vp, sz, C.c_int64, vp, sz, vp, sz,
                                              vp, vp, vp, sz, C.POINTER(Grads), C.POINTER(Timing), vp]
+    lib.msgs_backward_with_camera.restype = C.c_int
+    lib.msgs_backward_with_camera.argtypes = [C.POINTER(View), C.POINTER(Gaussians), vp, vp, sz, C.c_int64, vp, sz, vp, sz,
+                                              vp, vp, vp, sz, C.POINTER(Grads), vp, vp, vp, vp, sz, C.POINTER(Timing), vp]
+    lib.msgs_camera_grad_scratch_bytes.restype = sz
+    lib.msgs_camera_grad_scratch_bytes.argtypes = [C.c_int32]
     lib.msgs_backward_per_gaussian.restype = C.c_int
     lib.msgs_backward_per_gaussian.argtypes = [C.POINTER(View), C.POINTER(Gaussians), vp, vp, sz, vp, C.POINTER(Grads), vp]
     lib.msgs_sh_grad_from_views.restype = C.c_int
@@ -215,7 +220,7 @@ EXPORTS = ("msgs_abi_version", "msgs_error_string", "msgs_geom_bytes", "msgs_sta
            "msgs_status_create", "msgs_status_destroy", "msgs_forward_launch", "msgs_forward_finish",
            "msgs_set_occlusion", "msgs_occlusion_stats", "msgs_forward_info", "msgs_binning_bytes_slab",
            "msgs_stage2_scratch_bytes_slab", "msgs_slab_stats", "msgs_backward_with_depth",
-           "msgs_backward_scratch_bytes_deterministic_depth")
+           "msgs_backward_scratch_bytes_deterministic_depth", "msgs_backward_with_camera", "msgs_camera_grad_scratch_bytes")
 
 
 def check(rc, where):
