@@ -21,9 +21,13 @@ Workload (config.workload):
           `exchange.dense_pipelined` (that all-reduce overlapped with the NEXT view: only valid when an optimizer step
           covers >= 2 views per GPU) and `exchange.without_exchange`.
 
-Output: ONE JSON line on rank 0 (see the driver contract in the task statement) carrying `roofline`
-(dominant blend kernel: algorithmic bytes / HIP-event time / 8 TB/s) and `cpu_baseline` (the CPU oracle
-timed on this box's host cores on a bounded sample).  With --dump-outputs DIR rank 0 also writes what the last timed step
+Output: ONE JSON line on rank 0.  A plain run sets up, warms up, times the
+steps, writes --dump-outputs and prints the line; `kernel_ms` then holds only the blend kernel(s) timed live inside the timed
+region.  At N > 1 the line also carries the exchange variants above.  With --full the run goes on to measure everything else:
+`roofline` (dominant blend kernel: algorithmic bytes / HIP-event time / 8 TB/s, per-kernel figures from extra steps),
+`median_of_50`, `default_host_settings`, the pyramid levels, the fused entry, two views in flight, the training iteration, the
+C2 / C5 configs, the reference's schedule, the verification mode and `cpu_baseline` (the CPU oracle timed on the host cores);
+the --no-* options drop single legs of a --full run.  With --dump-outputs DIR rank 0 also writes what the last timed step
 computed (image planes, per-Gaussian outputs and gradients) as DIR/<name>.npy; the inputs are seeded, so two builds run
 with the same arguments can be compared array for array.
 """
@@ -431,6 +435,16 @@ def algorithmic_bytes(P, W, H, D, D_trav, V):
             "preprocess_bwd": V * (309 + 36 + 24) + V * 236}
 
 
+def mean_kernel_ms(timers):
+    """{kernel class: mean ms over the KernelTimers that recorded it}"""
+    acc = {}
+    for t in timers:
+        for k, v in t.read_ms().items():
+            if v >= 0:
+                acc.setdefault(k, []).append(v)
+    return {k: round(float(np.mean(v)), 4) for k, v in acc.items()}
+
+
 def binning_counts(dgr, ctx, P, dev):
     """(D, D_trav, V) of the forward whose autograd node is `ctx` (msgs_binning_stats)"""
     import ctypes as C
@@ -758,6 +772,10 @@ def main():
     ap.add_argument("--gaussians", type=int, default=1_000_000)
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, measure every informational leg as well (roofline, per-kernel times, pyramid, "
+                         "fused entry, two views, training iteration, C2 / C5, reference schedule, verification mode, CPU "
+                         "baseline); a plain run stops after the timed steps and --dump-outputs")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-timing", action="store_true")
     ap.add_argument("--no-pyramid", action="store_true")
@@ -846,7 +864,8 @@ def main():
     # HIP events recorded by the library on the stream it launches on, INSIDE the timed region: the two blend kernels (the
     # roofline's dominant kernel is one of them) on every 4th timed step.  An event record costs ~10 us of queue latency on this
     # runtime: all nine kernel classes on every 4th step slowed the timed region by 4 % (1.106 vs 1.066 ms per step, round 4),
-    # so the other seven classes are timed on extra steps AFTER the timed region (per_kernel, below).
+    # so the other seven classes are timed on extra steps AFTER the timed region (per_kernel, below; --full only).  The live
+    # events are recorded in plain runs too: the timed steps are the same launches with and without --full.
     TIMER_STRIDE = 4
     # at 1080p and above the backward blend is the dominant kernel by a wide margin (0.31 vs 0.18 ms at C3): it alone is timed
     # live there (two event records on every 4th step); smaller images time both blend kernels live
@@ -959,7 +978,7 @@ def main():
     ms_per_step = 1e3 * elapsed / args.steps
     value = world * (W * H / 1e6) / (elapsed / args.steps)
     # every kernel class on a few extra steps outside the timed region (roofline.per_kernel)
-    all_timers = [] if args.no_kernel_timing else [dgr._C.KernelTimer() for _ in range(4)]
+    all_timers = [] if args.no_kernel_timing or not args.full else [dgr._C.KernelTimer() for _ in range(4)]
     for t_ in all_timers:
         step(t_)
     torch.cuda.synchronize()
@@ -968,7 +987,7 @@ def main():
     # SURVEY 8(d) form of the same measurement (N = 1): median of >= 50 steps, each bracketed by HIP events on the compute
     # stream (the library launches on torch's current stream, so torch.cuda.Event sees its kernels)
     median50 = None
-    if world == 1:
+    if world == 1 and args.full:
         evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(50)]
         dgr._C.set_timer(None)
         for a_, b_ in evs:
@@ -986,7 +1005,7 @@ def main():
     # Python's collector on, autograd's backward on its device thread (the thread pools stay sized to the CPU quota: that cannot
     # be undone inside this process) — so that what the tuned settings are worth is visible next to `value`
     default_host = None
-    if world == 1:
+    if world == 1 and args.full:
         try:
             if SINGLE_THREAD_BACKWARD:
                 torch.autograd.set_multithreading_enabled(True)
@@ -1011,7 +1030,8 @@ def main():
     #   (b) that dense all-reduce overlapped with the rendering of the NEXT view (two buckets; an optimizer step then
     #       has to cover >= 2 views per GPU)
     #   (c) no exchange at all: pure view-sharded rendering fwd+bwd
-    # `value` above INCLUDES the complete (factored) exchange in every step.
+    # `value` above INCLUDES the complete (factored) exchange in every step.  These run with and without --full: they are
+    # what the C4 line is defined to carry next to its headline.
     extra = None
     if world > 1:
         from view_parallel import FlatGradBucket
@@ -1110,7 +1130,7 @@ def main():
     result = {
         "metric": "Mpixels/s fwd+bwd @1080p, 1M Gaussians; fraction of HBM roofline",
         "value": round(value, 3), "unit": "Mpixels/s", "n_gpus": world, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
+        "warmup": args.warmup, "full": bool(args.full), "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
         "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
         "timing_note": "Python's cyclic GC is collected before the warm-up of and paused during every timed region (a full collection "
                        f"of this process takes 30-70 ms); OMP/MKL/torch intra-op pools = {HOST_THREADS} threads (the container's CPU "
@@ -1160,7 +1180,21 @@ def main():
         # which communicator carried the exchange: "nccl" IS RCCL on ROCm; rccl_ranks = its world size (None on the gloo rehearsal)
         result["config"]["backend"] = dist.get_backend()
         result["config"]["rccl_ranks"] = dist.get_world_size() if dist.get_backend() == "nccl" else None
-    if rank == 0:
+    if extra is not None:
+        result["exchange"] = extra
+        result["two_views_per_rank"] = two_views
+    kernels = None
+    if rank == 0 and timers:
+        kernels = {**mean_kernel_ms(all_timers),             # all nine classes, steps after the timed region (--full)
+                   **mean_kernel_ms(timers.values())}        # the blend pair, live inside the timed region: these win
+    result["kernel_ms"] = kernels
+    result["kernel_timing"] = (None if not timers else
+                               f"HIP events recorded by the library: {' / '.join(LIVE)} live on {len(timers)} of the "
+                               f"{args.steps} timed steps, " + (f"the other classes on {len(all_timers)} steps after the timed "
+                                                                "region" if all_timers else "the other classes only with --full"))
+    if rank == 0 and not args.full:
+        print(json.dumps(result), flush=True)
+    if rank == 0 and args.full:
         # ---- roofline of the dominant kernel (per launch, averaged over the timed steps) ----
         stats = None
         try:
@@ -1196,20 +1230,6 @@ def main():
                                             "lane_efficiency": round(int(o3[5]) / max(64 * int(o3[4]), 1), 4)}
         except Exception as e:  # statistics are informative; never fail the bench line on them
             stats = {"error": repr(e)}
-        kernels = None
-        if timers:
-            acc = {}
-            for t in all_timers:                          # all nine classes, steps after the timed region
-                for k, v in t.read_ms().items():
-                    if v >= 0:
-                        acc.setdefault(k, []).append(v)
-            live = {}
-            for t in timers.values():                     # the blend pair, live inside the timed region: these win
-                for k, v in t.read_ms().items():
-                    if v >= 0:
-                        live.setdefault(k, []).append(v)
-            acc.update(live)
-            kernels = {k: round(float(np.mean(v)), 4) for k, v in acc.items()}
         roof = None
         if kernels and stats and "D_trav" in stats:
             N = W * H
@@ -1378,13 +1398,6 @@ def main():
         result["roofline"] = roof
         result["median_of_50"] = median50
         result["default_host_settings"] = default_host
-        result["kernel_ms"] = kernels
-        result["kernel_timing"] = (None if not timers else
-                                   f"HIP events recorded by the library: {' / '.join(LIVE)} live on {len(timers)} of the "
-                                   f"{args.steps} timed steps, the other classes on {len(all_timers)} steps after the timed region")
-        if extra is not None:
-            result["exchange"] = extra
-            result["two_views_per_rank"] = two_views
         # the reference's own measurement: render time per resolution scale (train.py:488-496,541; viewer.py:67-81)
         if world == 1 and (P, W, H) == (1_000_000, 1920, 1080) and not args.no_pyramid:
             try:
