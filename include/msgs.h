@@ -28,9 +28,9 @@
  * autograd thread).  Not stateless:
  *   - four PROCESS-WIDE mode flags: msgs_set_deterministic, msgs_set_backward_generation, msgs_set_blend_granularity,
  *     msgs_set_occlusion (the last three only choose between code paths that give the same results);
- *   - six environment variables latched on first use (process-wide): the initial values of the four flags
- *     (MSGS_DETERMINISTIC, MSGS_BWD_GEN, MSGS_BLEND_GRANULARITY, MSGS_NO_OCCLUSION) and MSGS_BLOCKING_SYNC,
- *     MSGS_NO_SPECULATIVE_STAGE2 — how the host learns the instance count; none changes a result.
+ *   - five environment variables latched on first use (process-wide): the initial values of the four flags
+ *     (MSGS_DETERMINISTIC, MSGS_BWD_GEN, MSGS_BLEND_GRANULARITY, MSGS_NO_OCCLUSION) and MSGS_BLOCKING_SYNC — how the
+ *     host learns the instance count; none changes a result.
  *     The A/B switches of rounds 1-5 (sort / scan / emit / forward-list variants, MSGS_DEPTH_SORT_BEGIN_BIT) are gone from the
  *     product together with the code paths they selected;
  *   - one 64-byte pinned status block per calling host thread for the calls that WAIT for the instance count
@@ -443,8 +443,9 @@ int msgs_slab_stats(const void* geom, size_t geom_bytes, int32_t P, int64_t* out
  * poll of pinned host words): the GPU never idles while the host learns D.  D <= capacity (the normal case): *stage2_done = 1.
  * Otherwise (first frame of a shape, or the scene outgrew the margin) *stage2_done = 0 and *num_instances_host = D: grow the
  * buffers and call msgs_forward_stage2, which overwrites the truncated result (same stream).  The binning buffer's internal
- * layout depends neither on D nor on the capacity (tile ranges first).  view->debug, the look-back sort variants and
- * MSGS_NO_SPECULATIVE_STAGE2=1 take the sequential route (wait for D, then launch stage 2 if the buffers suffice). */
+ * layout depends neither on D nor on the capacity (tile ranges first).  view->debug, an empty view, buffers below 4096
+ * instances and the look-back sort variants take the sequential route (wait for D, then launch stage 2 if the buffers
+ * suffice). */
 int msgs_forward(const msgs_view_t* view, const msgs_gaussians_t* gaussians, int32_t* radii, float* pixel_sizes,
                  void* geom, size_t geom_bytes, void* scratch1, size_t scratch1_bytes, void* binning,
                  size_t binning_bytes, void* scratch2, size_t scratch2_bytes, void* image, size_t image_bytes,

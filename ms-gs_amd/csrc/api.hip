@@ -123,6 +123,16 @@ int msgs_set_occlusion(int32_t on) { return set_occlusion(on); }
 }  // extern "C"
 
 namespace {
+// The caller's stage-2 buffers and outputs: the arguments of msgs_forward_stage2 behind D, as every forward entry point takes them
+struct Stage2Buffers {
+    void* binning; size_t binning_bytes;
+    void* scratch2; size_t scratch2_bytes;
+    void* image; size_t image_bytes;
+    float* out_color; float* out_acc_ps; float* out_depth;
+    void* grad_records; size_t grad_records_bytes;
+    int backward_follows;
+};
+
 // Speculative stage 2 (msgs_forward): everything stage 2 needs, handed to stage 1 so that it can launch stage 2 on the caller's
 // capacity-sized buffers right behind its own last kernel — BEFORE the host waits for the instance count.  The stage-2 kernels then
 // read min(D, capacity) from a device word the scan writes; the host checks D <= capacity afterwards (and the caller redoes
@@ -130,19 +140,12 @@ namespace {
 // the emit while the host learned D and launched (profiles/r3_idle.txt).
 struct SpecStage2 {
     int64_t capacity;
-    void* binning; size_t binning_bytes;
-    void* scratch2; size_t scratch2_bytes;
-    void* image; size_t image_bytes;
-    float* out_color; float* out_acc_ps; float* out_depth;
-    void* grad_records; size_t grad_records_bytes;
-    int backward_follows;
+    Stage2Buffers buf;
     int launched_rc;           // out: status of the speculative launch
 };
 int forward_stage2_impl(const msgs_view_t* view, const msgs_gaussians_t* g, const void* geom_v, size_t geom_bytes, int64_t D,
-                        void* binning_v, size_t binning_bytes, void* scratch_v, size_t scratch_bytes, void* image_v,
-                        size_t image_bytes, float* out_color, float* out_acc_ps, float* out_depth, void* grad_records,
-                        size_t grad_records_bytes, int backward_follows, const msgs_timing_t* timing, void* stream,
-                        const uint32_t* D_dev, uint64_t* fb_dev, uint64_t fb_ticket);
+                        const Stage2Buffers& b, const msgs_timing_t* timing, void* stream, const uint32_t* D_dev,
+                        uint64_t* fb_dev, uint64_t fb_ticket);
 
 // The instance count D comes back through three pinned, device-mapped host words {D, flags, ticket} that a kernel writes
 // itself and the host polls: no copy command, no interrupt-driven wait (a blocking hipStreamSynchronize wakes up tens of
@@ -254,7 +257,7 @@ int forward_stage1_launch(const msgs_view_t* view, const msgs_gaussians_t* g, in
     uint64_t* status_dev = total_dev + 2;
     uint32_t* clamped_dev = (uint32_t*)(total_dev + 5);       // min(D, capacity) for a speculative stage 2
     // the speculative stage 2's queue of heavy Gaussians starts empty (binning.hip): cleared by whoever publishes the count
-    uint32_t* heavy_q_word = spec ? (uint32_t*)((char*)spec->scratch2 + Stage2Scratch(spec->capacity).heavy_q) : nullptr;
+    uint32_t* heavy_q_word = spec ? (uint32_t*)((char*)spec->buf.scratch2 + Stage2Scratch(spec->capacity).heavy_q) : nullptr;
 
     tm.begin(MSGS_K_DEPTH_SORT);
     HIP_TRY(radix_sort_pairs((uint32_t*)(geom + GL.key), nullptr, (uint32_t*)(geom + GL.skey),
@@ -281,11 +284,8 @@ int forward_stage1_launch(const msgs_view_t* view, const msgs_gaussians_t* g, in
     pend.host = sb.host;
     pend.status_dev = status_dev;
     if (spec)       // stage 2 goes out NOW, sized for the capacity; the GPU runs it while the host waits for D
-        spec->launched_rc = forward_stage2_impl(view, g, geom_v, geom_bytes, spec->capacity, spec->binning, spec->binning_bytes,
-                                                spec->scratch2, spec->scratch2_bytes, spec->image, spec->image_bytes,
-                                                spec->out_color, spec->out_acc_ps, spec->out_depth, spec->grad_records,
-                                                spec->grad_records_bytes, spec->backward_follows, timing, stream, clamped_dev,
-                                                polled ? sb.dev : nullptr, ticket);
+        spec->launched_rc = forward_stage2_impl(view, g, geom_v, geom_bytes, spec->capacity, spec->buf, timing, stream,
+                                                clamped_dev, polled ? sb.dev : nullptr, ticket);
     return MSGS_OK;
 }
 
@@ -337,18 +337,6 @@ StatusBlock& thread_status_block() {
     return sb;
 }
 
-int forward_stage1_impl(const msgs_view_t* view, const msgs_gaussians_t* g, int32_t* radii, float* pixel_sizes,
-                        void* geom_v, size_t geom_bytes, void* scratch_v, size_t scratch_bytes,
-                        int64_t* num_instances_host, const msgs_timing_t* timing, void* stream, SpecStage2* spec) {
-    if (!num_instances_host) return MSGS_ERR_INVALID_ARG;
-    *num_instances_host = 0;
-    PendingCount pend;
-    int rc = forward_stage1_launch(view, g, radii, pixel_sizes, geom_v, geom_bytes, scratch_v, scratch_bytes, timing, stream,
-                                   spec, thread_status_block(), pend);
-    if (rc) return rc;
-    return forward_stage1_wait(pend, num_instances_host);
-}
-
 // largest D with bytes_of(D) <= bytes (bytes_of monotone); 0 if none
 template <class F>
 static int64_t max_instances_for(size_t bytes, F bytes_of) {
@@ -361,37 +349,22 @@ static int64_t max_instances_for(size_t bytes, F bytes_of) {
     return lo;
 }
 
-}  // namespace
-
-extern "C" {
-
-int msgs_forward_stage1(const msgs_view_t* view, const msgs_gaussians_t* g, int32_t* radii, float* pixel_sizes,
-                        void* geom_v, size_t geom_bytes, void* scratch_v, size_t scratch_bytes,
-                        int64_t* num_instances_host, const msgs_timing_t* timing, void* stream) {
-    return forward_stage1_impl(view, g, radii, pixel_sizes, geom_v, geom_bytes, scratch_v, scratch_bytes, num_instances_host,
-                               timing, stream, nullptr);
-}
-
 // instance capacities of the caller's stage-2 buffers: ids of `binning`, and what the scratch serves
-static void stage2_capacities(const msgs_view_t* view, size_t binning_bytes, size_t scratch2_bytes, int64_t& cb, int64_t& cs) {
+void stage2_capacities(const msgs_view_t* view, size_t binning_bytes, size_t scratch2_bytes, int64_t& cb, int64_t& cs) {
     const int W0 = view->image_width, H0 = view->image_height;
     cb = max_instances_for(binning_bytes, [&](int64_t d) { return msgs_binning_bytes(d, W0, H0); });
     cs = max_instances_for(scratch2_bytes, [&](int64_t d) { return msgs_stage2_scratch_bytes(d, W0, H0); });
 }
 
 // speculative stage 2 on the caller's buffers: possible when they hold at least 4096 instances, the view is not in debug
-// mode and the sort geometry can take its count from a device word (MSGS_NO_SPECULATIVE_STAGE2=1: never)
-static bool prepare_spec(const msgs_view_t* view, const msgs_gaussians_t* g, void* binning, size_t binning_bytes, void* scratch2,
-                         size_t scratch2_bytes, void* image, size_t image_bytes, float* out_color, float* out_acc_ps,
-                         float* out_depth, void* grad_records, size_t grad_records_bytes, int backward_follows,
-                         SpecStage2& spec) {
-    static const bool no_spec = [] { const char* e = getenv("MSGS_NO_SPECULATIVE_STAGE2"); return e && e[0] == '1'; }();
-    if (no_spec || view->debug || g->P <= 0 || !binning || !scratch2 || !image || !out_color || !out_acc_ps || !out_depth ||
+// mode and the sort geometry can take its count from a device word
+bool prepare_spec(const msgs_view_t* view, const msgs_gaussians_t* g, const Stage2Buffers& b, SpecStage2& spec) {
+    if (view->debug || g->P <= 0 || !b.binning || !b.scratch2 || !b.image || !b.out_color || !b.out_acc_ps || !b.out_depth ||
         view->image_width <= 0 || view->image_height <= 0)
         return false;
     const int W0 = view->image_width, H0 = view->image_height;
     int64_t cb, cs;
-    stage2_capacities(view, binning_bytes, scratch2_bytes, cb, cs);
+    stage2_capacities(view, b.binning_bytes, b.scratch2_bytes, cb, cs);
     int64_t cap = cb < cs ? cb : cs;
     const int tiles0 = ((W0 + TILE - 1) / TILE) * ((H0 + TILE - 1) / TILE);
     if (slab_wanted(view, g)) {          // in slab mode the buffers serve fewer instances: slab A's ids sit in front of slab B's
@@ -400,29 +373,80 @@ static bool prepare_spec(const msgs_view_t* view, const msgs_gaussians_t* g, voi
     }
     if (cap < 4096 || !radix_sort_supports_device_count(cap, 0, tile_bits(tiles0))) return false;
     spec.capacity = cap;
-    spec.binning = binning; spec.binning_bytes = binning_bytes;
-    spec.scratch2 = scratch2; spec.scratch2_bytes = scratch2_bytes;
-    spec.image = image; spec.image_bytes = image_bytes;
-    spec.out_color = out_color; spec.out_acc_ps = out_acc_ps; spec.out_depth = out_depth;
-    spec.grad_records = grad_records; spec.grad_records_bytes = grad_records_bytes;
-    spec.backward_follows = backward_follows;
+    spec.buf = b;
     spec.launched_rc = MSGS_OK;
     return true;
 }
 
-}  // extern "C"
+// A forward whose stage 1 is enqueued (with stage 2 behind it, if the buffers allowed) and whose count is not collected yet
+struct ForwardLaunch {
+    PendingCount pend;
+    bool spec = false;           // stage 2 went out speculatively ...
+    int64_t capacity = 0;        // ... for at most this many instances ...
+    int launched_rc = MSGS_OK;   // ... and its launch returned this
+};
+
+// The launch step of msgs_forward, msgs_forward_stage1 and msgs_forward_launch: stage 1, and stage 2 speculatively behind it
+// when `b` (nullable) allows.  Nothing is waited for.
+int forward_launch(const msgs_view_t* view, const msgs_gaussians_t* g, int32_t* radii, float* pixel_sizes, void* geom,
+                   size_t geom_bytes, void* scratch1, size_t scratch1_bytes, const Stage2Buffers* b,
+                   const msgs_timing_t* timing, void* stream, StatusBlock& sb, ForwardLaunch& fl) {
+    SpecStage2 spec{};
+    fl.spec = b && prepare_spec(view, g, *b, spec);
+    const int rc = forward_stage1_launch(view, g, radii, pixel_sizes, geom, geom_bytes, scratch1, scratch1_bytes, timing,
+                                         stream, fl.spec ? &spec : nullptr, sb, fl.pend);
+    if (rc) return rc;
+    fl.capacity = spec.capacity;
+    fl.launched_rc = spec.launched_rc;
+    return MSGS_OK;
+}
+
+// The finish step: waits for the count; *stage2_done = 1 when the speculative stage 2 served it (D <= its capacity)
+int forward_finish(ForwardLaunch& fl, int64_t* num_instances_host, int32_t* stage2_done) {
+    *stage2_done = 0;
+    const int rc = forward_stage1_wait(fl.pend, num_instances_host);
+    if (rc) return rc;
+    if (fl.spec && fl.launched_rc != MSGS_OK) return fl.launched_rc;
+    *stage2_done = fl.spec && *num_instances_host <= fl.capacity;
+    return MSGS_OK;
+}
+
+// stage 2 on buffers that serve D: msgs_forward_stage2, and msgs_forward's sequential route
+int forward_stage2_exact(const msgs_view_t* view, const msgs_gaussians_t* g, const void* geom, size_t geom_bytes, int64_t D,
+                         const Stage2Buffers& b, const msgs_timing_t* timing, void* stream) {
+    uint64_t* fb_dev = nullptr;
+    uint64_t fb_ticket = 0;
+    if (view && view->feedback_tag != 0 && !blocking_sync()) {        // feedback goes to the calling thread's status block
+        StatusBlock& sb = thread_status_block();
+        sb.ensure();
+        fb_dev = sb.dev;
+        fb_ticket = sb.ticket;
+    }
+    return forward_stage2_impl(view, g, geom, geom_bytes, D, b, timing, stream, nullptr, fb_dev, fb_ticket);
+}
+
+}  // namespace
 
 // the handle of msgs_forward_launch / msgs_forward_finish: its own pinned status block + the launch it is waiting for
 struct msgs_status {
     StatusBlock sb;
-    PendingCount pend;
+    ForwardLaunch fl;
     bool launched = false;       // a msgs_forward_launch has not been finished yet
-    bool stage2_launched = false;
-    int64_t capacity = 0;
-    int launched_rc = MSGS_OK;
 };
 
 extern "C" {
+
+int msgs_forward_stage1(const msgs_view_t* view, const msgs_gaussians_t* g, int32_t* radii, float* pixel_sizes,
+                        void* geom_v, size_t geom_bytes, void* scratch_v, size_t scratch_bytes,
+                        int64_t* num_instances_host, const msgs_timing_t* timing, void* stream) {
+    if (!num_instances_host) return MSGS_ERR_INVALID_ARG;
+    *num_instances_host = 0;
+    ForwardLaunch fl;
+    int32_t stage2_done;
+    const int rc = forward_launch(view, g, radii, pixel_sizes, geom_v, geom_bytes, scratch_v, scratch_bytes, nullptr, timing,
+                                  stream, thread_status_block(), fl);
+    return rc ? rc : forward_finish(fl, num_instances_host, &stage2_done);
+}
 
 int msgs_status_create(msgs_status_t** out) {
     if (!out) return MSGS_ERR_INVALID_ARG;
@@ -434,7 +458,7 @@ int msgs_status_create(msgs_status_t** out) {
 
 int msgs_status_destroy(msgs_status_t* st) {
     if (!st) return MSGS_OK;
-    if (st->launched && st->pend.active) (void)hipStreamSynchronize(st->pend.stream);   // a kernel may still write the block
+    if (st->launched && st->fl.pend.active) (void)hipStreamSynchronize(st->fl.pend.stream);   // a kernel may still write the block
     st->sb.release();
     delete st;
     return MSGS_OK;
@@ -447,16 +471,12 @@ int msgs_forward_launch(const msgs_view_t* view, const msgs_gaussians_t* g, int3
                         int32_t backward_follows, msgs_status_t* status, const msgs_timing_t* timing, void* stream) {
     if (!view || !g || !status) return MSGS_ERR_INVALID_ARG;
     if (status->launched) return MSGS_ERR_INVALID_ARG;          // one launch per handle at a time
-    SpecStage2 spec{};
-    const bool use_spec = prepare_spec(view, g, binning, binning_bytes, scratch2, scratch2_bytes, image, image_bytes, out_color,
-                                       out_acc_ps, out_depth, grad_records, grad_records_bytes, backward_follows, spec);
-    int rc = forward_stage1_launch(view, g, radii, pixel_sizes, geom, geom_bytes, scratch1, scratch1_bytes, timing, stream,
-                                   use_spec ? &spec : nullptr, status->sb, status->pend);
+    const Stage2Buffers b{binning, binning_bytes, scratch2, scratch2_bytes, image, image_bytes, out_color, out_acc_ps, out_depth,
+                          grad_records, grad_records_bytes, backward_follows};
+    const int rc = forward_launch(view, g, radii, pixel_sizes, geom, geom_bytes, scratch1, scratch1_bytes, &b, timing, stream,
+                                  status->sb, status->fl);
     if (rc) return rc;
     status->launched = true;
-    status->stage2_launched = use_spec;
-    status->capacity = spec.capacity;
-    status->launched_rc = status->stage2_launched ? spec.launched_rc : MSGS_OK;
     return MSGS_OK;
 }
 
@@ -466,11 +486,7 @@ int msgs_forward_finish(msgs_status_t* status, int64_t* num_instances_host, int3
     *num_instances_host = 0;
     if (!status->launched) return MSGS_ERR_INVALID_ARG;
     status->launched = false;
-    int rc = forward_stage1_wait(status->pend, num_instances_host);
-    if (rc) return rc;
-    if (status->stage2_launched && status->launched_rc != MSGS_OK) return status->launched_rc;
-    if (status->stage2_launched && *num_instances_host <= status->capacity) *stage2_done = 1;
-    return MSGS_OK;
+    return forward_finish(status->fl, num_instances_host, stage2_done);
 }
 
 int msgs_forward(const msgs_view_t* view, const msgs_gaussians_t* g, int32_t* radii, float* pixel_sizes, void* geom,
@@ -481,27 +497,23 @@ int msgs_forward(const msgs_view_t* view, const msgs_gaussians_t* g, int32_t* ra
                  void* stream) {
     if (!stage2_done) return MSGS_ERR_INVALID_ARG;
     *stage2_done = 0;
-    if (!view || !g) return MSGS_ERR_INVALID_ARG;
-    SpecStage2 spec{};
-    bool use_spec = prepare_spec(view, g, binning, binning_bytes, scratch2, scratch2_bytes, image, image_bytes, out_color,
-                                 out_acc_ps, out_depth, grad_records, grad_records_bytes, backward_follows, spec);
-    int rc = forward_stage1_impl(view, g, radii, pixel_sizes, geom, geom_bytes, scratch1, scratch1_bytes, num_instances_host,
-                                 timing, stream, use_spec ? &spec : nullptr);
-    if (rc) return rc;
+    if (!view || !g || !num_instances_host) return MSGS_ERR_INVALID_ARG;
+    *num_instances_host = 0;
+    const Stage2Buffers b{binning, binning_bytes, scratch2, scratch2_bytes, image, image_bytes, out_color, out_acc_ps, out_depth,
+                          grad_records, grad_records_bytes, backward_follows};
+    ForwardLaunch fl;
+    int rc = forward_launch(view, g, radii, pixel_sizes, geom, geom_bytes, scratch1, scratch1_bytes, &b, timing, stream,
+                            thread_status_block(), fl);
+    if (!rc) rc = forward_finish(fl, num_instances_host, stage2_done);
+    // a speculative stage 2 ran (is running) on these buffers, or ran truncated: then the caller redoes it on exact buffers
+    if (rc || fl.spec) return rc;
+    // the sequential route (no speculative launch: debug mode, no P, buffers below 4096 instances): stage 2 now, if the
+    // buffers serve D
     const int64_t D = *num_instances_host;
     const int W = view->image_width, H = view->image_height;
-    if (use_spec && spec.launched_rc != MSGS_OK) return spec.launched_rc;
-    if (use_spec && D <= spec.capacity) {       // the normal case: stage 2 already ran (is running) on these buffers
-        *stage2_done = 1;
-        return MSGS_OK;
-    }
-    if (use_spec) return MSGS_OK;               // the scene outgrew the guess: the caller redoes stage 2 on exact buffers
     if (!binning || binning_bytes < msgs_binning_bytes(D, W, H)) return MSGS_OK;
     if (D > 0 && (!scratch2 || scratch2_bytes < msgs_stage2_scratch_bytes(D, W, H))) return MSGS_OK;
-    rc = msgs_forward_stage2(view, g, geom, geom_bytes, D, binning, binning_bytes, scratch2, scratch2_bytes, image,
-                             image_bytes, out_color, out_acc_ps, out_depth, grad_records, grad_records_bytes, backward_follows,
-                             timing, stream);
-    if (rc) return rc;
+    if ((rc = forward_stage2_exact(view, g, geom, geom_bytes, D, b, timing, stream))) return rc;
     *stage2_done = 1;
     return MSGS_OK;
 }
@@ -524,17 +536,9 @@ int msgs_forward_stage2(const msgs_view_t* view, const msgs_gaussians_t* g, cons
                         void* image_v, size_t image_bytes, float* out_color, float* out_acc_ps, float* out_depth,
                         void* grad_records, size_t grad_records_bytes, int32_t backward_follows, const msgs_timing_t* timing,
                         void* stream) {
-    uint64_t* fb_dev = nullptr;
-    uint64_t fb_ticket = 0;
-    if (view && view->feedback_tag != 0 && !blocking_sync()) {        // feedback goes to the calling thread's status block
-        StatusBlock& sb = thread_status_block();
-        sb.ensure();
-        fb_dev = sb.dev;
-        fb_ticket = sb.ticket;
-    }
-    return forward_stage2_impl(view, g, geom_v, geom_bytes, D, binning_v, binning_bytes, scratch_v, scratch_bytes, image_v,
-                               image_bytes, out_color, out_acc_ps, out_depth, grad_records, grad_records_bytes, backward_follows,
-                               timing, stream, nullptr, fb_dev, fb_ticket);
+    const Stage2Buffers b{binning_v, binning_bytes, scratch_v, scratch_bytes, image_v, image_bytes, out_color, out_acc_ps,
+                          out_depth, grad_records, grad_records_bytes, backward_follows};
+    return forward_stage2_exact(view, g, geom_v, geom_bytes, D, b, timing, stream);
 }
 
 }  // extern "C"
@@ -544,24 +548,22 @@ namespace {
 // min(D_true, capacity) from *D_dev.
 // fb_dev / fb_ticket: pinned status block (device address) for the feedback publication, msgs_view_t.feedback_tag.
 int forward_stage2_impl(const msgs_view_t* view, const msgs_gaussians_t* g, const void* geom_v, size_t geom_bytes, int64_t D,
-                        void* binning_v, size_t binning_bytes, void* scratch_v, size_t scratch_bytes, void* image_v,
-                        size_t image_bytes, float* out_color, float* out_acc_ps, float* out_depth, void* grad_records,
-                        size_t grad_records_bytes, int backward_follows, const msgs_timing_t* timing, void* stream,
-                        const uint32_t* D_dev, uint64_t* fb_dev, uint64_t fb_ticket) {
+                        const Stage2Buffers& b, const msgs_timing_t* timing, void* stream, const uint32_t* D_dev,
+                        uint64_t* fb_dev, uint64_t fb_ticket) {
     int rc = check_inputs(view, g);
     if (rc) return rc;
     if (D < 0 || D > 0xFFFFFFFFll) return MSGS_ERR_TOO_MANY;
     const int P = g->P, W = view->image_width, H = view->image_height;
-    if (!binning_v || !image_v || !out_color || !out_acc_ps || !out_depth) return MSGS_ERR_INVALID_ARG;
+    if (!b.binning || !b.image || !b.out_color || !b.out_acc_ps || !b.out_depth) return MSGS_ERR_INVALID_ARG;
     if (P > 0 && (!geom_v || geom_bytes < msgs_geom_bytes(P))) return MSGS_ERR_CAPACITY;
-    if (binning_bytes < msgs_binning_bytes(D, W, H) || image_bytes < msgs_image_bytes(W, H)) return MSGS_ERR_CAPACITY;
-    if (D > 0 && (!scratch_v || scratch_bytes < msgs_stage2_scratch_bytes(D, W, H))) return MSGS_ERR_CAPACITY;
-    if (grad_records && grad_records_bytes < msgs_backward_scratch_bytes(P)) return MSGS_ERR_CAPACITY;
+    if (b.binning_bytes < msgs_binning_bytes(D, W, H) || b.image_bytes < msgs_image_bytes(W, H)) return MSGS_ERR_CAPACITY;
+    if (D > 0 && (!b.scratch2 || b.scratch2_bytes < msgs_stage2_scratch_bytes(D, W, H))) return MSGS_ERR_CAPACITY;
+    if (b.grad_records && b.grad_records_bytes < msgs_backward_scratch_bytes(P)) return MSGS_ERR_CAPACITY;
     hipStream_t s = (hipStream_t)stream;
     char* geom = const_cast<char*>((const char*)geom_v);        // (slab mode writes its header and second scan into geom)
-    char* binning = (char*)binning_v;
-    char* scratch = (char*)scratch_v;
-    char* image = (char*)image_v;
+    char* binning = (char*)b.binning;
+    char* scratch = (char*)b.scratch2;
+    char* image = (char*)b.image;
     const ViewParams vp = make_view_params(view);
     const int num_tiles = vp.gx * vp.gy;
     const ImageLayout IL(W, H);
@@ -577,64 +579,80 @@ int forward_stage2_impl(const msgs_view_t* view, const msgs_gaussians_t* g, cons
     const bool literal = g_deterministic.load() != 0;
     const bool feedback = view->feedback_tag != 0 && fb_dev != nullptr && P > 0 && forward_uses_quadrant_kernel(num_tiles) && !literal;
     unsigned long long* dtrav = feedback ? (unsigned long long*)(binning + BL.dtrav) : nullptr;
-    const size_t clear_bytes = grad_records ? GRAD_REC_BYTES * (size_t)P : 0;
+    const size_t clear_bytes = b.grad_records ? GRAD_REC_BYTES * (size_t)P : 0;
 
     // ---- depth slabs?  The buffers must serve this D in slab mode (SlabGeom); the speculative caller sized `D` accordingly
     bool slab = D > 0 && slab_wanted(view, g) && radix_sort_supports_device_count(D, 0, tbits);
     int64_t n_a_max = 0, cap_b = 0;
     if (slab) {
         int64_t cb, cs;
-        stage2_capacities(view, binning_bytes, scratch_bytes, cb, cs);
+        stage2_capacities(view, b.binning_bytes, b.scratch2_bytes, cb, cs);
         const SlabGeom SG(cb, cs, (double)view->slab_fraction, num_tiles, D);
         slab = SG.ok && SG.cap_d == D && SortScratch(SG.n_a_max).total <= SortScratch(SG.cap_b).total;
         n_a_max = SG.n_a_max;
         cap_b = SG.cap_b;
     }
 
-    if (!slab) {
-        const Stage2Scratch SL(D);
-        uint32_t* keys_sorted = D > 0 ? (uint32_t*)(scratch + SL.total) : nullptr;
-        bool ranges_prezeroed = false, keys16 = false;
-        if (D > 0) {
-            uint32_t* keys_a = (uint32_t*)(scratch + SL.keys_a);
-            uint32_t* ids_a = (uint32_t*)(scratch + SL.ids_a);
-            // emit also clears the tile sort's group-sum table and the tile-range array (two fill launches less)
-            ZeroJob zj2{nullptr, 0, (uint32_t*)ranges, BL.ranges_and_dtrav_words()};
-            const bool sort2_prezeroed = radix_sort_zero_region(D, 0, tbits, scratch + SL.sort, &zj2.p0, &zj2.n0);
-            ranges_prezeroed = true;
-            // tile ids (and the sentinel id = number of tiles) below 65536: the emit writes, the tile sort moves and the range
-            // search reads 16-bit keys — 6 instead of 8 bytes per pair and pass
-            keys16 = num_tiles < 65535 && radix_sort_keys16_ok(D, 0, tbits);
-            // the queue of heavy Gaussians (binning.hip: one more launch) — not on a view the caller marked as ordinary
-            // (msgs_view_t.no_heavy_queue: no covers closed anything lately, hence no crowd of giants in the first ranks either;
-            // the few Gaussians with many instances are then emitted by their wave inside emit_kernel, as before round 5)
-            uint32_t* heavy_q = view->no_heavy_queue ? nullptr : (uint32_t*)(scratch + SL.heavy_q);
-            if (heavy_q && !D_dev) HIP_TRY(launch_zero(heavy_q, 4, s));     // (a speculative launch had it cleared by stage 1's scan)
-            tm.begin(MSGS_K_EMIT);
-            HIP_TRY(launch_emit(vp, P, geom, keys_a, ids_a, D, s, zj2, D_dev, keys16, heavy_q));
-            tm.end(MSGS_K_EMIT);
+    // the scratch is laid out for the single pass's D, or for slab B's capacity (slab A uses its head)
+    const Stage2Scratch SL(slab ? cap_b : D);
+    uint32_t *keys_a = nullptr, *ids_a = nullptr, *keys_sorted = nullptr, *heavy_q = nullptr;
+    bool keys16 = false;
+    if (D > 0) {
+        keys_a = (uint32_t*)(scratch + SL.keys_a);
+        ids_a = (uint32_t*)(scratch + SL.ids_a);
+        keys_sorted = (uint32_t*)(scratch + SL.total);
+        // the queue of heavy Gaussians (binning.hip: one more launch) — not on a view the caller marked as ordinary
+        // (msgs_view_t.no_heavy_queue: no covers closed anything lately, hence no crowd of giants in the first ranks either;
+        // the few Gaussians with many instances are then emitted by their wave inside emit_kernel, as before round 5)
+        heavy_q = view->no_heavy_queue ? nullptr : (uint32_t*)(scratch + SL.heavy_q);
+        // tile ids (and the sentinel id = number of tiles) below 65536: the emit writes, the tile sort moves and the range
+        // search reads 16-bit keys — 6 instead of 8 bytes per pair and pass
+        keys16 = num_tiles < 65535 && radix_sort_keys16_ok(slab ? cap_b : D, 0, tbits) &&
+                 (!slab || radix_sort_keys16_ok(n_a_max, 0, tbits));
+    }
+
+    // One binning pass: emit -> tile sort -> ranges of at most `cap` instances, their number read from *count (nullptr: exactly
+    // `cap`); the sorted ids go to ids + base.  The emit also clears the tile sort's group-sum table and, with clear_ranges,
+    // the tile-range array (fill launches less).  `t` closes the emit's span, which the caller opens, and times the tile sort
+    // and the ranges.  cap == 0: no emit, no sort, only the ranges.
+    auto bin_pass = [&](const uint32_t* count, int64_t cap, uint32_t base, int slab_pass, const uint32_t* open,
+                        bool clear_ranges, bool ranges_prezeroed, int64_t density_D, const Timer& t) -> int {
+        if (cap > 0) {
+            ZeroJob zj{nullptr, 0, clear_ranges ? (uint32_t*)ranges : nullptr, clear_ranges ? BL.ranges_and_dtrav_words() : 0};
+            const bool sort_prezeroed = radix_sort_zero_region(cap, 0, tbits, scratch + SL.sort, &zj.p0, &zj.n0);
+            HIP_TRY(launch_emit(vp, P, geom, keys_a, ids_a, cap, s, zj, count, keys16, heavy_q, slab_pass, open, density_D));
+            t.end(MSGS_K_EMIT);
             if ((rc = debug_sync(view, s))) return rc;
-            tm.begin(MSGS_K_TILE_SORT);
-            HIP_TRY(radix_sort_pairs(keys_a, ids_a, keys_sorted, ids, D, 0, tbits, scratch + SL.sort, s, sort2_prezeroed, nullptr,
-                                     D_dev, keys16));
-            tm.end(MSGS_K_TILE_SORT);
+            t.begin(MSGS_K_TILE_SORT);
+            HIP_TRY(radix_sort_pairs(keys_a, ids_a, keys_sorted, ids + base, cap, 0, tbits, scratch + SL.sort, s, sort_prezeroed,
+                                     nullptr, count, keys16));
+            t.end(MSGS_K_TILE_SORT);
             if ((rc = debug_sync(view, s))) return rc;
         }
-        tm.begin(MSGS_K_RANGES);
-        HIP_TRY(launch_ranges(keys_sorted, D, ranges, num_tiles, s, ranges_prezeroed, D_dev, keys16));
-        tm.end(MSGS_K_RANGES);
+        t.begin(MSGS_K_RANGES);
+        HIP_TRY(launch_ranges(keys_sorted, cap, ranges, num_tiles, s, ranges_prezeroed, count, keys16, base));
+        t.end(MSGS_K_RANGES);
+        return MSGS_OK;
+    };
+
+    if (!slab) {
+        if (D > 0) {
+            if (heavy_q && !D_dev) HIP_TRY(launch_zero(heavy_q, 4, s));     // (a speculative launch had it cleared by stage 1's scan)
+            tm.begin(MSGS_K_EMIT);
+        }
+        if ((rc = bin_pass(D_dev, D, 0, 0, nullptr, /*clear_ranges*/ true, /*ranges_prezeroed*/ D > 0, 0, tm))) return rc;
         if ((rc = debug_sync(view, s))) return rc;
 
         tm.begin(MSGS_K_BLEND_FWD);
         if (literal) {          // verification mode: the reference's per-pixel loop restated literally (literal.hip)
-            if (grad_records && clear_bytes) HIP_TRY(launch_zero(grad_records, clear_bytes, s));
-            HIP_TRY(launch_blend_forward_literal(vp, geom, P, ids, ranges, out_color, out_acc_ps, out_depth, final_T, n_contrib,
-                                                 (uint32_t*)(image + IL.tile_order) + num_tiles, s));
+            if (b.grad_records && clear_bytes) HIP_TRY(launch_zero(b.grad_records, clear_bytes, s));
+            HIP_TRY(launch_blend_forward_literal(vp, geom, P, ids, ranges, b.out_color, b.out_acc_ps, b.out_depth, final_T,
+                                                 n_contrib, (uint32_t*)(image + IL.tile_order) + num_tiles, s));
         } else {
             if (D == 0 && dtrav) HIP_TRY(launch_zero(dtrav, 8 * (size_t)DTRAV_SLOTS, s));      // (no emit ran: nobody cleared them)
             const FwdSlabArgs fa{0, nullptr, nullptr, nullptr, dtrav};
-            HIP_TRY(launch_blend_forward(vp, geom, ids, ranges, out_color, out_acc_ps, out_depth, final_T, n_contrib, tile_last,
-                                         grad_records, clear_bytes, s, dtrav ? &fa : nullptr));
+            HIP_TRY(launch_blend_forward(vp, geom, ids, ranges, b.out_color, b.out_acc_ps, b.out_depth, final_T, n_contrib,
+                                         tile_last, b.grad_records, clear_bytes, s, dtrav ? &fa : nullptr));
         }
     } else {
         // ---------------- slab A: the nearest ranks, up to slab_fraction * D instances ----------------
@@ -642,33 +660,15 @@ int forward_stage2_impl(const msgs_view_t* view, const msgs_gaussians_t* g, cons
         SlabHeader* hdr = reinterpret_cast<SlabHeader*>(geom + GL.slab_hdr);
         uint32_t* open_bits = (uint32_t*)(image + IL.open_bits);
         uint32_t* open_list = (uint32_t*)(image + IL.open_list);
-        const Stage2Scratch SL(cap_b);                       // the scratch is laid out for slab B's capacity; A uses its head
-        uint32_t* keys_a = (uint32_t*)(scratch + SL.keys_a);
-        uint32_t* ids_a = (uint32_t*)(scratch + SL.ids_a);
-        uint32_t* keys_sorted = (uint32_t*)(scratch + SL.total);
-        uint32_t* heavy_q = view->no_heavy_queue ? nullptr : (uint32_t*)(scratch + SL.heavy_q);
-        const bool keys16 = num_tiles < 65535 && radix_sort_keys16_ok(n_a_max, 0, tbits) && radix_sort_keys16_ok(cap_b, 0, tbits);
         tm.begin(MSGS_K_EMIT);
         HIP_TRY(launch_slab_split(P, geom, D, D_dev, view->slab_fraction, open_bits, num_tiles, s));
         if (heavy_q) HIP_TRY(launch_zero(heavy_q, 4, s));
-        ZeroJob zjA{nullptr, 0, (uint32_t*)ranges, BL.ranges_and_dtrav_words()};
-        const bool sortA_prezeroed = radix_sort_zero_region(n_a_max, 0, tbits, scratch + SL.sort, &zjA.p0, &zjA.n0);
-        HIP_TRY(launch_emit(vp, P, geom, keys_a, ids_a, n_a_max, s, zjA, &hdr->DA, keys16, heavy_q, 1, nullptr, D));
-        tm.end(MSGS_K_EMIT);
-        if ((rc = debug_sync(view, s))) return rc;
-        tm.begin(MSGS_K_TILE_SORT);
-        HIP_TRY(radix_sort_pairs(keys_a, ids_a, keys_sorted, ids, n_a_max, 0, tbits, scratch + SL.sort, s, sortA_prezeroed, nullptr,
-                                 &hdr->DA, keys16));
-        tm.end(MSGS_K_TILE_SORT);
-        if ((rc = debug_sync(view, s))) return rc;
-        tm.begin(MSGS_K_RANGES);
-        HIP_TRY(launch_ranges(keys_sorted, n_a_max, ranges, num_tiles, s, true, &hdr->DA, keys16, 0u));
-        tm.end(MSGS_K_RANGES);
+        if ((rc = bin_pass(&hdr->DA, n_a_max, 0, 1, nullptr, /*clear_ranges*/ true, /*ranges_prezeroed*/ true, D, tm))) return rc;
         if ((rc = debug_sync(view, s))) return rc;
         tm.begin(MSGS_K_BLEND_FWD);
         const FwdSlabArgs fa{1, open_bits, open_list, &hdr->n_open, dtrav};
-        HIP_TRY(launch_blend_forward(vp, geom, ids, ranges, out_color, out_acc_ps, out_depth, final_T, n_contrib, tile_last,
-                                     grad_records, clear_bytes, s, &fa));
+        HIP_TRY(launch_blend_forward(vp, geom, ids, ranges, b.out_color, b.out_acc_ps, b.out_depth, final_T, n_contrib, tile_last,
+                                     b.grad_records, clear_bytes, s, &fa));
         tm.end(MSGS_K_BLEND_FWD);
         if ((rc = debug_sync(view, s))) return rc;
 
@@ -682,20 +682,16 @@ int forward_stage2_impl(const msgs_view_t* view, const msgs_gaussians_t* g, cons
         HIP_TRY(exclusive_scan_u32(offs_b, nullptr, offs_b, P, (uint64_t*)(geom + GL.scan_b), &hdr->total_b, s, nullptr, nullptr, 0,
                                    (const uint32_t*)(geom + GL.nvalid), &hdr->DB, (uint64_t)cap_b, nullptr, heavy_q, &hdr->pad0,
                                    0xFFFFFFFFu, nullptr, &hdr->pad[0]));
-        ZeroJob zjB{nullptr, 0, nullptr, 0};
-        const bool sortB_prezeroed = radix_sort_zero_region(cap_b, 0, tbits, scratch + SL.sort, &zjB.p0, &zjB.n0);
-        HIP_TRY(launch_emit(vp, P, geom, keys_a, ids_a, cap_b, s, zjB, &hdr->DB, keys16, heavy_q, 2, open_bits));
-        if ((rc = debug_sync(view, s))) return rc;
-        HIP_TRY(radix_sort_pairs(keys_a, ids_a, keys_sorted, ids + n_a_max, cap_b, 0, tbits, scratch + SL.sort, s, sortB_prezeroed,
-                                 nullptr, &hdr->DB, keys16));
-        if ((rc = debug_sync(view, s))) return rc;
-        HIP_TRY(launch_ranges(keys_sorted, cap_b, ranges, num_tiles, s, true, &hdr->DB, keys16, (uint32_t)n_a_max));
+        // (slab A's emit cleared the ranges; slab B's sub-steps are timed as a whole)
+        if ((rc = bin_pass(&hdr->DB, cap_b, (uint32_t)n_a_max, 2, open_bits, /*clear_ranges*/ false, /*ranges_prezeroed*/ true, 0,
+                           Timer{nullptr, s})))
+            return rc;
         const FwdSlabArgs fb{2, open_bits, open_list, &hdr->n_open, dtrav};
-        HIP_TRY(launch_blend_forward(vp, geom, ids, ranges, out_color, out_acc_ps, out_depth, final_T, n_contrib, tile_last,
+        HIP_TRY(launch_blend_forward(vp, geom, ids, ranges, b.out_color, b.out_acc_ps, b.out_depth, final_T, n_contrib, tile_last,
                                      nullptr, 0, s, &fb));
         tm.end(MSGS_K_SLAB_B);
     }
-    if (backward_follows && !literal)  // give the backward's one-wave-per-tile kernel a heaviest-first launch order
+    if (b.backward_follows && !literal)  // give the backward's one-wave-per-tile kernel a heaviest-first launch order
         HIP_TRY(launch_tile_order(vp, tile_last, (uint32_t*)(image + IL.tile_order), s));
     if (feedback) {
         const GeomLayout GL(P);

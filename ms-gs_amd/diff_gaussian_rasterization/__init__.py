@@ -493,6 +493,15 @@ def _note_info(key):
     _occ_hot[key] = HEAVY_QUEUE_MEMORY if info[1] else max(_occ_hot.get(key, 1) - 1, 0)
 
 
+def _note_count(key, D, guess, done):
+    """after the instance count D of a forward has been collected on this thread; done: its stage 2 needs no redo"""
+    _note_instances(key, D, guess)
+    _note_info(key)
+    forward_stats["forwards"] += 1
+    if not done:
+        forward_stats["non_speculative"] += 1
+
+
 _size_cache = _LRU()
 
 
@@ -517,6 +526,27 @@ def _stage2_bytes(D, W, H, frac):
     if frac > 0.0:
         return int(lib.msgs_binning_bytes_slab(D, W, H, frac)), int(lib.msgs_stage2_scratch_bytes_slab(D, W, H))
     return int(lib.msgs_binning_bytes(D, W, H)), int(lib.msgs_stage2_scratch_bytes(D, W, H))
+
+
+def _redo_stage2(call, geom, image, D, frac, outs, grad_rec, backward_follows, stream):
+    """Stage 2 again, on buffers sized for the instance count D, when the speculative one did not serve it (first frame of this
+    shape, or the scene grew past the margin); returns the new binning buffer.  The outputs are overwritten in place.
+
+    This run reads the geom a truncated speculative stage 2 (capacity < D) may have written to.  What that run left there is
+    rewritten or no longer read as input (tests/test_stage2_routes_gpu.py): the SlabHeader counts, the open-tile bitmap and
+    n_open are reset by slab_split_kernel; the heavy-queue word is cleared before each emit; offs_b / scan_b are recomputed by
+    slab B's recount and scan; and the flag that marks offs_b as stage 1's cell ranges (SlabHeader pad[0]) was cleared by the
+    first run's slab B scan, so this run recounts without the cell prefilter."""
+    color, acc_ps, depth = outs
+    nb_, ns_ = _stage2_bytes(D, call.W, call.H, frac)
+    binning = _bytes(nb_, call.device)
+    scratch2 = _bytes(ns_, call.device)
+    _C.check(_C.lib.msgs_forward_stage2(call.view_ref, call.g_ref, _ptr(geom), geom.numel(), D,
+                                        _ptr(binning), binning.numel(), _ptr(scratch2), scratch2.numel(),
+                                        _ptr(image), image.numel(), _ptr(color), _ptr(acc_ps), _ptr(depth),
+                                        _ptr(grad_rec), grad_rec.numel() if grad_rec is not None else 0,
+                                        int(backward_follows), _C.timer_ptr(), stream), "msgs_forward_stage2")
+    return binning
 
 
 # ---- deferred forwards: several views in flight from one host thread (include/msgs.h msgs_forward_launch / _finish) ----
@@ -590,11 +620,11 @@ class _PendingForward:
                 return self.state
             if self.status is None:                     # an earlier resolve() failed: the view has no result
                 raise RuntimeError("this forward failed when its instance count was collected") from self.error
-            lib, call = _C.lib, self.call
+            call = self.call
             D, done = C.c_int64(0), C.c_int32(0)
             status, self.status = self.status, None
             try:
-                _C.check(lib.msgs_forward_finish(status, C.byref(D), C.byref(done)), "msgs_forward_finish")
+                _C.check(_C.lib.msgs_forward_finish(status, C.byref(D), C.byref(done)), "msgs_forward_finish")
             except Exception as e:
                 self.error = e
                 raise
@@ -602,29 +632,12 @@ class _PendingForward:
                 _give_status(status)
                 self.scratch1 = None
             D = int(D.value)
-            guess = self.guess
-            _note_instances(self.key, D, guess)
-            _note_info(self.key)
-            forward_stats["forwards"] += 1
-            if not done.value:                          # first frame of this shape, or the scene grew past the margin
-                # (the redo runs stage 2 again on the same geom: see _forward_impl for what the truncated run left there)
-                forward_stats["non_speculative"] += 1
-                dev, W, H = call.device, call.W, call.H
-                color, acc_ps, depth = self.outs
+            _note_count(self.key, D, self.guess, done.value)
+            if not done.value:
                 self.error = RuntimeError("stage 2 on exact buffers failed")     # cleared below
-                with _on_device(dev), torch.cuda.stream(self.stream):
-                    nb_, ns_ = _stage2_bytes(D, W, H, float(call.view.slab_fraction))
-                    self.binning = _bytes(nb_, dev)
-                    scratch2 = _bytes(ns_, dev)
-                    grad_rec = self.grad_rec
-                    _C.check(lib.msgs_forward_stage2(call.view_ref, call.g_ref, _ptr(self.geom), self.geom.numel(), D,
-                                                     _ptr(self.binning), self.binning.numel(), _ptr(scratch2),
-                                                     scratch2.numel(), _ptr(self.image), self.image.numel(), _ptr(color),
-                                                     _ptr(acc_ps), _ptr(depth), _ptr(grad_rec),
-                                                     grad_rec.numel() if grad_rec is not None else 0,
-                                                     int(self.backward_follows), _C.timer_ptr(),
-                                                     C.c_void_p(self.stream.cuda_stream)), "msgs_forward_stage2")
-                    del scratch2
+                with _on_device(call.device), torch.cuda.stream(self.stream):
+                    self.binning = _redo_stage2(call, self.geom, self.image, D, float(call.view.slab_fraction), self.outs,
+                                                self.grad_rec, self.backward_follows, C.c_void_p(self.stream.cuda_stream))
             self.state = (self.geom, self.binning, self.image, D)
             self.outs = self.grad_rec = self.error = None
             return self.state
@@ -705,26 +718,20 @@ def _forward_impl(call, grad_rec=None, backward_follows=False):
                                   _ptr(grad_rec), grad_rec.numel() if grad_rec is not None else 0, int(backward_follows),
                                   C.byref(D), C.byref(done), _C.timer_ptr(), stream), "msgs_forward")
         D = int(D.value)
-        _note_instances(key, D, guess)
-        _note_info(key)
         del scratch1, scratch2, tmp
-        forward_stats["forwards"] += 1
-        if not done.value:                              # first frame of this shape, or the scene grew past the margin
-            # Stage 2 again, on the geom a truncated speculative stage 2 (capacity < D) may have written to.  What that run left
-            # there is rewritten or no longer read as input (tests/test_stage2_routes_gpu.py): the SlabHeader counts, the open-tile
-            # bitmap and n_open are reset by slab_split_kernel; the heavy-queue word is cleared before each emit; offs_b /
-            # scan_b are recomputed by slab B's recount and scan; and the flag that marks offs_b as stage 1's cell ranges
-            # (SlabHeader pad[0]) was cleared by the first run's slab B scan, so this run recounts without the cell prefilter.
-            forward_stats["non_speculative"] += 1
-            nb_, ns_ = _stage2_bytes(D, W, H, frac)
-            binning = _bytes(nb_, dev)
-            scratch2 = _bytes(ns_, dev)
-            _C.check(lib.msgs_forward_stage2(call.view_ref, call.g_ref, _ptr(geom), n_geom, D,
-                                             _ptr(binning), binning.numel(), _ptr(scratch2), scratch2.numel(),
-                                             _ptr(image), n_img, _ptr(color), _ptr(acc_ps), _ptr(depth),
-                                             _ptr(grad_rec), grad_rec.numel() if grad_rec is not None else 0,
-                                             int(backward_follows), _C.timer_ptr(), stream), "msgs_forward_stage2")
+        _note_count(key, D, guess, done.value)
+        if not done.value:
+            binning = _redo_stage2(call, geom, image, D, frac, (color, acc_ps, depth), grad_rec, backward_follows, stream)
     return color, acc_ps, depth, radii, pixel_sizes, (geom, binning, image, D)
+
+
+def _forward_tail(ctx, call, state, outs):
+    """the end of every autograd forward: what its backward finds on ctx; returns the five outputs"""
+    color, acc_ps, depth, radii, pixel_sizes = outs
+    ctx.call, ctx.state, ctx.radii = call, state, radii
+    ctx.mark_non_differentiable(acc_ps, radii, pixel_sizes)     # depth is differentiable (DESIGN.md 2, M6)
+    ctx.set_materialize_grads(False)      # grad_depth is None unless the loss used the depth map: then the colour-only path
+    return tuple(outs)
 
 
 class _RasterizeGaussians(torch.autograd.Function):
@@ -754,15 +761,10 @@ class _RasterizeGaussians(torch.autograd.Function):
         call = _Call(raster_settings, means3D, _opt(sh), _opt(colors_precomp), opacities, _opt(scales),
                      _opt(rotations), _opt(cov3Ds_precomp), _opt(max_pixel_sizes), _opt(min_pixel_sizes),
                      _opt(occ_multiplier), _opt(dc_delta), _opt(base_mask))
-        color, acc_ps, depth, radii, pixel_sizes, state = _forward_impl(call, _alloc_grad_records(ctx, call.P, call.device), ctx.backward_follows)
-        ctx.call = call
-        ctx.state = state
-        ctx.radii = radii
+        *outs, state = _forward_impl(call, _alloc_grad_records(ctx, call.P, call.device), ctx.backward_follows)
         ctx.shapes = (means2D.shape, opacities.shape)
         _save_inputs(ctx, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp)
-        ctx.mark_non_differentiable(acc_ps, radii, pixel_sizes)     # depth is differentiable
-        ctx.set_materialize_grads(False)      # grad_depth is None unless the loss used the depth map: then the colour-only path
-        return color, acc_ps, depth, radii, pixel_sizes
+        return _forward_tail(ctx, call, state, outs)
 
     @staticmethod
     def backward(ctx, grad_color, grad_acc_ps, grad_depth, grad_radii, grad_pixel_sizes):
@@ -993,14 +995,11 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
         call = _Call(raster_settings, xyz, None, None, opacity_raw, scaling_raw, rotation_raw, None,
                      _opt(max_pixel_sizes), _opt(min_pixel_sizes), _opt(occ_multiplier), _opt(dc_delta),
                      _opt(base_mask), raw_features=(features_dc, features_rest))
-        color, acc_ps, depth, radii, pixel_sizes, state = _forward_impl(call, _alloc_grad_records(ctx, call.P, call.device), ctx.backward_follows)
-        ctx.call, ctx.state, ctx.radii = call, state, radii
+        *outs, state = _forward_impl(call, _alloc_grad_records(ctx, call.P, call.device), ctx.backward_follows)
         ctx.shapes = (means2D.shape, features_dc.shape, features_rest.shape, opacity_raw.shape)
         _snapshot_sinks(ctx, (xyz, features_dc, features_rest, opacity_raw, scaling_raw, rotation_raw))
         _save_inputs(ctx, xyz, features_dc, features_rest, opacity_raw, scaling_raw, rotation_raw)
-        ctx.mark_non_differentiable(acc_ps, radii, pixel_sizes)     # depth is differentiable
-        ctx.set_materialize_grads(False)      # grad_depth is None unless the loss used the depth map: then the colour-only path
-        return color, acc_ps, depth, radii, pixel_sizes
+        return _forward_tail(ctx, call, state, outs)
 
     @staticmethod
     def backward(ctx, grad_color, grad_acc_ps, grad_depth, grad_radii, grad_pixel_sizes):
@@ -1076,15 +1075,12 @@ class _RasterizeGaussiansChained(torch.autograd.Function):
         call = _Call(raster_settings, xyz, _opt(shs), None, opacities, scales, rotations, None,
                      _opt(max_pixel_sizes), _opt(min_pixel_sizes), _opt(occ_multiplier), _opt(dc_delta),
                      _opt(base_mask), raw_features=(features_dc, features_rest), rotations_raw=rotation_raw)
-        color, acc_ps, depth, radii, pixel_sizes, state = _forward_impl(call, _alloc_grad_records(ctx, call.P, call.device), ctx.backward_follows)
-        ctx.call, ctx.state, ctx.radii = call, state, radii
+        *outs, state = _forward_impl(call, _alloc_grad_records(ctx, call.P, call.device), ctx.backward_follows)
         ctx.shapes = (means2D.shape, features_dc.shape, features_rest.shape, opacity_raw.shape)
         _snapshot_sinks(ctx, (xyz, features_dc, features_rest, opacity_raw, scaling_raw, rotation_raw))
         _save_inputs(ctx, xyz, features_dc, features_rest, opacity_raw, scaling_raw, rotation_raw, shs, opacities,
                      scales, rotations)
-        ctx.mark_non_differentiable(acc_ps, radii, pixel_sizes)     # depth is differentiable
-        ctx.set_materialize_grads(False)      # grad_depth is None unless the loss used the depth map: then the colour-only path
-        return color, acc_ps, depth, radii, pixel_sizes
+        return _forward_tail(ctx, call, state, outs)
 
     @staticmethod
     def backward(ctx, grad_color, grad_acc_ps, grad_depth, grad_radii, grad_pixel_sizes):
