@@ -545,6 +545,82 @@ typedef struct msgs_densify_stats {
 } msgs_densify_stats_t;
 int msgs_densify_stats(const msgs_densify_stats_t* stats, void* stream);
 
+/* ---- model surgery: clone, split, prune, grow, append (densification mechanism) ---------------------------------
+ * The reference's GaussianModel.densify_and_prune / grow_large_gaussians / prune_points / densification_postfix
+ * (/root/reference/scene/gaussian_model.py:452-537,599-662) as two calls over every per-Gaussian tensor (DESIGN.md SPEC D1):
+ *   msgs_densify_select  one thread per source row decides its fate (kept, cloned, split, children kept, grown), clears
+ *                        column reso_lvl of xyz_gradient_accum / denom IN PLACE as the reference does, and builds the row
+ *                        map of the output in `scratch` (stable placement, no atomics).  Reads the segment sizes back:
+ *                        the call's only host synchronisation.
+ *                        counts_host[8] = { kept, clones kept, children kept (per child), split, grown, appended, P_out, 0 }
+ *   msgs_densify_apply   one launch writes every output tensor from the map, with one rule per tensor and row kind.
+ * Output rows: kept source rows, then clones, first children, second children, grown rows, appended rows (each in source
+ * order).  Thresholds are float32 (the rounding torch applies to a Python float compared with a float32 tensor). */
+#define MSGS_DENSIFY_PRUNE 0        /* densify_and_prune: clone + split + prune                         */
+#define MSGS_DENSIFY_GROW 1         /* grow_large_gaussians                                             */
+#define MSGS_DENSIFY_PRUNE_MASK 2   /* prune_points(mask)                                               */
+#define MSGS_DENSIFY_APPEND 3       /* densification_postfix                                            */
+typedef struct msgs_densify_select {
+    int32_t mode;                    /* MSGS_DENSIFY_* */
+    int32_t reso_lvl;                /* column of accum / denom read (GROW) and cleared (PRUNE: 0, GROW, APPEND) */
+    int32_t reso_lvls;               /* L: second dim of accum / denom */
+    int32_t has_max_screen_size;     /* PRUNE: `if max_screen_size:` of the reference */
+    int64_t P;                       /* source rows */
+    int64_t n_append;                /* APPEND: rows appended */
+    float grad_threshold;            /* PRUNE: max_grad; GROW: grad_threshold */
+    float min_opacity;               /* PRUNE */
+    float scale_limit;               /* PRUNE: percent_dense * extent */
+    float big_world_limit;           /* PRUNE: 0.1 * extent */
+    float max_screen_size;           /* PRUNE, when has_max_screen_size */
+    int32_t reserved;
+    const float* opacity;            /* [P] logits (PRUNE) */
+    const float* scaling;            /* [P,3] log scales (PRUNE) */
+    float* xyz_gradient_accum;       /* [P,L,1] (PRUNE, GROW, APPEND) */
+    float* denom;                    /* [P,L,1] (PRUNE, GROW, APPEND) */
+    const int64_t* target_reso_lvl;  /* [P] (PRUNE) */
+    const uint8_t* prune_mask;       /* [P] bool, true = remove (PRUNE_MASK) */
+} msgs_densify_select_t;
+size_t msgs_densify_scratch_bytes(int64_t P, int64_t n_append);
+int msgs_densify_select(const msgs_densify_select_t* sel, void* scratch, size_t scratch_bytes, int64_t* counts_host,
+                        void* stream);
+
+/* rules of msgs_densify_tensor_t.rule[kind], kind = 0 kept, 1 clone, 2 first child, 3 second child, 4 grown, 5 appended */
+#define MSGS_DR_COPY 0               /* the source row */
+#define MSGS_DR_ZERO 1               /* zeros (false for bool) */
+#define MSGS_DR_COPY_CLEAR_COL 2     /* the source row with element reso_lvl zeroed (accum / denom) */
+#define MSGS_DR_SPLIT_XYZ 3          /* R(q) (z * exp(s)) + xyz, z = draws row (split ordinal, + n_split for the 2nd child) */
+#define MSGS_DR_SPLIT_SCALE 4        /* log(exp(s) / 1.6) */
+#define MSGS_DR_SPLIT_DIV 5          /* x / 1.6 */
+#define MSGS_DR_GROW_OPACITY 6       /* inverse_sigmoid(sigmoid(o) / 2) */
+#define MSGS_DR_GROW_SCALE 7         /* log(exp(s) * 2) */
+#define MSGS_DR_GROW_MUL 8           /* x * 2 */
+#define MSGS_DR_CONST 9              /* `constant` (int64 tensors) */
+#define MSGS_DR_APPEND 10            /* row of append_src */
+#define MSGS_DENSIFY_MAX_TENSORS 32
+typedef struct msgs_densify_tensor {
+    void* dst;                       /* [P_out, width] */
+    const void* src;                 /* [P, width] */
+    const void* append_src;          /* [n_append, width] (MSGS_DR_APPEND) */
+    int64_t constant;                /* MSGS_DR_CONST */
+    int32_t width;                   /* elements per row */
+    int32_t elem_bytes;              /* 4 float32, 8 int64, 1 bool */
+    uint8_t rule[8];                 /* per row kind (6 used) */
+} msgs_densify_tensor_t;
+typedef struct msgs_densify_apply {
+    int64_t P;                       /* as in the select call that filled `scratch` */
+    int64_t n_append;                /* as in the select call */
+    int64_t P_out;                   /* counts_host[6] of the select call */
+    int64_t n_split;                 /* counts_host[3] */
+    int32_t n_tensors;
+    int32_t reso_lvl;                /* column zeroed by MSGS_DR_COPY_CLEAR_COL */
+    const float* xyz;                /* [P,3] sources of MSGS_DR_SPLIT_XYZ */
+    const float* scaling;            /* [P,3] */
+    const float* rotation;           /* [P,4] */
+    const float* draws;              /* [2*n_split, 3] standard normal draws */
+    const msgs_densify_tensor_t* tensors;
+} msgs_densify_apply_t;
+int msgs_densify_apply(const msgs_densify_apply_t* apply, const void* scratch, size_t scratch_bytes, void* stream);
+
 /* ---- fused photometric loss ----------------------------------------------------------------
  * loss = (1 - lambda_dssim) * l1_loss(img, gt) + lambda_dssim * (1 - ssim(img, gt))   (/root/reference/train.py:209-211)
  * with l1_loss / ssim of /root/reference/utils/loss_utils.py:17-18,32-63 (window 11, sigma 1.5, zero padding, mean).

@@ -1021,6 +1021,25 @@ int msgs_densify_stats(const msgs_densify_stats_t* d, void* stream) {
     return MSGS_OK;
 }
 
+size_t msgs_densify_scratch_bytes(int64_t P, int64_t n_append) {
+    return densify_scratch_bytes(P > 0 ? P : 0, n_append > 0 ? n_append : 0);
+}
+
+int msgs_densify_select(const msgs_densify_select_t* sel, void* scratch, size_t scratch_bytes, int64_t* counts_host,
+                        void* stream) {
+    if (!sel || !counts_host || !scratch) return MSGS_ERR_INVALID_ARG;
+    if (int rc = densify_check_select(*sel)) return rc;
+    if (scratch_bytes < densify_scratch_bytes(sel->P, sel->n_append)) return MSGS_ERR_CAPACITY;
+    return densify_select(*sel, (char*)scratch, counts_host, (hipStream_t)stream);
+}
+
+int msgs_densify_apply(const msgs_densify_apply_t* apply, const void* scratch, size_t scratch_bytes, void* stream) {
+    if (!apply || !scratch) return MSGS_ERR_INVALID_ARG;
+    if (int rc = densify_check_apply(*apply)) return rc;
+    if (scratch_bytes < densify_scratch_bytes(apply->P, apply->n_append)) return MSGS_ERR_CAPACITY;
+    return densify_apply(*apply, (const char*)scratch, (hipStream_t)stream);
+}
+
 static int loss_args_ok(const float* img, const float* gt, int32_t C, int32_t H, int32_t W, float lambda) {
     if (!img || !gt || C < 1 || H < 1 || W < 1 || !(lambda >= 0.f && lambda <= 1.f)) return MSGS_ERR_INVALID_ARG;
     if ((int64_t)C * H * W > (int64_t)1 << 31 || C > 65535) return MSGS_ERR_TOO_MANY;

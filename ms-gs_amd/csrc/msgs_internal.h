@@ -697,6 +697,13 @@ hipError_t launch_adam(const msgs_adam_tensor_t* tensors, int n, int64_t step, d
                        hipStream_t s);
 hipError_t launch_densify_stats(const msgs_densify_stats_t& d, hipStream_t s);
 
+// densify.hip
+size_t densify_scratch_bytes(int64_t P, int64_t n_append);
+int densify_check_select(const msgs_densify_select_t& s);
+int densify_check_apply(const msgs_densify_apply_t& a);
+int densify_select(const msgs_densify_select_t& s, char* scratch, int64_t* counts_host, hipStream_t st);
+int densify_apply(const msgs_densify_apply_t& a, const char* scratch, hipStream_t st);
+
 // loss.hip
 size_t loss_scratch_bytes(int C, int H, int W);
 void ssim_window_host(float w[11]);

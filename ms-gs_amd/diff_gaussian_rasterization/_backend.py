@@ -81,6 +81,33 @@ class DensifyStats(C.Structure):
                 ("base_mask", C.c_void_p)]
 
 
+DENSIFY_PRUNE, DENSIFY_GROW, DENSIFY_PRUNE_MASK, DENSIFY_APPEND = 0, 1, 2, 3
+(DR_COPY, DR_ZERO, DR_COPY_CLEAR_COL, DR_SPLIT_XYZ, DR_SPLIT_SCALE, DR_SPLIT_DIV, DR_GROW_OPACITY, DR_GROW_SCALE, DR_GROW_MUL,
+ DR_CONST, DR_APPEND) = range(11)
+DENSIFY_MAX_TENSORS = 32
+
+
+class DensifySelect(C.Structure):        # msgs_densify_select_t
+    _fields_ = [("mode", C.c_int32), ("reso_lvl", C.c_int32), ("reso_lvls", C.c_int32), ("has_max_screen_size", C.c_int32),
+                ("P", C.c_int64), ("n_append", C.c_int64),
+                ("grad_threshold", C.c_float), ("min_opacity", C.c_float), ("scale_limit", C.c_float),
+                ("big_world_limit", C.c_float), ("max_screen_size", C.c_float), ("reserved", C.c_int32),
+                ("opacity", C.c_void_p), ("scaling", C.c_void_p), ("xyz_gradient_accum", C.c_void_p), ("denom", C.c_void_p),
+                ("target_reso_lvl", C.c_void_p), ("prune_mask", C.c_void_p)]
+
+
+class DensifyTensor(C.Structure):        # msgs_densify_tensor_t
+    _fields_ = [("dst", C.c_void_p), ("src", C.c_void_p), ("append_src", C.c_void_p), ("constant", C.c_int64),
+                ("width", C.c_int32), ("elem_bytes", C.c_int32), ("rule", C.c_uint8 * 8)]
+
+
+class DensifyApply(C.Structure):         # msgs_densify_apply_t
+    _fields_ = [("P", C.c_int64), ("n_append", C.c_int64), ("P_out", C.c_int64), ("n_split", C.c_int64),
+                ("n_tensors", C.c_int32), ("reso_lvl", C.c_int32),
+                ("xyz", C.c_void_p), ("scaling", C.c_void_p), ("rotation", C.c_void_p), ("draws", C.c_void_p),
+                ("tensors", C.POINTER(DensifyTensor))]
+
+
 class Timing(C.Structure):
     _fields_ = [("ev", C.c_void_p * (2 * K_COUNT))]
 
@@ -180,6 +207,12 @@ def _load():
     lib.msgs_adam_step.argtypes = [C.POINTER(AdamTensor), C.c_int32, C.c_int64, C.c_double, C.c_double, C.c_double, vp]
     lib.msgs_densify_stats.restype = C.c_int
     lib.msgs_densify_stats.argtypes = [C.POINTER(DensifyStats), vp]
+    lib.msgs_densify_scratch_bytes.restype = sz
+    lib.msgs_densify_scratch_bytes.argtypes = [C.c_int64, C.c_int64]
+    lib.msgs_densify_select.restype = C.c_int
+    lib.msgs_densify_select.argtypes = [C.POINTER(DensifySelect), vp, sz, C.POINTER(C.c_int64), vp]
+    lib.msgs_densify_apply.restype = C.c_int
+    lib.msgs_densify_apply.argtypes = [C.POINTER(DensifyApply), vp, sz, vp]
     lib.msgs_loss_scratch_bytes.restype = sz
     lib.msgs_loss_scratch_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
     lib.msgs_loss_forward.restype = C.c_int
@@ -220,7 +253,8 @@ EXPORTS = ("msgs_abi_version", "msgs_error_string", "msgs_geom_bytes", "msgs_sta
            "msgs_status_create", "msgs_status_destroy", "msgs_forward_launch", "msgs_forward_finish",
            "msgs_set_occlusion", "msgs_occlusion_stats", "msgs_forward_info", "msgs_binning_bytes_slab",
            "msgs_stage2_scratch_bytes_slab", "msgs_slab_stats", "msgs_backward_with_depth",
-           "msgs_backward_scratch_bytes_deterministic_depth", "msgs_backward_with_camera", "msgs_camera_grad_scratch_bytes")
+           "msgs_backward_scratch_bytes_deterministic_depth", "msgs_backward_with_camera", "msgs_camera_grad_scratch_bytes",
+           "msgs_densify_scratch_bytes", "msgs_densify_select", "msgs_densify_apply")
 
 
 def check(rc, where):
