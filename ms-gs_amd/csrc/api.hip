@@ -826,10 +826,8 @@ int backward_impl(const msgs_view_t* view, const msgs_gaussians_t* g, const int3
     if ((rc = debug_sync(view, s))) return rc;
 
     tm.begin(MSGS_K_PREPROCESS_BWD);
-    if (det)      // the nine TEXTBOOK sums per Gaussian ([P, 9] doubles; [P, 10] with depth) as they are
-        HIP_TRY(launch_preprocess_backward(vp, *g, radii, geom, grad_rec, *grads, s, true, dL_ddepth != nullptr, cam));
-    else
-        HIP_TRY(launch_preprocess_backward(vp, *g, radii, geom, grad_rec, *grads, s, false, dL_ddepth != nullptr, cam));
+    // det: the nine TEXTBOOK sums per Gaussian ([P, 9] doubles; [P, 10] with depth) as they are
+    HIP_TRY(launch_preprocess_backward(vp, *g, radii, geom, grad_rec, *grads, s, det, dL_ddepth != nullptr, cam));
     tm.end(MSGS_K_PREPROCESS_BWD);
     return debug_sync(view, s);
 }

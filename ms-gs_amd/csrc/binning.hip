@@ -607,18 +607,14 @@ hipError_t launch_emit(const ViewParams& vp, int P, const char* geom, uint32_t* 
     if (heavy_q) {
         // at most D / EMIT_HEAVY_MIN Gaussians can be queued; workgroups beyond the queue's length leave at once
         const unsigned hb = (unsigned)std::min<int64_t>(2048, D / EMIT_HEAVY_MIN + 1);
-        if (keys16 && slab == 2)
-            hipLaunchKernelGGL((emit_heavy_kernel<uint16_t, true>), dim3(hb), block, 0, s, vp, P, geom, k16, ids, D, D_dev,
-                               (const uint32_t*)heavy_q, sl);
-        else if (keys16)
-            hipLaunchKernelGGL((emit_heavy_kernel<uint16_t, false>), dim3(hb), block, 0, s, vp, P, geom, k16, ids, D, D_dev,
-                               (const uint32_t*)heavy_q, sl);
-        else if (slab == 2)
-            hipLaunchKernelGGL((emit_heavy_kernel<uint32_t, true>), dim3(hb), block, 0, s, vp, P, geom, keys, ids, D, D_dev,
-                               (const uint32_t*)heavy_q, sl);
-        else
-            hipLaunchKernelGGL((emit_heavy_kernel<uint32_t, false>), dim3(hb), block, 0, s, vp, P, geom, keys, ids, D, D_dev,
-                               (const uint32_t*)heavy_q, sl);
+        with_bool(slab == 2, [&](auto SLAB_B) {
+            if (keys16)
+                hipLaunchKernelGGL((emit_heavy_kernel<uint16_t, decltype(SLAB_B)::value>), dim3(hb), block, 0, s, vp, P, geom, k16, ids, D,
+                                   D_dev, (const uint32_t*)heavy_q, sl);
+            else
+                hipLaunchKernelGGL((emit_heavy_kernel<uint32_t, decltype(SLAB_B)::value>), dim3(hb), block, 0, s, vp, P, geom, keys, ids, D,
+                                   D_dev, (const uint32_t*)heavy_q, sl);
+        });
     }
     return hipGetLastError();
 }

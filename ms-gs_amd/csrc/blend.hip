@@ -896,8 +896,8 @@ __global__ void trace_set_kernel(unsigned long long* p) { g_tile_trace = p; }
 // COUNT = true (diagnostic replica, msgs_blend_lane_stats): nothing is reduced or written; grad_out receives four counters —
 // (tile, entry) visits, (quadrant, entry) evaluations (each 64 lanes), lanes that contributed, visits with a contribution.
 // (The verification mode — msgs_set_deterministic — does not run this kernel: literal.hip restates the reference's loop.)
-// CH = 4 (colour + depth): the depth channel of backward_walk, with z in the free slot of s_bi.  (CH is an int, not a second
-// bool: tools/isa_mix.py looks for this kernel by a mangled name, which a second bool parameter would start to match.)
+// CH = 4 (colour + depth): the depth channel of backward_walk, with z in the free slot of s_bi.  (tools/isa_mix.py finds the
+// <false, 3> instantiation by the mangled-name fragment `blend_backward_tile_kernelILb0ELi3E`: parameters added behind CH keep it.)
 template <bool COUNT = false, int CH = 3>
 __global__ __launch_bounds__(64) void blend_backward_tile_kernel(ViewParams vp, const GaussRec* __restrict__ rec,
                                                                  const uint32_t* __restrict__ ids,
@@ -1109,30 +1109,37 @@ int set_blend_granularity(int mode) { return g_granularity.exchange(mode == 1 ||
 //         74/98;  G = 32: 167/207, 115/130, 104/108, 91/97
 //   SB 1: G = 16: 329/368, 139/152, 82/94, 76/89;  G = 32: 277/330, 120/130, 73/86, 65/81;  G = 64: 246/304, 112/131, 71/84, 62/74
 // i.e. the best shape keeps 2000-3000 waves in flight: 4x4 blocks down to ~64 tiles, 2x2 blocks down to ~16, single pixels below.
-struct FineShape { int sb, g; };
-static FineShape fine_shape(int tiles) {
-    FineShape f;
-    f.sb = tiles <= 16 ? 1 : (tiles <= 64 ? 2 : 4);
-    f.g = f.sb == 1 ? 64 : (f.sb == 2 ? 16 : (tiles < 768 ? 4 : 1));   // (>= 768 tiles — forced granularity only — one workgroup per
-    return f;                                                           //  tile fills the chip)
+// Only the four shapes chosen below are built; the others of the table were measured and are no longer instantiated.
+// A shape names what is launched: workgroups of WAVES waves, a wave per SB x SB sub-block, G = groups workgroups per tile.
+template <int WAVES, int SB>
+struct FineShape { static constexpr int waves = WAVES, sb = SB, groups = (TILE / SB) * (TILE / SB) / WAVES; };
+// f(FineShape<WAVES, SB>{}) for the shape of a `tiles`-tile image (forward and backward alike)
+template <class F>
+static void with_fine_shape(int tiles, F&& f) {
+    if (tiles <= 16) f(FineShape<4, 1>{});            // single pixels, G = 64
+    else if (tiles <= 64) f(FineShape<4, 2>{});       // 2x2 sub-blocks, G = 16
+    else if (tiles < 768) f(FineShape<4, 4>{});       // 4x4 sub-blocks, G = 4
+    else f(FineShape<16, 4>{});                       // (>= 768 tiles — forced granularity only — one workgroup per tile fills the chip)
 }
-template <int WAVES, int SB = 4, class... Args>
-static void launch_fine_fwd(int tiles, hipStream_t s, Args... args) {
-    constexpr int NSB = (TILE / SB) * (TILE / SB);
-    hipLaunchKernelGGL((blend_forward_fine_kernel<WAVES, SB>), dim3(tiles * (NSB / WAVES)), dim3(64 * WAVES), 0, s, args...);
-}
-template <int WAVES, int SB = 4, int CH = 3, class... Args>
-static void launch_fine_bwd(int tiles, hipStream_t s, Args... args) {
-    constexpr int NSB = (TILE / SB) * (TILE / SB);
-    hipLaunchKernelGGL((blend_backward_fine_kernel<WAVES, SB, CH>), dim3(tiles * (NSB / WAVES)), dim3(64 * WAVES), 0, s, args...);
-}
-static bool use_fine(int tiles, int max_tiles) {
-    const int g = g_granularity.load();
-    return g == 2 || (g == 0 && tiles < max_tiles);
-}
-static bool bwd_v1(int tiles) {
-    const int forced = g_bwd_gen.load();
-    return forced ? forced == 1 : tiles < BWD_GEN2_MIN_TILES;
+
+// Which kernel a `tiles`-tile image runs, decided once per launch from one load of each process-wide flag:
+//   forward   granularity 2, or granularity 0 and tiles < FINE_MAX_TILES_FWD     Fine
+//             otherwise                                                          Quadrant (the quadrant-list kernel)
+//   backward  granularity 2 (whatever the generation)                            Fine
+//             granularity 0, generation 0 and tiles < FINE_MAX_TILES_BWD         Fine
+//             otherwise generation 1, or generation 0 and tiles < BWD_GEN2_MIN_TILES   Quadrant (four waves per tile)
+//             otherwise (generation 2, or generation 0 from BWD_GEN2_MIN_TILES on)     Tile (one wave per tile)
+// (a forced generation switches the by-tile-count Fine choice off in the backward only)
+enum class FwdRoute { Quadrant, Fine };
+enum class BwdRoute { Fine, Quadrant, Tile };
+struct Routes { FwdRoute fwd; BwdRoute bwd; };
+static Routes routes(int tiles) {
+    const int gran = g_granularity.load(), gen = g_bwd_gen.load();
+    Routes r;
+    r.fwd = gran == 2 || (gran == 0 && tiles < FINE_MAX_TILES_FWD) ? FwdRoute::Fine : FwdRoute::Quadrant;
+    if (gran == 2 || (gran == 0 && gen == 0 && tiles < FINE_MAX_TILES_BWD)) r.bwd = BwdRoute::Fine;
+    else r.bwd = (gen ? gen == 1 : tiles < BWD_GEN2_MIN_TILES) ? BwdRoute::Quadrant : BwdRoute::Tile;
+    return r;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1197,15 +1204,11 @@ __global__ __launch_bounds__(ORDER_THREADS) void tile_order_kernel(int num_tiles
 }
 }  // namespace
 
-static bool bwd_uses_tile_kernel(int tiles) {
-    return !(g_granularity.load() == 2 || (g_bwd_gen.load() == 0 && use_fine(tiles, FINE_MAX_TILES_BWD))) && !bwd_v1(tiles);
-}
-
 hipError_t launch_tile_order(const ViewParams& vp, const uint32_t* tile_last, uint32_t* tile_order, hipStream_t s) {
     const int tiles = vp.gx * vp.gy;
-    if (tiles < 8 || !bwd_uses_tile_kernel(tiles)) return hipSuccess;
+    const Routes r = routes(tiles);
     // the fine-grained forward kernels do not write tile_last (and clear the order's validity word): no order from garbage
-    if (use_fine(tiles, FINE_MAX_TILES_FWD)) return hipSuccess;
+    if (tiles < 8 || r.bwd != BwdRoute::Tile || r.fwd == FwdRoute::Fine) return hipSuccess;
     hipLaunchKernelGGL(tile_order_kernel, dim3(8), dim3(ORDER_THREADS), 0, s, tiles, tile_last, tile_order);
     return hipGetLastError();
 }
@@ -1231,30 +1234,19 @@ hipError_t launch_blend_forward(const ViewParams& vp, const char* geom, const ui
     // tile_last sits in front of tile_order in the image state (ImageLayout): the order's validity word
     uint32_t* order_flag = tile_last ? reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(tile_last) +
                                                                    align256(4 * (size_t)tiles)) + tiles : nullptr;
-    auto fine = [&] {            // few tiles (low pyramid levels): one wave per 4x4 sub-block, the tile split over G workgroups
-        const FineShape f = fine_shape(tiles);
-#define MSGS_FINE_FWD(WAVES, SB) launch_fine_fwd<WAVES, SB>(tiles, s, vp, rec, ids, ranges, out_color, out_ps, out_depth, final_T, \
-                                                            n_contrib, cp, cn, order_flag)
-        if (f.sb == 1) {                      // single pixels: 256 waves per tile
-            if (f.g >= 64) MSGS_FINE_FWD(4, 1); else if (f.g == 32) MSGS_FINE_FWD(8, 1); else MSGS_FINE_FWD(16, 1);
-        } else if (f.sb == 2) {               // 2x2 sub-blocks: 64 waves per tile
-            if (f.g >= 32) MSGS_FINE_FWD(2, 2); else if (f.g == 16) MSGS_FINE_FWD(4, 2); else if (f.g == 8) MSGS_FINE_FWD(8, 2);
-            else MSGS_FINE_FWD(16, 2);
-        } else {                              // 4x4 sub-blocks: 16 waves per tile
-            if (f.g >= 16) MSGS_FINE_FWD(1, 4); else if (f.g == 8) MSGS_FINE_FWD(2, 4); else if (f.g == 4) MSGS_FINE_FWD(4, 4);
-            else if (f.g == 2) MSGS_FINE_FWD(8, 4); else MSGS_FINE_FWD(16, 4);
-        }
-#undef MSGS_FINE_FWD
-    };
     FwdSlab sb{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     if (slab) {
         sb.dtrav = slab->dtrav;
         if (slab->pass == 1) { sb.open_bits = slab->open_bits; sb.open_list = slab->open_list; sb.n_open = slab->n_open; }
         if (slab->pass == 2) { sb.tile_list = slab->open_list; sb.n_tiles = slab->n_open; }
     }
-    if (use_fine(tiles, FINE_MAX_TILES_FWD)) {
+    if (routes(tiles).fwd == FwdRoute::Fine) {   // few tiles (low pyramid levels): one wave per sub-block, the tile split over G workgroups
         if (slab && slab->pass != 0) return hipErrorInvalidValue;        // (the caller engages slabs from SLAB_MIN_TILES tiles on)
-        fine();
+        with_fine_shape(tiles, [&](auto shape) {
+            using S = decltype(shape);
+            hipLaunchKernelGGL((blend_forward_fine_kernel<S::waves, S::sb>), dim3(tiles * S::groups), dim3(64 * S::waves), 0, s, vp, rec,
+                               ids, ranges, out_color, out_ps, out_depth, final_T, n_contrib, cp, cn, order_flag);
+        });
     } else {
         // slab B walks the list of open tiles with a grid that fills the chip once (normally a handful of tiles)
         const int grid = sb.tile_list ? std::min(tiles, 2048) : tiles;
@@ -1273,7 +1265,7 @@ hipError_t launch_forward_feedback(const unsigned long long* dtrav, const SlabHe
 }
 
 // does the forward of a `tiles`-tile image run the quadrant-list kernel (the one that can publish open tiles / tile lengths)?
-bool forward_uses_quadrant_kernel(int tiles) { return tiles > 0 && !use_fine(tiles, FINE_MAX_TILES_FWD); }
+bool forward_uses_quadrant_kernel(int tiles) { return tiles > 0 && routes(tiles).fwd == FwdRoute::Quadrant; }
 
 hipError_t launch_blend_backward(const ViewParams& vp, const char* geom, const uint32_t* ids, const uint2* ranges,
                                  const float* final_T, const uint32_t* n_contrib, const float* dL_dcolor,
@@ -1281,36 +1273,23 @@ hipError_t launch_blend_backward(const ViewParams& vp, const char* geom, const u
     const int tiles = vp.gx * vp.gy;
     if (tiles == 0) return hipSuccess;
     const GaussRec* rec = reinterpret_cast<const GaussRec*>(geom);
+    const BwdRoute route = routes(tiles).bwd;
     // dL_ddepth != nullptr: the depth variants of the same three kernels (same route choice, record slot 9 = dL/dz)
-    if (g_granularity.load() == 2 || (g_bwd_gen.load() == 0 && use_fine(tiles, FINE_MAX_TILES_BWD))) {
-        const FineShape f = fine_shape(tiles);
-#define MSGS_FINE_BWD(WAVES, SB) (dL_ddepth ? launch_fine_bwd<WAVES, SB, 4>(tiles, s, vp, rec, ids, ranges, final_T, n_contrib, \
-                                                                            dL_dcolor, grad_rec, dL_ddepth)                         \
-                                            : launch_fine_bwd<WAVES, SB, 3>(tiles, s, vp, rec, ids, ranges, final_T, n_contrib,    \
-                                                                            dL_dcolor, grad_rec, (const float*)nullptr))
-        if (f.sb == 1) {
-            if (f.g >= 64) MSGS_FINE_BWD(4, 1); else if (f.g == 32) MSGS_FINE_BWD(8, 1); else MSGS_FINE_BWD(16, 1);
-        } else if (f.sb == 2) {
-            if (f.g >= 32) MSGS_FINE_BWD(2, 2); else if (f.g == 16) MSGS_FINE_BWD(4, 2); else if (f.g == 8) MSGS_FINE_BWD(8, 2);
-            else MSGS_FINE_BWD(16, 2);
-        } else {
-            if (f.g >= 16) MSGS_FINE_BWD(1, 4); else if (f.g == 8) MSGS_FINE_BWD(2, 4); else if (f.g == 4) MSGS_FINE_BWD(4, 4);
-            else if (f.g == 2) MSGS_FINE_BWD(8, 4); else MSGS_FINE_BWD(16, 4);
-        }
-#undef MSGS_FINE_BWD
-    }
-    else if (!bwd_v1(tiles) && dL_ddepth)
-        hipLaunchKernelGGL((blend_backward_tile_kernel<false, 4>), dim3(tiles), dim3(64), 0, s, vp, rec, ids, ranges, final_T,
-                           n_contrib, dL_dcolor, (void*)grad_rec, tile_order, dL_ddepth);
-    else if (!bwd_v1(tiles))
-        hipLaunchKernelGGL((blend_backward_tile_kernel<false, 3>), dim3(tiles), dim3(64), 0, s, vp, rec, ids, ranges, final_T,
-                           n_contrib, dL_dcolor, (void*)grad_rec, tile_order, (const float*)nullptr);
-    else if (dL_ddepth)
-        hipLaunchKernelGGL(blend_backward_kernel<4>, dim3(tiles), dim3(256), 0, s, vp, rec, ids, ranges, final_T,
-                           n_contrib, dL_dcolor, grad_rec, dL_ddepth);
-    else
-        hipLaunchKernelGGL(blend_backward_kernel<3>, dim3(tiles), dim3(256), 0, s, vp, rec, ids, ranges, final_T,
-                           n_contrib, dL_dcolor, grad_rec, (const float*)nullptr);
+    with_bool(dL_ddepth != nullptr, [&](auto DEPTH) {
+        constexpr int CH = decltype(DEPTH)::value ? 4 : 3;
+        if (route == BwdRoute::Fine)
+            with_fine_shape(tiles, [&](auto shape) {
+                using S = decltype(shape);
+                hipLaunchKernelGGL((blend_backward_fine_kernel<S::waves, S::sb, CH>), dim3(tiles * S::groups), dim3(64 * S::waves), 0, s,
+                                   vp, rec, ids, ranges, final_T, n_contrib, dL_dcolor, grad_rec, dL_ddepth);
+            });
+        else if (route == BwdRoute::Tile)
+            hipLaunchKernelGGL((blend_backward_tile_kernel<false, CH>), dim3(tiles), dim3(64), 0, s, vp, rec, ids, ranges, final_T,
+                               n_contrib, dL_dcolor, (void*)grad_rec, tile_order, dL_ddepth);
+        else
+            hipLaunchKernelGGL(blend_backward_kernel<CH>, dim3(tiles), dim3(256), 0, s, vp, rec, ids, ranges, final_T, n_contrib,
+                               dL_dcolor, grad_rec, dL_ddepth);
+    });
     return hipGetLastError();
 }
 
@@ -1386,12 +1365,10 @@ hipError_t launch_blend_backward_det(const ViewParams& vp, int P, const char* ge
     // backward takes (GRAD_REC_BYTES per Gaussian holds ten)
     static_assert(sizeof(grad_acc_t) == 8, "the verification mode's sums are doubles");
     static_assert(DET_INST_FLOATS_DEPTH <= GRAD_REC_FLOATS, "the [P, 10] sums fit the grad_rec region");
-    if (dL_ddepth)
-        hipLaunchKernelGGL(det_reduce_kernel<DET_INST_FLOATS_DEPTH>, dim3((unsigned)((D + 255) / 256)), dim3(256), 0, s, keys_s,
-                           entry, D, inst, grad_rec, DET_INST_FLOATS_DEPTH);
-    else
-        hipLaunchKernelGGL(det_reduce_kernel<DET_INST_FLOATS>, dim3((unsigned)((D + 255) / 256)), dim3(256), 0, s, keys_s, entry, D, inst,
-                           grad_rec, DET_INST_FLOATS);
+    with_bool(dL_ddepth != nullptr, [&](auto DEPTH) {
+        constexpr int NF = decltype(DEPTH)::value ? DET_INST_FLOATS_DEPTH : DET_INST_FLOATS;
+        hipLaunchKernelGGL(det_reduce_kernel<NF>, dim3((unsigned)((D + 255) / 256)), dim3(256), 0, s, keys_s, entry, D, inst, grad_rec, NF);
+    });
     return hipGetLastError();
 }
 

@@ -255,15 +255,11 @@ hipError_t launch_blend_backward_literal(const ViewParams& vp, const char* geom,
     const int tiles = vp.gx * vp.gy;
     if (tiles == 0) return hipSuccess;
     const GeomLayout L(P > 0 ? P : 1);
-    if (dL_ddepth) {
-        hipLaunchKernelGGL(blend_backward_literal_kernel<true>, dim3(tiles), dim3(LB), 0, s, vp,
+    with_bool(dL_ddepth != nullptr, [&](auto DEPTH) {
+        hipLaunchKernelGGL(blend_backward_literal_kernel<decltype(DEPTH)::value>, dim3(tiles), dim3(LB), 0, s, vp,
                            reinterpret_cast<const GaussRec*>(geom + L.rec), reinterpret_cast<const float4*>(geom + L.litrec), ids,
                            ranges, final_T, n_contrib, dL_dcolor, inst_grad, dL_ddepth);
-        return hipGetLastError();
-    }
-    hipLaunchKernelGGL(blend_backward_literal_kernel<false>, dim3(tiles), dim3(LB), 0, s, vp, reinterpret_cast<const GaussRec*>(geom + L.rec),
-                       reinterpret_cast<const float4*>(geom + L.litrec), ids, ranges, final_T, n_contrib, dL_dcolor, inst_grad,
-                       (const float*)nullptr);
+    });
     return hipGetLastError();
 }
 

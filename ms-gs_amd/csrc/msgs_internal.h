@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <cmath>
+#include <type_traits>
 #include "../../include/msgs.h"
 
 namespace msgs {
@@ -656,6 +657,13 @@ hipError_t exclusive_scan_u32(const uint32_t* in, const uint32_t* gather, uint32
                               uint32_t* overflow_flag = nullptr, uint32_t in_mask = 0xFFFFFFFFu, uint32_t* side_out = nullptr,
                               uint32_t* side_flag = nullptr);    // overflow_flag: set to 1 when the total exceeds `clamp`;
                                                                   // side_flag: set to 1 when side_out is written, to 0 otherwise
+// a run-time bool as a compile-time one: f(std::true_type{}) or f(std::false_type{}).  A launcher picks a kernel's bool
+// template arguments with it — one launch expression in a generic lambda, `decltype(B)::value` as the argument — instead of
+// one copy of the launch per value
+template <class F>
+inline void with_bool(bool b, F&& f) {
+    if (b) f(std::true_type{}); else f(std::false_type{});
+}
 // device-side fill with zeros (sort.hip): an ordinary kernel launch — hipMemsetAsync costs ~10 us of queue latency per
 // call on this runtime (barrier packets around the fill), four of them per step were 3 % of the C3 step
 hipError_t launch_zero(void* ptr, size_t bytes, hipStream_t s);     // ptr and bytes multiples of 4

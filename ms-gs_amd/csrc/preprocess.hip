@@ -1378,12 +1378,10 @@ hipError_t launch_preprocess(const ViewParams& vp, const msgs_gaussians_t& g, in
                              char* geom, hipStream_t s, ZeroJob zj, uint32_t* heavy_list, uint32_t* heavy_count, uint32_t* heavy_blk,
                              bool write_litrec) {
     if (g.P == 0) return hipSuccess;
-    if (g.raw_params != 0 && g.shs == nullptr)
-        hipLaunchKernelGGL(preprocess_kernel<true>, dim3((g.P + 255) / 256), dim3(256), 0, s, vp, g, radii, pixel_sizes, geom, zj,
-                           heavy_list, heavy_count, heavy_blk, write_litrec ? 1 : 0);
-    else
-        hipLaunchKernelGGL(preprocess_kernel<false>, dim3((g.P + 255) / 256), dim3(256), 0, s, vp, g, radii, pixel_sizes, geom, zj,
-                           heavy_list, heavy_count, heavy_blk, write_litrec ? 1 : 0);
+    with_bool(g.raw_params != 0 && g.shs == nullptr, [&](auto SPLIT_ROWS) {
+        hipLaunchKernelGGL(preprocess_kernel<decltype(SPLIT_ROWS)::value>, dim3((g.P + 255) / 256), dim3(256), 0, s, vp, g, radii,
+                           pixel_sizes, geom, zj, heavy_list, heavy_count, heavy_blk, write_litrec ? 1 : 0);
+    });
     return hipGetLastError();
 }
 
@@ -1423,10 +1421,10 @@ hipError_t launch_preprocess_backward(const ViewParams& vp, const msgs_gaussians
     if (camera) {            // camera gradients (msgs_backward_with_camera; never with the optimizer step, api.hip refuses it)
         if (aib) return hipErrorInvalidValue;
         const CamPartials cp{camera->rows};
-        if (textbook && depth) hipLaunchKernelGGL((preprocess_backward_kernel<true, false, true, true>), grid, block, 0, s, vp, g, radii, geom, grad_rec, grads, cp);
-        else if (textbook) hipLaunchKernelGGL((preprocess_backward_kernel<true, false, false, true>), grid, block, 0, s, vp, g, radii, geom, grad_rec, grads, cp);
-        else if (depth) hipLaunchKernelGGL((preprocess_backward_kernel<false, false, true, true>), grid, block, 0, s, vp, g, radii, geom, grad_rec, grads, cp);
-        else hipLaunchKernelGGL((preprocess_backward_kernel<false, false, false, true>), grid, block, 0, s, vp, g, radii, geom, grad_rec, grads, cp);
+        with_bool(textbook, [&](auto TB) { with_bool(depth, [&](auto DP) {
+            hipLaunchKernelGGL((preprocess_backward_kernel<decltype(TB)::value, false, decltype(DP)::value, true>), grid, block, 0, s, vp, g,
+                               radii, geom, grad_rec, grads, cp);
+        }); });
         hipError_t e = hipGetLastError();
         if (e == hipSuccess && grads.accumulated) e = hipEventRecord((hipEvent_t)grads.accumulated, s);
         if (e != hipSuccess) return e;
@@ -1444,16 +1442,11 @@ hipError_t launch_preprocess_backward(const ViewParams& vp, const msgs_gaussians
                            camera->dL_dviewmatrix, camera->dL_dprojmatrix, camera->dL_dcampos);
         return hipGetLastError();
     }
-    if (depth) {             // record slot 9 = dL/dz (msgs_backward_with_depth)
-        if (textbook && aib) hipLaunchKernelGGL((preprocess_backward_kernel<true, true, true>), grid, block, 0, s, vp, g, radii, geom, grad_rec, grads, ad);
-        else if (textbook) hipLaunchKernelGGL((preprocess_backward_kernel<true, false, true>), grid, block, 0, s, vp, g, radii, geom, grad_rec, grads, ad);
-        else if (aib) hipLaunchKernelGGL((preprocess_backward_kernel<false, true, true>), grid, block, 0, s, vp, g, radii, geom, grad_rec, grads, ad);
-        else hipLaunchKernelGGL((preprocess_backward_kernel<false, false, true>), grid, block, 0, s, vp, g, radii, geom, grad_rec, grads, ad);
-    }
-    else if (textbook && aib) hipLaunchKernelGGL((preprocess_backward_kernel<true, true>), grid, block, 0, s, vp, g, radii, geom, grad_rec, grads, ad);
-    else if (textbook) hipLaunchKernelGGL((preprocess_backward_kernel<true, false>), grid, block, 0, s, vp, g, radii, geom, grad_rec, grads, ad);
-    else if (aib) hipLaunchKernelGGL((preprocess_backward_kernel<false, true>), grid, block, 0, s, vp, g, radii, geom, grad_rec, grads, ad);
-    else hipLaunchKernelGGL((preprocess_backward_kernel<false, false>), grid, block, 0, s, vp, g, radii, geom, grad_rec, grads, ad);
+    // depth: record slot 9 = dL/dz (msgs_backward_with_depth)
+    with_bool(textbook, [&](auto TB) { with_bool(aib != nullptr, [&](auto ADAM) { with_bool(depth, [&](auto DP) {
+        hipLaunchKernelGGL((preprocess_backward_kernel<decltype(TB)::value, decltype(ADAM)::value, decltype(DP)::value>), grid, block, 0, s,
+                           vp, g, radii, geom, grad_rec, grads, ad);
+    }); }); });
     hipError_t e = hipGetLastError();
     if (e == hipSuccess && grads.accumulated) e = hipEventRecord((hipEvent_t)grads.accumulated, s);
     return e;

@@ -320,10 +320,11 @@ def test_forward_capacity_guess_paths_give_identical_results():
     assert routes[0] == 1 and routes[-1] == 0, (D, routes)      # both routes taken
 
 
-@pytest.mark.parametrize("W,H", [(203, 117), (120, 67), (43, 29)])
+@pytest.mark.parametrize("W,H", [(203, 117), (120, 67), (43, 29), (523, 397)])
 def test_blend_granularities_agree(W, H):
-    """The fine-grained kernels (one wave per 4x4 / 2x2 / 1x1 pixel sub-block: 104, 40 and 6 tiles select the three shapes,
-    blend.hip fine_shape) evaluate every pixel with the same arithmetic in
+    """The fine-grained kernels (one wave per 4x4 / 2x2 / 1x1 pixel sub-block: 104, 40 and 6 tiles select the three shapes
+    with four waves per workgroup, 825 tiles the 4x4 shape with a tile's sixteen waves in one workgroup — the four shapes of
+    blend.hip with_fine_shape) evaluate every pixel with the same arithmetic in
     the same order as the quadrant-per-wave kernels: forward outputs bit-identical, gradients equal up to the float32 partial sums the
     waves form over their pixels (the cross-tile accumulation is exact).  Ragged image (W, H not multiples of 16 or 4), multi-scale filters on, non-zero background."""
     import diff_gaussian_rasterization as dgr

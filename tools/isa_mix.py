@@ -1,6 +1,6 @@
 """Instruction mix of the two blend kernels' hot loops, counted in the ISA the compiler actually emitted (gfx950 assembly of
 ms-gs_amd/csrc/blend.hip) — the input of bench.py's issue model (roofline.valu_issue / roofline.useful_issue) instead of
-hand-counted constants.  Run by `make` after the library is linked:
+hand-counted constants.  Run by `make isa` (build() does, best effort; tests/test_isa_mix_cpu.py checks that it still works):
 
     hipcc --offload-arch=gfx950 <the library's flags> -S --cuda-device-only csrc/blend.hip -o build/blend.s
     python3 tools/isa_mix.py build/blend.s build/isa_mix.json
@@ -15,7 +15,7 @@ Classes (cycles per wave64 instruction per SIMD from tools/valu_calib.hip, profi
 
 forward  (blend_forward_kernel<false>): the innermost loop that holds the most v_exp_f32 is the entry walk; one trip evaluates
          as many entries as it has v_exp_f32 (four).  Reported per (wave, entry).
-backward (blend_backward_tile_kernel<false,false>): the innermost loop with >= 4 v_exp_f32 is the per-entry loop of the
+backward (blend_backward_tile_kernel<false, 3>): the innermost loop with >= 4 v_exp_f32 is the per-entry loop of the
          one-wave-per-tile kernel.  Its body is cut at the forward conditional branches the compiler left in place:
            quadrant   a conditionally skipped segment that holds one v_exp_f32 (one per 8x8 quadrant; averaged)
            reduction  the conditionally skipped tail that holds the DPP reduce-scatter and the atomic
@@ -119,7 +119,7 @@ def main():
                         "cycles_per_wave_entry": cycles(fwd),
                         "valu_mix": [fwd["plain"] / valu(fwd), fwd["half"] / valu(fwd), fwd["trans"] / valu(fwd)]}
 
-    a, b = kernel_range(lines, "blend_backward_tile_kernelILb0ELb0E")
+    a, b = kernel_range(lines, "blend_backward_tile_kernelILb0ELi3E")
     loops, lab = loops_of(lines, a, b)
     cand = [se for se in innermost(loops) if n_exp(lines, *se) >= 4]
     s, e = min(cand, key=lambda se: se[1] - se[0])
