@@ -325,6 +325,43 @@ int msgs_backward_with_camera(const msgs_view_t* view, const msgs_gaussians_t* g
 /* bytes of msgs_backward_with_camera's camera_scratch for P Gaussians (no clearing needed) */
 size_t msgs_camera_grad_scratch_bytes(int32_t P);
 
+/* ---- alpha map and background gradient -------------------------------------- */
+/* msgs_alpha_map: the accumulated opacity of every pixel, out_alpha [H,W] float32 = 1 - final_T, from the transmittance the
+ * forward of this view left in image_state (>= msgs_image_bytes(W, H)); one float32 subtraction per pixel, 0 where nothing was
+ * blended.  In exact arithmetic sum_i alpha_i T_i: the colour of a render with colour 1 over background 0.  Call it behind
+ * the forward that filled image_state, on the same stream (again behind a stage 2 that was run a second time). */
+int msgs_alpha_map(const msgs_view_t* view, const void* image_state, size_t image_bytes, float* out_alpha, void* stream);
+
+/* msgs_backward_with_alpha: msgs_backward_with_camera plus the gradient of the alpha map.  dL_dalpha is [H,W] float32,
+ * NULL = none — then exactly msgs_backward_with_camera (same kernels, same bits).  Non-NULL: the alpha variants of the
+ * blend-backward kernels run; G_p = dL/dA_p adds G_p T_final / (1 - alpha_i) to dL/dalpha_i (the background term with -G_p
+ * beside bg . dL/dC) and reaches opacity, conic, mean2D and everything behind them; alpha carries no colour or SH gradient.
+ * The sums, the records, the per-Gaussian kernel and every scratch size are those of the call without dL_dalpha; every mode
+ * of msgs_backward_with_camera is served (raw_params 0 / 1 / 2, accumulate, factored SH, depth, the verification mode, and
+ * adam_in_backward when no camera gradient is wanted). */
+int msgs_backward_with_alpha(const msgs_view_t* view, const msgs_gaussians_t* g,
+                             const int32_t* radii,
+                             const void* geom, size_t geom_bytes,
+                             int64_t num_instances,
+                             const void* binning, size_t binning_bytes,
+                             const void* image_state, size_t image_bytes,
+                             const float* dL_dcolor, const float* dL_ddepth, const float* dL_dalpha,
+                             void* scratch, size_t scratch_bytes,
+                             const msgs_grads_t* grads,
+                             float* dL_dviewmatrix, float* dL_dprojmatrix, float* dL_dcampos,
+                             void* camera_scratch, size_t camera_scratch_bytes,
+                             const msgs_timing_t* timing, void* stream);
+
+/* msgs_bg_grad: the gradient of the background colour, dL_dbg [3] float32 (device) = sum_p final_T_p dL/dC_{c,p} — view->bg
+ * enters every pixel as final_T bg.  image_state = NULL: final_T = 1 everywhere (a view without Gaussians, which has no image
+ * state).  Each product is rounded to float32 and added in double: one [3] row of doubles per workgroup goes to `scratch`
+ * (>= msgs_bg_grad_scratch_bytes(W, H), no clearing needed) in a partition that depends on W H alone, and a second launch adds
+ * the rows in index order — no atomics, the same bits on every run.  Independent of the backward calls: dL_dbg is always
+ * overwritten and msgs_grads_t.accumulate does not reach it. */
+size_t msgs_bg_grad_scratch_bytes(int32_t width, int32_t height);
+int msgs_bg_grad(const msgs_view_t* view, const void* image_state, size_t image_bytes, const float* dL_dcolor,
+                 float* dL_dbg, void* scratch, size_t scratch_bytes, void* stream);
+
 /* msgs_backward_per_gaussian: the per-Gaussian half of msgs_backward ALONE (2-D covariance backward, projection, SH,
  * scale / quaternion chain — upstream's computeCov2DCUDA + preprocessCUDA backward, SURVEY 2.2 K8 + K9) on per-Gaussian
  * 2-D gradients supplied by the caller instead of the blend backward's sums: sums2d [P,9] DOUBLES (device) =

@@ -704,11 +704,33 @@ int forward_stage2_impl(const msgs_view_t* view, const msgs_gaussians_t* g, cons
 }  // namespace
 
 namespace {
-// msgs_backward_with_depth (cam = NULL) and msgs_backward_with_camera
+// msgs_backward_with_depth (cam = NULL, dL_dalpha = NULL), msgs_backward_with_camera and msgs_backward_with_alpha
 int backward_impl(const msgs_view_t* view, const msgs_gaussians_t* g, const int32_t* radii, const void* geom_v,
                   size_t geom_bytes, int64_t D, const void* binning_v, size_t binning_bytes, const void* image_v,
-                  size_t image_bytes, const float* dL_dcolor, const float* dL_ddepth, void* scratch_v, size_t scratch_bytes,
-                  const msgs_grads_t* grads, const CameraGrads* cam, const msgs_timing_t* timing, void* stream);
+                  size_t image_bytes, const float* dL_dcolor, const float* dL_ddepth, const float* dL_dalpha, void* scratch_v,
+                  size_t scratch_bytes, const msgs_grads_t* grads, const CameraGrads* cam, const msgs_timing_t* timing,
+                  void* stream);
+
+// msgs_backward_with_camera (dL_dalpha = NULL) and msgs_backward_with_alpha: the camera arguments are checked in one place.
+// No camera pointer: every mode of msgs_backward_with_depth (the optimizer step in the per-Gaussian kernel included)
+int backward_camera_alpha(const msgs_view_t* view, const msgs_gaussians_t* g, const int32_t* radii, const void* geom_v,
+                          size_t geom_bytes, int64_t D, const void* binning_v, size_t binning_bytes, const void* image_v,
+                          size_t image_bytes, const float* dL_dcolor, const float* dL_ddepth, const float* dL_dalpha,
+                          void* scratch_v, size_t scratch_bytes, const msgs_grads_t* grads, float* dL_dviewmatrix,
+                          float* dL_dprojmatrix, float* dL_dcampos, void* camera_scratch, size_t camera_scratch_bytes,
+                          const msgs_timing_t* timing, void* stream) {
+    if (!dL_dviewmatrix && !dL_dprojmatrix && !dL_dcampos)
+        return backward_impl(view, g, radii, geom_v, geom_bytes, D, binning_v, binning_bytes, image_v, image_bytes, dL_dcolor,
+                             dL_ddepth, dL_dalpha, scratch_v, scratch_bytes, grads, nullptr, timing, stream);
+    int rc = check_inputs(view, g);
+    if (rc) return rc;
+    if (!grads || grads->adam_in_backward) return MSGS_ERR_INVALID_ARG;      // out of scope: refused, not silently wrong
+    if (g->P > 0 && !camera_scratch) return MSGS_ERR_INVALID_ARG;
+    if (g->P > 0 && camera_scratch_bytes < msgs_camera_grad_scratch_bytes(g->P)) return MSGS_ERR_CAPACITY;
+    CameraGrads cam{dL_dviewmatrix, dL_dprojmatrix, dL_dcampos, (double*)camera_scratch};
+    return backward_impl(view, g, radii, geom_v, geom_bytes, D, binning_v, binning_bytes, image_v, image_bytes, dL_dcolor,
+                         dL_ddepth, dL_dalpha, scratch_v, scratch_bytes, grads, &cam, timing, stream);
+}
 }  // namespace
 
 extern "C" {
@@ -726,7 +748,7 @@ int msgs_backward_with_depth(const msgs_view_t* view, const msgs_gaussians_t* g,
                              size_t image_bytes, const float* dL_dcolor, const float* dL_ddepth, void* scratch_v,
                              size_t scratch_bytes, const msgs_grads_t* grads, const msgs_timing_t* timing, void* stream) {
     return backward_impl(view, g, radii, geom_v, geom_bytes, D, binning_v, binning_bytes, image_v, image_bytes, dL_dcolor,
-                         dL_ddepth, scratch_v, scratch_bytes, grads, nullptr, timing, stream);
+                         dL_ddepth, nullptr, scratch_v, scratch_bytes, grads, nullptr, timing, stream);
 }
 
 size_t msgs_camera_grad_scratch_bytes(int32_t P) { return camera_grad_rows_bytes(P); }
@@ -737,25 +759,60 @@ int msgs_backward_with_camera(const msgs_view_t* view, const msgs_gaussians_t* g
                               size_t scratch_bytes, const msgs_grads_t* grads, float* dL_dviewmatrix, float* dL_dprojmatrix,
                               float* dL_dcampos, void* camera_scratch, size_t camera_scratch_bytes,
                               const msgs_timing_t* timing, void* stream) {
-    if (!dL_dviewmatrix && !dL_dprojmatrix && !dL_dcampos)
-        return msgs_backward_with_depth(view, g, radii, geom_v, geom_bytes, D, binning_v, binning_bytes, image_v, image_bytes,
-                                        dL_dcolor, dL_ddepth, scratch_v, scratch_bytes, grads, timing, stream);
-    int rc = check_inputs(view, g);
-    if (rc) return rc;
-    if (!grads || grads->adam_in_backward) return MSGS_ERR_INVALID_ARG;      // out of scope: refused, not silently wrong
-    if (g->P > 0 && !camera_scratch) return MSGS_ERR_INVALID_ARG;
-    if (g->P > 0 && camera_scratch_bytes < msgs_camera_grad_scratch_bytes(g->P)) return MSGS_ERR_CAPACITY;
-    CameraGrads cam{dL_dviewmatrix, dL_dprojmatrix, dL_dcampos, (double*)camera_scratch};
-    return backward_impl(view, g, radii, geom_v, geom_bytes, D, binning_v, binning_bytes, image_v, image_bytes, dL_dcolor,
-                         dL_ddepth, scratch_v, scratch_bytes, grads, &cam, timing, stream);
+    return backward_camera_alpha(view, g, radii, geom_v, geom_bytes, D, binning_v, binning_bytes, image_v, image_bytes, dL_dcolor,
+                                 dL_ddepth, nullptr, scratch_v, scratch_bytes, grads, dL_dviewmatrix, dL_dprojmatrix, dL_dcampos,
+                                 camera_scratch, camera_scratch_bytes, timing, stream);
+}
+
+// (dL_dalpha = NULL: exactly msgs_backward_with_camera — the same call)
+int msgs_backward_with_alpha(const msgs_view_t* view, const msgs_gaussians_t* g, const int32_t* radii, const void* geom_v,
+                             size_t geom_bytes, int64_t D, const void* binning_v, size_t binning_bytes, const void* image_v,
+                             size_t image_bytes, const float* dL_dcolor, const float* dL_ddepth, const float* dL_dalpha,
+                             void* scratch_v, size_t scratch_bytes, const msgs_grads_t* grads, float* dL_dviewmatrix,
+                             float* dL_dprojmatrix, float* dL_dcampos, void* camera_scratch, size_t camera_scratch_bytes,
+                             const msgs_timing_t* timing, void* stream) {
+    return backward_camera_alpha(view, g, radii, geom_v, geom_bytes, D, binning_v, binning_bytes, image_v, image_bytes, dL_dcolor,
+                                 dL_ddepth, dL_dalpha, scratch_v, scratch_bytes, grads, dL_dviewmatrix, dL_dprojmatrix, dL_dcampos,
+                                 camera_scratch, camera_scratch_bytes, timing, stream);
+}
+
+int msgs_alpha_map(const msgs_view_t* view, const void* image_v, size_t image_bytes, float* out_alpha, void* stream) {
+    if (!view || !image_v || !out_alpha || view->image_width < 1 || view->image_height < 1) return MSGS_ERR_INVALID_ARG;
+    const int W = view->image_width, H = view->image_height;
+    if (image_bytes < msgs_image_bytes(W, H)) return MSGS_ERR_CAPACITY;
+    hipStream_t s = (hipStream_t)stream;
+    const ImageLayout IL(W, H);
+    HIP_TRY(launch_alpha_map((const float*)((const char*)image_v + IL.final_T), out_alpha, (size_t)W * H, s));
+    return debug_sync(view, s);
+}
+
+size_t msgs_bg_grad_scratch_bytes(int32_t width, int32_t height) {
+    if (width < 1 || height < 1) return 0;
+    return bg_grad_rows_bytes((size_t)width * height);
+}
+
+int msgs_bg_grad(const msgs_view_t* view, const void* image_v, size_t image_bytes, const float* dL_dcolor, float* dL_dbg,
+                 void* scratch, size_t scratch_bytes, void* stream) {
+    if (!view || !dL_dcolor || !dL_dbg || !scratch || view->image_width < 1 || view->image_height < 1)
+        return MSGS_ERR_INVALID_ARG;
+    if ((uintptr_t)scratch & 7) return MSGS_ERR_INVALID_ARG;                 // rows of doubles
+    const int W = view->image_width, H = view->image_height;
+    if (image_v && image_bytes < msgs_image_bytes(W, H)) return MSGS_ERR_CAPACITY;
+    if (scratch_bytes < msgs_bg_grad_scratch_bytes(W, H)) return MSGS_ERR_CAPACITY;
+    hipStream_t s = (hipStream_t)stream;
+    const ImageLayout IL(W, H);
+    HIP_TRY(launch_bg_grad(image_v ? (const float*)((const char*)image_v + IL.final_T) : nullptr, dL_dcolor, (size_t)W * H, dL_dbg,
+                           (double*)scratch, s));
+    return debug_sync(view, s);
 }
 }  // extern "C"
 
 namespace {
 int backward_impl(const msgs_view_t* view, const msgs_gaussians_t* g, const int32_t* radii, const void* geom_v,
                   size_t geom_bytes, int64_t D, const void* binning_v, size_t binning_bytes, const void* image_v,
-                  size_t image_bytes, const float* dL_dcolor, const float* dL_ddepth, void* scratch_v, size_t scratch_bytes,
-                  const msgs_grads_t* grads, const CameraGrads* cam, const msgs_timing_t* timing, void* stream) {
+                  size_t image_bytes, const float* dL_dcolor, const float* dL_ddepth, const float* dL_dalpha, void* scratch_v,
+                  size_t scratch_bytes, const msgs_grads_t* grads, const CameraGrads* cam, const msgs_timing_t* timing,
+                  void* stream) {
     int rc = check_inputs(view, g);
     if (rc) return rc;
     if (!grads || !dL_dcolor) return MSGS_ERR_INVALID_ARG;
@@ -817,11 +874,13 @@ int backward_impl(const msgs_view_t* view, const msgs_gaussians_t* g, const int3
     if (det)      // grad_rec is the first region of the deterministic scratch layout
         HIP_TRY(launch_blend_backward_det(vp, P, geom, (const uint32_t*)(binning + BL.ids), D,
                                           (const uint2*)(binning + BL.ranges), (const float*)(image + IL.final_T),
-                                          (const uint32_t*)(image + IL.n_contrib), dL_dcolor, (char*)scratch_v, s, dL_ddepth));
+                                          (const uint32_t*)(image + IL.n_contrib), dL_dcolor, (char*)scratch_v, s, dL_ddepth,
+                                          dL_dalpha));
     else
         HIP_TRY(launch_blend_backward(vp, geom, (const uint32_t*)(binning + BL.ids), (const uint2*)(binning + BL.ranges),
                                       (const float*)(image + IL.final_T), (const uint32_t*)(image + IL.n_contrib),
-                                      dL_dcolor, grad_rec, s, (const uint32_t*)(image + IL.tile_order), dL_ddepth));
+                                      dL_dcolor, grad_rec, s, (const uint32_t*)(image + IL.tile_order), dL_ddepth,
+                                      dL_dalpha));
     tm.end(MSGS_K_BLEND_BWD);
     if ((rc = debug_sync(view, s))) return rc;
 

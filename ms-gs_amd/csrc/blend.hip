@@ -633,7 +633,10 @@ __device__ __forceinline__ void backward_walk(const uint16_t* lp, int cnt, int b
 //   [6..8] sum alpha T dL/dC_c                     with q = alpha_raw * dL/dalpha
 //   [9]    sum alpha T dL/dD  (= dL/dz; depth variant only)
 // CH = 3: the colour backward (the default); CH = 4: colour + depth (msgs_backward_with_depth), dL_ddepth [H,W] read
-template <int CH>
+// ALPHA (msgs_backward_with_alpha): a gradient G = dL/dA of the alpha map A = 1 - T_final arrives in dL_dalpha [H,W]; it adds
+// G T_final / (1 - alpha_i) to dL/dalpha_i, which is the background term with -G in the place of bg . dL/dC: an inside pixel
+// starts S at bg . dL/dC - G.  Nothing else changes (no new sum, no new record slot); ALPHA = false never reads the pointer.
+template <int CH, bool ALPHA = false>
 __global__ __launch_bounds__(256) void blend_backward_kernel(ViewParams vp, const GaussRec* __restrict__ rec,
                                                              const uint32_t* __restrict__ ids,
                                                              const uint2* __restrict__ ranges,
@@ -641,7 +644,8 @@ __global__ __launch_bounds__(256) void blend_backward_kernel(ViewParams vp, cons
                                                              const uint32_t* __restrict__ n_contrib,
                                                              const float* __restrict__ dL_dcolor,
                                                              grad_acc_t* __restrict__ grad_rec,
-                                                             const float* __restrict__ dL_ddepth) {
+                                                             const float* __restrict__ dL_ddepth,
+                                                             const float* __restrict__ dL_dalpha) {
     constexpr bool DEPTH = CH == 4;
     __shared__ float4 s_r0[BATCH], s_r1[BATCH];
     __shared__ float2 s_b[BATCH];                          // {blue, sign_test_bound}
@@ -682,6 +686,7 @@ __global__ __launch_bounds__(256) void blend_backward_kernel(ViewParams vp, cons
     // S_{i-1} = S_i + alpha_i (g_i - S_i): the three per-channel recurrences of the textbook form collapse into one
     // scalar, and starting it at bg . dL/dC absorbs the separate background term (-T_final bg.dL / (1 - alpha_i)).
     st.S = vp.bg[0] * st.dL0 + vp.bg[1] * st.dL1 + vp.bg[2] * st.dL2;
+    if constexpr (ALPHA) { if (inside) st.S -= dL_dalpha[pix]; }     // the alpha map's share (lanes outside the image do not read)
     // the nine lanes that issue the per-entry atomics (depth: ten, lane 3 delivers component 9)
     const bool alane = DEPTH ? lane < 16 && (!(lane & 2) || lane == 2 || lane == 3) : lane < 16 && (!(lane & 2) || lane == 2);
     const uint32_t aoff = DEPTH ? row_reduce_component10(lane) : row_reduce_component(lane);
@@ -717,7 +722,7 @@ __global__ __launch_bounds__(256) void blend_backward_kernel(ViewParams vp, cons
 // sub-block (lanes 0..15), WAVES per workgroup, 16 / WAVES workgroups per tile; same per-pixel arithmetic in the same order as
 // blend_backward_kernel; one atomic per (sub-block, Gaussian, component).  A workgroup walks the tile's list back from the last
 // entry ITS pixels blended.
-template <int WAVES, int SB = 4, int CH = 3>
+template <int WAVES, int SB = 4, int CH = 3, bool ALPHA = false>
 __global__ __launch_bounds__(64 * WAVES) void blend_backward_fine_kernel(ViewParams vp, const GaussRec* __restrict__ rec,
                                                              const uint32_t* __restrict__ ids,
                                                              const uint2* __restrict__ ranges,
@@ -725,7 +730,8 @@ __global__ __launch_bounds__(64 * WAVES) void blend_backward_fine_kernel(ViewPar
                                                              const uint32_t* __restrict__ n_contrib,
                                                              const float* __restrict__ dL_dcolor,
                                                              grad_acc_t* __restrict__ grad_rec,
-                                                             const float* __restrict__ dL_ddepth) {
+                                                             const float* __restrict__ dL_ddepth,
+                                                             const float* __restrict__ dL_dalpha) {
     constexpr bool DEPTH = CH == 4;
     constexpr int PER_ROW = TILE / SB, NSB = PER_ROW * PER_ROW, LANES = SB * SB;
     constexpr int T = 64 * WAVES, G = NSB / WAVES;
@@ -771,6 +777,7 @@ __global__ __launch_bounds__(64 * WAVES) void blend_backward_fine_kernel(ViewPar
     // S_{i-1} = S_i + alpha_i (g_i - S_i): the three per-channel recurrences of the textbook form collapse into one
     // scalar, and starting it at bg . dL/dC absorbs the separate background term (-T_final bg.dL / (1 - alpha_i)).
     st.S = vp.bg[0] * st.dL0 + vp.bg[1] * st.dL1 + vp.bg[2] * st.dL2;
+    if constexpr (ALPHA) { if (inside) st.S -= dL_dalpha[pix]; }     // the alpha map's share (lanes outside the image do not read)
     // the nine lanes that issue the per-entry atomics (depth: ten, lane 3 delivers component 9)
     const bool alane = DEPTH ? lane < 16 && (!(lane & 2) || lane == 2 || lane == 3) : lane < 16 && (!(lane & 2) || lane == 2);
     const uint32_t aoff = DEPTH ? row_reduce_component10(lane) : row_reduce_component(lane);
@@ -897,8 +904,9 @@ __global__ void trace_set_kernel(unsigned long long* p) { g_tile_trace = p; }
 // (tile, entry) visits, (quadrant, entry) evaluations (each 64 lanes), lanes that contributed, visits with a contribution.
 // (The verification mode — msgs_set_deterministic — does not run this kernel: literal.hip restates the reference's loop.)
 // CH = 4 (colour + depth): the depth channel of backward_walk, with z in the free slot of s_bi.  (tools/isa_mix.py finds the
-// <false, 3> instantiation by the mangled-name fragment `blend_backward_tile_kernelILb0ELi3E`: parameters added behind CH keep it.)
-template <bool COUNT = false, int CH = 3>
+// <false, 3, false> instantiation by the mangled-name fragment `blend_backward_tile_kernelILb0ELi3ELb0E`.)
+// ALPHA: see blend_backward_kernel.
+template <bool COUNT = false, int CH = 3, bool ALPHA = false>
 __global__ __launch_bounds__(64) void blend_backward_tile_kernel(ViewParams vp, const GaussRec* __restrict__ rec,
                                                                  const uint32_t* __restrict__ ids,
                                                                  const uint2* __restrict__ ranges,
@@ -907,7 +915,8 @@ __global__ __launch_bounds__(64) void blend_backward_tile_kernel(ViewParams vp, 
                                                                  const float* __restrict__ dL_dcolor,
                                                                  void* __restrict__ grad_out,
                                                                  const uint32_t* __restrict__ tile_order,
-                                                                 const float* __restrict__ dL_ddepth) {
+                                                                 const float* __restrict__ dL_ddepth,
+                                                                 const float* __restrict__ dL_dalpha) {
     constexpr bool DEPTH = CH == 4;
     __shared__ float4 s_r0[WB], s_r1[WB];
     __shared__ float4 s_bi[WB];                            // {blue, sign_test_bound, id bits, - | depth}: 16-byte stride like s_r0 /
@@ -947,6 +956,7 @@ __global__ __launch_bounds__(64) void blend_backward_tile_kernel(ViewParams vp, 
             s.dL2 = (inside && !COUNT) ? dL_dcolor[2 * N + pix] : 0.f;
             s.dLd = (DEPTH && inside) ? dL_ddepth[pix] : 0.f;
             s.S = vp.bg[0] * s.dL0 + vp.bg[1] * s.dL1 + vp.bg[2] * s.dL2;
+            if constexpr (ALPHA) { if (inside) s.S -= dL_dalpha[pix]; }
             s.T = Tf;
             return __builtin_amdgcn_readfirstlane(wave_max_u32(s.last));
         };
@@ -1269,27 +1279,30 @@ bool forward_uses_quadrant_kernel(int tiles) { return tiles > 0 && routes(tiles)
 
 hipError_t launch_blend_backward(const ViewParams& vp, const char* geom, const uint32_t* ids, const uint2* ranges,
                                  const float* final_T, const uint32_t* n_contrib, const float* dL_dcolor,
-                                 grad_acc_t* grad_rec, hipStream_t s, const uint32_t* tile_order, const float* dL_ddepth) {
+                                 grad_acc_t* grad_rec, hipStream_t s, const uint32_t* tile_order, const float* dL_ddepth,
+                                 const float* dL_dalpha) {
     const int tiles = vp.gx * vp.gy;
     if (tiles == 0) return hipSuccess;
     const GaussRec* rec = reinterpret_cast<const GaussRec*>(geom);
     const BwdRoute route = routes(tiles).bwd;
     // dL_ddepth != nullptr: the depth variants of the same three kernels (same route choice, record slot 9 = dL/dz)
-    with_bool(dL_ddepth != nullptr, [&](auto DEPTH) {
+    // dL_dalpha != nullptr: the alpha variants (msgs_backward_with_alpha), again the same three kernels and the same route
+    with_bool(dL_ddepth != nullptr, [&](auto DEPTH) { with_bool(dL_dalpha != nullptr, [&](auto ALPHA) {
         constexpr int CH = decltype(DEPTH)::value ? 4 : 3;
+        constexpr bool AL = decltype(ALPHA)::value;
         if (route == BwdRoute::Fine)
             with_fine_shape(tiles, [&](auto shape) {
                 using S = decltype(shape);
-                hipLaunchKernelGGL((blend_backward_fine_kernel<S::waves, S::sb, CH>), dim3(tiles * S::groups), dim3(64 * S::waves), 0, s,
-                                   vp, rec, ids, ranges, final_T, n_contrib, dL_dcolor, grad_rec, dL_ddepth);
+                hipLaunchKernelGGL((blend_backward_fine_kernel<S::waves, S::sb, CH, AL>), dim3(tiles * S::groups), dim3(64 * S::waves), 0, s,
+                                   vp, rec, ids, ranges, final_T, n_contrib, dL_dcolor, grad_rec, dL_ddepth, dL_dalpha);
             });
         else if (route == BwdRoute::Tile)
-            hipLaunchKernelGGL((blend_backward_tile_kernel<false, CH>), dim3(tiles), dim3(64), 0, s, vp, rec, ids, ranges, final_T,
-                               n_contrib, dL_dcolor, (void*)grad_rec, tile_order, dL_ddepth);
+            hipLaunchKernelGGL((blend_backward_tile_kernel<false, CH, AL>), dim3(tiles), dim3(64), 0, s, vp, rec, ids, ranges, final_T,
+                               n_contrib, dL_dcolor, (void*)grad_rec, tile_order, dL_ddepth, dL_dalpha);
         else
-            hipLaunchKernelGGL(blend_backward_kernel<CH>, dim3(tiles), dim3(256), 0, s, vp, rec, ids, ranges, final_T, n_contrib,
-                               dL_dcolor, grad_rec, dL_ddepth);
-    });
+            hipLaunchKernelGGL((blend_backward_kernel<CH, AL>), dim3(tiles), dim3(256), 0, s, vp, rec, ids, ranges, final_T, n_contrib,
+                               dL_dcolor, grad_rec, dL_ddepth, dL_dalpha);
+    }); });
     return hipGetLastError();
 }
 
@@ -1340,7 +1353,8 @@ DetScratch::DetScratch(int64_t P, int64_t D, int nf) {
 
 hipError_t launch_blend_backward_det(const ViewParams& vp, int P, const char* geom, const uint32_t* ids, int64_t D,
                                      const uint2* ranges, const float* final_T, const uint32_t* n_contrib,
-                                     const float* dL_dcolor, char* scratch, hipStream_t s, const float* dL_ddepth) {
+                                     const float* dL_dcolor, char* scratch, hipStream_t s, const float* dL_ddepth,
+                                     const float* dL_dalpha) {
     const int tiles = vp.gx * vp.gy;
     if (tiles == 0 || D <= 0) return hipSuccess;
     const int nf = dL_ddepth ? DET_INST_FLOATS_DEPTH : DET_INST_FLOATS;
@@ -1353,7 +1367,7 @@ hipError_t launch_blend_backward_det(const ViewParams& vp, int P, const char* ge
     hipError_t e = launch_zero(inst, sizeof(double) * nf * (size_t)D, s);
     if (e != hipSuccess) return e;
     // the reference's per-pixel backward restated literally (literal.hip): nine (ten) double sums per tile entry
-    e = launch_blend_backward_literal(vp, geom, P, ids, ranges, final_T, n_contrib, dL_dcolor, inst, s, dL_ddepth);
+    e = launch_blend_backward_literal(vp, geom, P, ids, ranges, final_T, n_contrib, dL_dcolor, inst, s, dL_ddepth, dL_dalpha);
     if (e != hipSuccess) return e;
     e = hipMemcpyAsync(keys, ids, 4 * (size_t)D, hipMemcpyDeviceToDevice, s);      // the sort clobbers its input
     if (e != hipSuccess) return e;
@@ -1382,7 +1396,7 @@ hipError_t launch_blend_backward_lane_stats(const ViewParams& vp, const char* ge
     if (tiles)
         hipLaunchKernelGGL(blend_backward_tile_kernel<true>, dim3(tiles), dim3(64), 0, s, vp,
                            reinterpret_cast<const GaussRec*>(geom), ids, ranges, final_T, n_contrib, (const float*)nullptr, (void*)out4,
-                           (const uint32_t*)nullptr, (const float*)nullptr);
+                           (const uint32_t*)nullptr, (const float*)nullptr, (const float*)nullptr);
     return hipGetLastError();
 }
 

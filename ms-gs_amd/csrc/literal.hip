@@ -104,22 +104,14 @@ __global__ __launch_bounds__(LB) void blend_forward_literal_kernel(ViewParams vp
     }
 }
 
-// 64-lane sum of a double in a fixed tree (every lane receives the total)
-__device__ __forceinline__ double wave_sum_f64(double v) {
-    for (int off = 32; off > 0; off >>= 1) {
-        const unsigned long long u = (unsigned long long)__double_as_longlong(v);
-        const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)u, off), hi = (unsigned)__shfl_xor((int)(unsigned)(u >> 32), off);
-        v += __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-    }
-    return v;
-}
-
 // The textbook backward per pixel; the nine float32 products of every (pixel, entry) pair enter DOUBLE sums over the tile's 256
 // pixels — lanes of a wave in a fixed butterfly, the four waves in order — stored at inst_grad[range.x + position][0..8].
 // DEPTH (a depth gradient, msgs_backward_with_depth): the depth map restated as a fourth channel — its own accum_rec /
 // last_color with colour z and no background term — and a tenth product dchannel_dcolor dL/dD (= dL/dz), [0..9] per entry.
+// ALPHA (a gradient G of the alpha map A = 1 - T_final, msgs_backward_with_alpha): dL/dalpha gains G T_final / (1 - alpha),
+// the background term with -G beside bg . dL/dC; G enters bg_dot last, as one float32 subtraction.
 constexpr int LBB = 32;             // entries per backward batch (4 waves x 9 doubles each in LDS)
-template <bool DEPTH>
+template <bool DEPTH, bool ALPHA = false>
 __global__ __launch_bounds__(LB) void blend_backward_literal_kernel(ViewParams vp, const GaussRec* __restrict__ rec,
                                                                     const float4* __restrict__ litrec,
                                                                     const uint32_t* __restrict__ ids,
@@ -128,7 +120,8 @@ __global__ __launch_bounds__(LB) void blend_backward_literal_kernel(ViewParams v
                                                                     const uint32_t* __restrict__ n_contrib,
                                                                     const float* __restrict__ dL_dcolor,
                                                                     double* __restrict__ inst_grad,
-                                                                    const float* __restrict__ dL_ddepth) {
+                                                                    const float* __restrict__ dL_ddepth,
+                                                                    const float* __restrict__ dL_dalpha_map) {
     constexpr int NF = DEPTH ? DET_INST_FLOATS_DEPTH : DET_INST_FLOATS;
     __shared__ float2 s_xy[LBB];
     __shared__ float4 s_con[LBB];
@@ -151,6 +144,8 @@ __global__ __launch_bounds__(LB) void blend_backward_literal_kernel(ViewParams v
     if (inside) { dL_dpixel[0] = dL_dcolor[pix]; dL_dpixel[1] = dL_dcolor[N + pix]; dL_dpixel[2] = dL_dcolor[2 * N + pix]; }
     float accum_rec[3] = {0.f, 0.f, 0.f}, last_color[3] = {0.f, 0.f, 0.f}, last_alpha = 0.f;
     const float dL_dD = (DEPTH && inside) ? dL_ddepth[pix] : 0.f;
+    float dL_dA = 0.f;                                      // (lanes outside the image do not read)
+    if constexpr (ALPHA) { if (inside) dL_dA = dL_dalpha_map[pix]; }
     float accum_rec_d = 0.f, last_depth = 0.f;
     const float ddelx_dx = 0.5f * vp.W, ddely_dy = 0.5f * vp.H;
     const float bg[3] = {vp.bg[0], vp.bg[1], vp.bg[2]};
@@ -205,6 +200,7 @@ __global__ __launch_bounds__(LB) void blend_backward_literal_kernel(ViewParams v
                         float bg_dot = 0.f;
 #pragma unroll
                         for (int c = 0; c < 3; ++c) bg_dot += bg[c] * dL_dpixel[c];
+                        if constexpr (ALPHA) bg_dot -= dL_dA;
                         dL_dalpha += (-T_final / (1.f - alpha)) * bg_dot;
                         const float dL_dG = con.w * dL_dalpha;      // Q6: through the clamp
                         const float gdx = G * dx, gdy = G * dy;
@@ -251,15 +247,15 @@ hipError_t launch_blend_forward_literal(const ViewParams& vp, const char* geom, 
 
 hipError_t launch_blend_backward_literal(const ViewParams& vp, const char* geom, int P, const uint32_t* ids, const uint2* ranges,
                                          const float* final_T, const uint32_t* n_contrib, const float* dL_dcolor, double* inst_grad,
-                                         hipStream_t s, const float* dL_ddepth) {
+                                         hipStream_t s, const float* dL_ddepth, const float* dL_dalpha) {
     const int tiles = vp.gx * vp.gy;
     if (tiles == 0) return hipSuccess;
     const GeomLayout L(P > 0 ? P : 1);
-    with_bool(dL_ddepth != nullptr, [&](auto DEPTH) {
-        hipLaunchKernelGGL(blend_backward_literal_kernel<decltype(DEPTH)::value>, dim3(tiles), dim3(LB), 0, s, vp,
-                           reinterpret_cast<const GaussRec*>(geom + L.rec), reinterpret_cast<const float4*>(geom + L.litrec), ids,
-                           ranges, final_T, n_contrib, dL_dcolor, inst_grad, dL_ddepth);
-    });
+    with_bool(dL_ddepth != nullptr, [&](auto DEPTH) { with_bool(dL_dalpha != nullptr, [&](auto ALPHA) {
+        hipLaunchKernelGGL((blend_backward_literal_kernel<decltype(DEPTH)::value, decltype(ALPHA)::value>), dim3(tiles), dim3(LB), 0, s,
+                           vp, reinterpret_cast<const GaussRec*>(geom + L.rec), reinterpret_cast<const float4*>(geom + L.litrec), ids,
+                           ranges, final_T, n_contrib, dL_dcolor, inst_grad, dL_ddepth, dL_dalpha);
+    }); });
     return hipGetLastError();
 }
 

@@ -301,6 +301,16 @@ struct ImageLayout {
 // ---------------------------------------------------------------------------------------------
 // device helpers
 // ---------------------------------------------------------------------------------------------
+// 64-lane sum of a double in a fixed butterfly: every lane receives the total, the same bits on every run (the deterministic
+// reductions of literal.hip, the camera-gradient rows of preprocess.hip and the background gradient of alpha.hip)
+__device__ __forceinline__ double wave_sum_f64(double v) {
+    for (int off = 32; off > 0; off >>= 1) {
+        const unsigned long long u = (unsigned long long)__double_as_longlong(v);
+        const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)u, off), hi = (unsigned)__shfl_xor((int)(unsigned)(u >> 32), off);
+        v += __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+    }
+    return v;
+}
 // One Adam step of ONE float, term by term torch.optim.Adam's single-tensor formulation (torch/optim/adam.py,
 // _single_tensor_adam; amsgrad = False, weight_decay = 0, maximize = False) with the roundings of the ATen kernels:
 //     m <- fma(1 - beta1, g - m, m)                      (Tensor.lerp_, weight < 0.5 branch)
@@ -624,7 +634,8 @@ hipError_t launch_blend_forward_literal(const ViewParams& vp, const char* geom, 
                                         uint32_t* order_flag, hipStream_t s);
 hipError_t launch_blend_backward_literal(const ViewParams& vp, const char* geom, int P, const uint32_t* ids, const uint2* ranges,
                                          const float* final_T, const uint32_t* n_contrib, const float* dL_dcolor, double* inst_grad,
-                                         hipStream_t s, const float* dL_ddepth = nullptr);
+                                         hipStream_t s, const float* dL_ddepth = nullptr,
+                                         const float* dL_dalpha = nullptr);   // non-null: + the alpha map's gradient [H,W]
 hipError_t launch_sh_grad_from_views(int P, int n_views, int deg, const float* means3D, const float* campos,
                                      int64_t campos_stride, const float* drgb, int64_t drgb_stride, float scale,
                                      float* d_dc, float* d_rest, hipStream_t s);
@@ -698,7 +709,14 @@ struct DetScratch {
 };
 hipError_t launch_blend_backward_det(const ViewParams& vp, int P, const char* geom, const uint32_t* ids, int64_t D,
                                      const uint2* ranges, const float* final_T, const uint32_t* n_contrib,
-                                     const float* dL_dcolor, char* scratch, hipStream_t s, const float* dL_ddepth = nullptr);
+                                     const float* dL_dcolor, char* scratch, hipStream_t s, const float* dL_ddepth = nullptr,
+                                     const float* dL_dalpha = nullptr);
+
+// alpha.hip: the alpha map A = 1 - final_T and the background colour's gradient (two launches, no atomics)
+hipError_t launch_alpha_map(const float* final_T, float* out_alpha, size_t N, hipStream_t s);
+size_t bg_grad_rows_bytes(size_t N);     // one [3] double row per workgroup of launch 1
+hipError_t launch_bg_grad(const float* final_T /* nullable: T = 1 */, const float* dL_dcolor, size_t N, float* dL_dbg,
+                          double* rows, hipStream_t s);
 
 // epilogue.hip
 hipError_t launch_adam(const msgs_adam_tensor_t* tensors, int n, int64_t step, double beta1, double beta2, double eps,
@@ -751,7 +769,8 @@ hipError_t launch_forward_feedback(const unsigned long long* dtrav, const SlabHe
 hipError_t launch_blend_backward(const ViewParams& vp, const char* geom, const uint32_t* ids, const uint2* ranges,
                                  const float* final_T, const uint32_t* n_contrib, const float* dL_dcolor,
                                  grad_acc_t* grad_rec, hipStream_t s, const uint32_t* tile_order = nullptr,
-                                 const float* dL_ddepth = nullptr);   // non-null: the depth variants (record slot 9 = dL/dz)
+                                 const float* dL_ddepth = nullptr,    // non-null: the depth variants (record slot 9 = dL/dz)
+                                 const float* dL_dalpha = nullptr);   // non-null: the alpha variants (S starts at bg.dL/dC - dL/dA)
 // heaviest-first launch order of the one-wave-per-tile backward from the forward's per-tile traversal lengths
 hipError_t launch_tile_order(const ViewParams& vp, const uint32_t* tile_last, uint32_t* tile_order, hipStream_t s);
 hipError_t launch_blend_lane_stats(const ViewParams& vp, const char* geom, const uint32_t* ids, const uint2* ranges,

@@ -724,16 +724,6 @@ __device__ __forceinline__ float (&camera_dir_lds())[3][256] {
     return s;
 }
 
-// sum over the 64 lanes in a fixed butterfly (every lane ends with the same bits)
-__device__ __forceinline__ double wave_sum_f64(double v) {
-    for (int off = 32; off > 0; off >>= 1) {
-        const unsigned long long u = (unsigned long long)__double_as_longlong(v);
-        const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)u, off), hi = (unsigned)__shfl_xor((int)(unsigned)(u >> 32), off);
-        v += __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-    }
-    return v;
-}
-
 // (held to 96 registers = 5 waves per SIMD: measured 116 us with the compiler's 102 registers / 4 waves, 112 us with 5 waves and
 //  one spilled register, 125 us with 6 waves and 22 spills; 121 us before the rows were staged in two runs)
 // TEXTBOOK = true (msgs_backward_per_gaussian, the K8 + K9 isolation entry of the parity tests): grad_rec is NOT this

@@ -282,6 +282,27 @@ def _call_backward(lib, call, ctx, geom, binning, image, D, dL, dL_ddepth, scrat
         _C.check(lib.msgs_backward_with_depth(*args, _ptr(dL_ddepth), *tail), "msgs_backward_with_depth")
 
 
+def _call_backward_with_alpha(lib, call, ctx, geom, binning, image, D, dL, dL_ddepth, dL_dalpha, scratch, grads, stream,
+                              camera=None):
+    """msgs_backward_with_alpha: the loss used the alpha map (dL_dalpha: contiguous float32 [H,W]); depth and camera gradients
+    as in _call_backward"""
+    cs = camera.scratch if camera is not None else None
+    cam = (camera.dV, camera.dPM, camera.dcp) if camera is not None else (None, None, None)
+    _C.check(lib.msgs_backward_with_alpha(call.view_ref, call.g_ref, _ptr(ctx.radii), _ptr(geom), geom.numel(), D, _ptr(binning),
+                                          binning.numel(), _ptr(image), image.numel(), _ptr(dL), _ptr(dL_ddepth), _ptr(dL_dalpha),
+                                          _ptr(scratch), scratch.numel(), C.byref(grads), _ptr(cam[0]), _ptr(cam[1]), _ptr(cam[2]),
+                                          _ptr(cs), cs.numel() if cs is not None else 0, _C.timer_ptr(), stream),
+             "msgs_backward_with_alpha")
+
+
+def _run_backward(lib, call, ctx, geom, binning, image, D, dL, dLd, dLa, scratch, grads, stream, cam):
+    """today's entry (_call_backward) unless the loss used the alpha map"""
+    if dLa is None:
+        _call_backward(lib, call, ctx, geom, binning, image, D, dL, dLd, scratch, grads, stream, cam)
+    else:
+        _call_backward_with_alpha(lib, call, ctx, geom, binning, image, D, dL, dLd, dLa, scratch, grads, stream, cam)
+
+
 # Camera gradients (DESIGN.md 2, M8).  autograd does not look inside the settings NamedTuple, so when grad mode is on and
 # one of its viewmatrix / projmatrix / campos requires grad, those three tensors also go to the autograd Function as extra
 # trailing inputs; the backward then returns their gradients (in each tensor's own shape, dtype and device).  Otherwise
@@ -293,13 +314,73 @@ def _camera_inputs(rs):
     return cam if any(torch.is_tensor(t) and t.requires_grad for t in cam) else ()
 
 
-def _note_camera(ctx, camera):
-    """forward: which camera inputs want a gradient (ctx.camera: () or three (shape, dtype, device) | None)"""
+def _note_camera(ctx, camera, behind=0):
+    """forward: which camera inputs want a gradient (ctx.camera: () or three (shape, dtype, device) | None); `behind`: the
+    number of trailing inputs that follow the camera's three (_extra_inputs)"""
     if not camera:
         ctx.camera = ()
         return
-    want = ctx.needs_input_grad[-3:]
+    n = len(ctx.needs_input_grad) - behind
+    want = ctx.needs_input_grad[n - 3:n]
     ctx.camera = tuple((t.shape, t.dtype, t.device) if w else None for t, w in zip(camera, want))
+
+
+# Alpha map and background gradient (DESIGN.md 2, M9).  The trailing inputs of the three autograd Functions are, in this order,
+#   [viewmatrix, projmatrix, campos]   _camera_inputs: three tensors or nothing
+#   [bg]                               grad mode on and settings.bg requires grad: the background colour, for its gradient
+#   [_ALPHA]                           return_alpha=True: a marker (not a tensor) — the Function returns alpha as a sixth output
+# A call that asks for neither new thing passes exactly what it passed before them.
+class _AlphaMarker:
+    def __repr__(self):
+        return "return_alpha"
+
+
+_ALPHA = _AlphaMarker()
+
+
+def _extra_inputs(rs, return_alpha=False):
+    extra = _camera_inputs(rs)
+    if torch.is_grad_enabled() and torch.is_tensor(rs.bg) and rs.bg.requires_grad:
+        extra = tuple(extra) + (rs.bg,)
+    return tuple(extra) + (_ALPHA,) if return_alpha else extra
+
+
+def _note_extra(ctx, extra):
+    """forward: split the trailing inputs; leaves ctx.camera (_note_camera), ctx.bg ((shape, dtype, device) when the
+    background wants a gradient, else None), ctx.n_extra_tail (inputs behind the camera's) and returns return_alpha"""
+    alpha = bool(extra) and extra[-1] is _ALPHA
+    rest = extra[:-1] if alpha else extra
+    bg = rest[-1] if len(rest) in (1, 4) else None
+    camera = rest[:3] if len(rest) >= 3 else ()
+    ctx.n_extra_tail = len(extra) - len(camera)
+    ctx.has_bg = bg is not None
+    ctx.bg = None
+    if bg is not None and ctx.needs_input_grad[len(ctx.needs_input_grad) - 1 - int(alpha)]:
+        ctx.bg = (bg.shape, bg.dtype, bg.device)
+    _note_camera(ctx, camera, ctx.n_extra_tail)
+    ctx.return_alpha = alpha
+    return camera, alpha
+
+
+def _alpha_map(call, image, alpha, stream):
+    """alpha = 1 - final_T of the image state, on `stream` behind the forward that wrote it"""
+    _C.check(_C.lib.msgs_alpha_map(call.view_ref, _ptr(image), image.numel(), _ptr(alpha), stream), "msgs_alpha_map")
+
+
+def _bg_grad(ctx, view_ref, image, dL, W, H, dev, stream):
+    """dL/dbg in the background tensor's own shape, dtype and device (msgs_bg_grad: two launches, independent of the backward
+    call); image None: a view without Gaussians (final_T = 1)"""
+    shape, dtype, device = ctx.bg
+    out = torch.empty(3, dtype=torch.float32, device=dev)
+    scratch = _bytes(_C.lib.msgs_bg_grad_scratch_bytes(W, H), dev)
+    _C.check(_C.lib.msgs_bg_grad(view_ref, _ptr(image), image.numel() if image is not None else 0, _ptr(dL), _ptr(out),
+                                 _ptr(scratch), scratch.numel(), stream), "msgs_bg_grad")
+    return out.view(shape).to(device=device, dtype=dtype)
+
+
+def _extra_grads(ctx, g_cam, g_bg):
+    """gradients of the trailing inputs in their order: camera, bg, the alpha marker"""
+    return tuple(g_cam) + ((g_bg,) if ctx.has_bg else ()) + ((None,) if ctx.return_alpha else ())
 
 
 def _refuse_camera_with(camera):
@@ -528,7 +609,7 @@ def _stage2_bytes(D, W, H, frac):
     return int(lib.msgs_binning_bytes(D, W, H)), int(lib.msgs_stage2_scratch_bytes(D, W, H))
 
 
-def _redo_stage2(call, geom, image, D, frac, outs, grad_rec, backward_follows, stream):
+def _redo_stage2(call, geom, image, D, frac, outs, grad_rec, backward_follows, stream, alpha=None):
     """Stage 2 again, on buffers sized for the instance count D, when the speculative one did not serve it (first frame of this
     shape, or the scene grew past the margin); returns the new binning buffer.  The outputs are overwritten in place.
 
@@ -546,6 +627,8 @@ def _redo_stage2(call, geom, image, D, frac, outs, grad_rec, backward_follows, s
                                         _ptr(image), image.numel(), _ptr(color), _ptr(acc_ps), _ptr(depth),
                                         _ptr(grad_rec), grad_rec.numel() if grad_rec is not None else 0,
                                         int(backward_follows), _C.timer_ptr(), stream), "msgs_forward_stage2")
+    if alpha is not None:                  # final_T was overwritten: the alpha map again, behind it on the same stream
+        _alpha_map(call, image, alpha, stream)
     return binning
 
 
@@ -606,8 +689,9 @@ class _PendingForward:
     """State of one launched forward: resolve() -> (geom, binning, image, D), waiting for the count if nobody has yet."""
 
     def __init__(self, call, status, stream, key, guess, geom, binning, image, outs, grad_rec, keep, backward_follows=False,
-                 scratch1=None):
+                 scratch1=None, alpha=None):
         self.backward_follows = bool(backward_follows)
+        self.alpha = alpha                    # the alpha map of a return_alpha call: rewritten behind a redo of stage 2
         self.scratch1 = scratch1              # holds the device status words msgs_forward_finish may still copy from
         self.call, self.status, self.stream, self.key, self.guess = call, status, stream, key, guess
         self.geom, self.binning, self.image, self.outs, self.grad_rec, self.keep = geom, binning, image, outs, grad_rec, keep
@@ -637,9 +721,10 @@ class _PendingForward:
                 self.error = RuntimeError("stage 2 on exact buffers failed")     # cleared below
                 with _on_device(call.device), torch.cuda.stream(self.stream):
                     self.binning = _redo_stage2(call, self.geom, self.image, D, float(call.view.slab_fraction), self.outs,
-                                                self.grad_rec, self.backward_follows, C.c_void_p(self.stream.cuda_stream))
+                                                self.grad_rec, self.backward_follows, C.c_void_p(self.stream.cuda_stream),
+                                                self.alpha)
             self.state = (self.geom, self.binning, self.image, D)
-            self.outs = self.grad_rec = self.error = None
+            self.outs = self.grad_rec = self.error = self.alpha = None
             return self.state
 
     def abandon(self):
@@ -655,7 +740,8 @@ def _resolve(state):
     return state.resolve() if isinstance(state, _PendingForward) else state
 
 
-def _forward_impl(call, grad_rec=None, backward_follows=False):
+def _forward_impl(call, grad_rec=None, backward_follows=False, want_alpha=False):
+    """-> (color, acc_ps, depth, radii, pixel_sizes, state); with want_alpha the alpha map sits in front of `state`"""
     dev, P, W, H = call.device, call.P, call.W, call.H
     lib = _C.lib
     key = (dev.index, P, W, H, call.view.filter_small, call.view.filter_large)
@@ -673,6 +759,7 @@ def _forward_impl(call, grad_rec=None, backward_follows=False):
         color = torch.empty(3, H, W, dtype=torch.float32, device=dev)
         acc_ps = torch.empty(H, W, dtype=torch.float32, device=dev)
         depth = torch.empty(H, W, dtype=torch.float32, device=dev)
+        alpha = torch.empty(H, W, dtype=torch.float32, device=dev) if want_alpha else None
         n_geom, n_s1, n_img = _sizes(P, W, H)
         guess = _instance_guess(key)
         # two allocations instead of five: what the backward needs again (geom | image | binning) and what dies with the
@@ -704,8 +791,11 @@ def _forward_impl(call, grad_rec=None, backward_follows=False):
                 _give_status(status)
                 raise
             state = _PendingForward(call, status, cur, key, guess, geom, binning, image, (color, acc_ps, depth), grad_rec, keep,
-                                    backward_follows, scratch1)
+                                    backward_follows, scratch1, alpha)
             pending.append(state)
+            if want_alpha:                    # valid in stream order like the other outputs (resolve() rewrites it behind a redo)
+                _alpha_map(call, image, alpha, stream)
+                return color, acc_ps, depth, radii, pixel_sizes, alpha, state
             return color, acc_ps, depth, radii, pixel_sizes, state
         tmp = _bytes(_a256(n_s1) + n_s2, dev)
         scratch1 = tmp[:n_s1]
@@ -722,23 +812,26 @@ def _forward_impl(call, grad_rec=None, backward_follows=False):
         _note_count(key, D, guess, done.value)
         if not done.value:
             binning = _redo_stage2(call, geom, image, D, frac, (color, acc_ps, depth), grad_rec, backward_follows, stream)
+        if want_alpha:
+            _alpha_map(call, image, alpha, stream)
+            return color, acc_ps, depth, radii, pixel_sizes, alpha, (geom, binning, image, D)
     return color, acc_ps, depth, radii, pixel_sizes, (geom, binning, image, D)
 
 
 def _forward_tail(ctx, call, state, outs):
-    """the end of every autograd forward: what its backward finds on ctx; returns the five outputs"""
-    color, acc_ps, depth, radii, pixel_sizes = outs
+    """the end of every autograd forward: what its backward finds on ctx; returns the five outputs (six with return_alpha)"""
+    color, acc_ps, depth, radii, pixel_sizes = outs[:5]
     ctx.call, ctx.state, ctx.radii = call, state, radii
-    ctx.mark_non_differentiable(acc_ps, radii, pixel_sizes)     # depth is differentiable (DESIGN.md 2, M6)
-    ctx.set_materialize_grads(False)      # grad_depth is None unless the loss used the depth map: then the colour-only path
+    ctx.mark_non_differentiable(acc_ps, radii, pixel_sizes)     # depth and alpha are differentiable (DESIGN.md 2, M6, M9)
+    ctx.set_materialize_grads(False)      # grad_depth / grad_alpha are None unless the loss used that map: then today's path
     return tuple(outs)
 
 
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                max_pixel_sizes, min_pixel_sizes, occ_multiplier, dc_delta, base_mask, raster_settings, *camera):
-        _note_camera(ctx, camera)
+                max_pixel_sizes, min_pixel_sizes, occ_multiplier, dc_delta, base_mask, raster_settings, *extra):
+        camera, want_alpha = _note_extra(ctx, extra)
         if means3D.shape[0] == 0:
             # nothing to rasterize: background image, no native call (every per-Gaussian tensor is empty,
             # which upstream's convention cannot tell apart from "not provided")
@@ -752,25 +845,37 @@ class _RasterizeGaussians(torch.autograd.Function):
             ctx.in_shapes = [t.shape for t in (means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
                                                cov3Ds_precomp)]
             ctx.dev = dev
+            ctx.HW = (H, W, int(bool(rs.debug)))
             outs = (color, torch.zeros(H, W, device=dev), torch.zeros(H, W, device=dev),
                     torch.zeros(0, dtype=torch.int32, device=dev), torch.zeros(0, device=dev))
             ctx.mark_non_differentiable(outs[1], *outs[3:])     # (depth stays differentiable: zero gradients)
+            if want_alpha:                                      # (nothing blended: alpha 0, zero gradients)
+                outs = outs + (torch.zeros(H, W, device=dev),)
             ctx.set_materialize_grads(False)
             return outs
         ctx.empty = False
         call = _Call(raster_settings, means3D, _opt(sh), _opt(colors_precomp), opacities, _opt(scales),
                      _opt(rotations), _opt(cov3Ds_precomp), _opt(max_pixel_sizes), _opt(min_pixel_sizes),
                      _opt(occ_multiplier), _opt(dc_delta), _opt(base_mask))
-        *outs, state = _forward_impl(call, _alloc_grad_records(ctx, call.P, call.device), ctx.backward_follows)
+        *outs, state = _forward_impl(call, _alloc_grad_records(ctx, call.P, call.device), ctx.backward_follows, want_alpha)
         ctx.shapes = (means2D.shape, opacities.shape)
         _save_inputs(ctx, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp)
         return _forward_tail(ctx, call, state, outs)
 
     @staticmethod
-    def backward(ctx, grad_color, grad_acc_ps, grad_depth, grad_radii, grad_pixel_sizes):
+    def backward(ctx, grad_color, grad_acc_ps, grad_depth, grad_radii, grad_pixel_sizes, grad_alpha=None):
         if ctx.empty:
             cam = tuple(None if m is None else torch.zeros(m[0], dtype=m[1], device=m[2]) for m in ctx.camera)
-            return tuple(torch.zeros(s, device=ctx.dev) for s in ctx.in_shapes) + (None,) * 6 + cam
+            g_bg = None
+            if ctx.bg is not None:          # the image is the background: dL/dbg_c = sum_p dL/dC_{c,p} (final_T = 1)
+                H, W, debug = ctx.HW
+                if grad_color is None:
+                    grad_color = torch.zeros(3, H, W, dtype=torch.float32, device=ctx.dev)
+                view = _C.View(H, W, 1.0, 1.0, 1.0, 1.0, 0, 0, 0, 0, 0, debug, 0, 0, 0.0, 0, None, None, None, None)
+                with _on_device(ctx.dev):
+                    stream = C.c_void_p(torch.cuda.current_stream(ctx.dev).cuda_stream)
+                    g_bg = _bg_grad(ctx, C.byref(view), None, _f32c(grad_color), W, H, ctx.dev, stream)
+            return tuple(torch.zeros(s, device=ctx.dev) for s in ctx.in_shapes) + (None,) * 6 + _extra_grads(ctx, cam, g_bg)
         _check_saved(ctx)
         call = ctx.call
         if grad_color is None:
@@ -794,12 +899,14 @@ class _RasterizeGaussians(torch.autograd.Function):
             grads = _C.Grads(_ptr(g_means3D), _ptr(g_means2D), _ptr(g_sh), _ptr(g_col), _ptr(g_opac),
                              _ptr(g_scales), _ptr(g_rot), _ptr(g_cov), None, None, None, is_clear)
             cam = _CameraGrads(ctx, P, dev) if ctx.camera else None
-            _call_backward(lib, call, ctx, geom, binning, image, D, dL, dLd, scratch, grads, stream, cam)
+            dLa = _f32c(grad_alpha) if grad_alpha is not None else None
+            _run_backward(lib, call, ctx, geom, binning, image, D, dL, dLd, dLa, scratch, grads, stream, cam)
+            g_bg = _bg_grad(ctx, call.view_ref, image, dL, call.W, call.H, dev, stream) if ctx.bg is not None else None
         m2_shape, op_shape = ctx.shapes
         # occ_multiplier / dc_delta / pixel-size inputs / masks receive no gradient (DESIGN.md SPEC M5)
         return (g_means3D, g_means2D.view(m2_shape) if g_means2D.shape == m2_shape else g_means2D,
                 g_sh, g_col, g_opac.view(op_shape), g_scales, g_rot, g_cov,
-                None, None, None, None, None, None) + (cam.grads(ctx) if cam is not None else ())
+                None, None, None, None, None, None) + _extra_grads(ctx, cam.grads(ctx) if cam is not None else (), g_bg)
 
 
 # Gradient sinks (view-parallel training): a trainer that exchanges gradients through one flat bucket registers, per leaf
@@ -987,22 +1094,22 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, xyz, means2D, features_dc, features_rest, opacity_raw, scaling_raw, rotation_raw,
-                max_pixel_sizes, min_pixel_sizes, occ_multiplier, dc_delta, base_mask, raster_settings, *camera):
+                max_pixel_sizes, min_pixel_sizes, occ_multiplier, dc_delta, base_mask, raster_settings, *extra):
         if xyz.shape[0] == 0:
             raise ValueError("rasterize_gaussians_raw: empty model")
+        camera, want_alpha = _note_extra(ctx, extra)
         _refuse_camera_with(camera)
-        _note_camera(ctx, camera)
         call = _Call(raster_settings, xyz, None, None, opacity_raw, scaling_raw, rotation_raw, None,
                      _opt(max_pixel_sizes), _opt(min_pixel_sizes), _opt(occ_multiplier), _opt(dc_delta),
                      _opt(base_mask), raw_features=(features_dc, features_rest))
-        *outs, state = _forward_impl(call, _alloc_grad_records(ctx, call.P, call.device), ctx.backward_follows)
+        *outs, state = _forward_impl(call, _alloc_grad_records(ctx, call.P, call.device), ctx.backward_follows, want_alpha)
         ctx.shapes = (means2D.shape, features_dc.shape, features_rest.shape, opacity_raw.shape)
         _snapshot_sinks(ctx, (xyz, features_dc, features_rest, opacity_raw, scaling_raw, rotation_raw))
         _save_inputs(ctx, xyz, features_dc, features_rest, opacity_raw, scaling_raw, rotation_raw)
         return _forward_tail(ctx, call, state, outs)
 
     @staticmethod
-    def backward(ctx, grad_color, grad_acc_ps, grad_depth, grad_radii, grad_pixel_sizes):
+    def backward(ctx, grad_color, grad_acc_ps, grad_depth, grad_radii, grad_pixel_sizes, grad_alpha=None):
         _check_saved(ctx)
         call = ctx.call
         if grad_color is None:
@@ -1050,10 +1157,12 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
                              C.c_void_p(ready.cuda_event) if (factor is not None and ready is not None) else None,
                              is_clear, acc_flag, ev_wait, ev_rec, C.addressof(adam) if adam is not None else None)
             cam = _CameraGrads(ctx, P, dev) if ctx.camera else None
-            _call_backward(lib, call, ctx, geom, binning, image, D, dL, dLd, scratch, grads, stream, cam)
+            dLa = _f32c(grad_alpha) if grad_alpha is not None else None
+            _run_backward(lib, call, ctx, geom, binning, image, D, dL, dLd, dLa, scratch, grads, stream, cam)
             if adam is not None:
                 step_opt.commit_step_in_backward(ctx.leaves)
-        g_cam = cam.grads(ctx) if cam is not None else ()
+            g_bg = _bg_grad(ctx, call.view_ref, image, dL, call.W, call.H, dev, stream) if ctx.bg is not None else None
+        g_cam = _extra_grads(ctx, cam.grads(ctx) if cam is not None else (), g_bg)
         if accum is not None or adam is not None:   # the leaf gradients live in the accumulator / were consumed by the step
             return (None, g_m2.view(m2_shape), None, None, None, None, None, None, None, None, None, None, None) + g_cam
         return (g_xyz, g_m2.view(m2_shape), g_dc, g_rest, g_opac, g_scal, g_rot, None, None, None, None, None, None) + g_cam
@@ -1069,13 +1178,13 @@ class _RasterizeGaussiansChained(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xyz, means2D, features_dc, features_rest, opacity_raw, scaling_raw, rotation_raw,
                 shs, opacities, scales, rotations, max_pixel_sizes, min_pixel_sizes, occ_multiplier, dc_delta, base_mask,
-                raster_settings, *camera):
+                raster_settings, *extra):
+        camera, want_alpha = _note_extra(ctx, extra)
         _refuse_camera_with(camera)
-        _note_camera(ctx, camera)
         call = _Call(raster_settings, xyz, _opt(shs), None, opacities, scales, rotations, None,
                      _opt(max_pixel_sizes), _opt(min_pixel_sizes), _opt(occ_multiplier), _opt(dc_delta),
                      _opt(base_mask), raw_features=(features_dc, features_rest), rotations_raw=rotation_raw)
-        *outs, state = _forward_impl(call, _alloc_grad_records(ctx, call.P, call.device), ctx.backward_follows)
+        *outs, state = _forward_impl(call, _alloc_grad_records(ctx, call.P, call.device), ctx.backward_follows, want_alpha)
         ctx.shapes = (means2D.shape, features_dc.shape, features_rest.shape, opacity_raw.shape)
         _snapshot_sinks(ctx, (xyz, features_dc, features_rest, opacity_raw, scaling_raw, rotation_raw))
         _save_inputs(ctx, xyz, features_dc, features_rest, opacity_raw, scaling_raw, rotation_raw, shs, opacities,
@@ -1083,9 +1192,9 @@ class _RasterizeGaussiansChained(torch.autograd.Function):
         return _forward_tail(ctx, call, state, outs)
 
     @staticmethod
-    def backward(ctx, grad_color, grad_acc_ps, grad_depth, grad_radii, grad_pixel_sizes):
-        g = _RasterizeGaussiansRaw.backward(ctx, grad_color, grad_acc_ps, grad_depth, grad_radii, grad_pixel_sizes)
-        return g[:7] + (None,) * 10 + g[13:]            # (camera gradients, when asked for, at the end)
+    def backward(ctx, grad_color, grad_acc_ps, grad_depth, grad_radii, grad_pixel_sizes, grad_alpha=None):
+        g = _RasterizeGaussiansRaw.backward(ctx, grad_color, grad_acc_ps, grad_depth, grad_radii, grad_pixel_sizes, grad_alpha)
+        return g[:7] + (None,) * 10 + g[13:]            # (the trailing inputs' gradients — camera, bg, alpha marker — at the end)
 
 
 # Recognition of the reference's getters (scene/gaussian_model.py:127-153) in the autograd graph of the arguments of
@@ -1172,25 +1281,32 @@ def sh_grad_from_views(means3D, gathered, n_views, sh_degree, scale, out_dc, out
 
 
 def rasterize_gaussians_raw(xyz, means2D, features_dc, features_rest, opacity_raw, scaling_raw, rotation_raw,
-                            max_pixel_sizes, min_pixel_sizes, occ_multiplier, dc_delta, base_mask, raster_settings):
+                            max_pixel_sizes, min_pixel_sizes, occ_multiplier, dc_delta, base_mask, raster_settings,
+                            return_alpha=False):
+    """return_alpha=True: a sixth output, the alpha map [H,W] (1 - final transmittance), differentiable"""
     _note_grad_mode()
     return _RasterizeGaussiansRaw.apply(xyz, means2D, features_dc, features_rest, opacity_raw, scaling_raw,
                                         rotation_raw, max_pixel_sizes, min_pixel_sizes, occ_multiplier, dc_delta,
-                                        base_mask, raster_settings, *_camera_inputs(raster_settings))
+                                        base_mask, raster_settings, *_extra_inputs(raster_settings, return_alpha))
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                        max_pixel_sizes, min_pixel_sizes, occ_multiplier, dc_delta, base_mask, raster_settings):
+                        max_pixel_sizes, min_pixel_sizes, occ_multiplier, dc_delta, base_mask, raster_settings,
+                        return_alpha=False):
+    """return_alpha=True: a sixth output, the alpha map [H,W] (1 - final transmittance), differentiable"""
     _note_grad_mode()
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
                                      cov3Ds_precomp, max_pixel_sizes, min_pixel_sizes, occ_multiplier, dc_delta,
-                                     base_mask, raster_settings, *_camera_inputs(raster_settings))
+                                     base_mask, raster_settings, *_extra_inputs(raster_settings, return_alpha))
 
 
 class GaussianRasterizer(nn.Module):
-    def __init__(self, raster_settings):
+    def __init__(self, raster_settings, return_alpha=False):
+        """return_alpha=True: forward / forward_raw return the 6-tuple (color, acc_pixel_size, depth, radii, pixel_sizes, alpha)
+        with alpha [H,W] float32 = 1 - final transmittance, differentiable; default: the reference's 5-tuple"""
         super().__init__()
         self.raster_settings = raster_settings
+        self.return_alpha = bool(return_alpha)
 
     def markVisible(self, positions):
         """Boolean mask of points in front of the near plane (upstream markVisible; unused by the
@@ -1242,7 +1358,7 @@ class GaussianRasterizer(nn.Module):
         o = lambda t: t if t is not None else empty
         return rasterize_gaussians_raw(xyz, means2D, features_dc, features_rest, opacity_raw, scaling_raw,
                                        rotation_raw, o(max_pixel_sizes), o(min_pixel_sizes), o(occ_multiplier),
-                                       o(dc_delta), o(base_mask), self.raster_settings)
+                                       o(dc_delta), o(base_mask), self.raster_settings, self.return_alpha)
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
                 cov3D_precomp=None, max_pixel_sizes=None, min_pixel_sizes=None, occ_multiplier=None,
@@ -1273,7 +1389,7 @@ class GaussianRasterizer(nn.Module):
                     means3D, means2D, *leaves, shs.detach() if _chain_reads_cat else empty, opacities.detach(), scales.detach(),
                     rotations.detach(),
                     o(max_pixel_sizes), o(min_pixel_sizes), o(occ_multiplier), o(dc_delta), o(base_mask), rs,
-                    *_camera_inputs(rs))
+                    *_extra_inputs(rs, self.return_alpha))
         return rasterize_gaussians(
             means3D, means2D,
             shs if shs is not None else empty,
@@ -1287,4 +1403,4 @@ class GaussianRasterizer(nn.Module):
             occ_multiplier if occ_multiplier is not None else empty,
             dc_delta if dc_delta is not None else empty,
             base_mask if base_mask is not None else empty,
-            rs)
+            rs, self.return_alpha)

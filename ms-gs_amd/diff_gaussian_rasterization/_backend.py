@@ -184,6 +184,15 @@ def _load():
                                               vp, vp, vp, sz, C.POINTER(Grads), vp, vp, vp, vp, sz, C.POINTER(Timing), vp]
     lib.msgs_camera_grad_scratch_bytes.restype = sz
     lib.msgs_camera_grad_scratch_bytes.argtypes = [C.c_int32]
+    lib.msgs_alpha_map.restype = C.c_int
+    lib.msgs_alpha_map.argtypes = [C.POINTER(View), vp, sz, vp, vp]
+    lib.msgs_backward_with_alpha.restype = C.c_int
+    lib.msgs_backward_with_alpha.argtypes = [C.POINTER(View), C.POINTER(Gaussians), vp, vp, sz, C.c_int64, vp, sz, vp, sz,
+                                             vp, vp, vp, vp, sz, C.POINTER(Grads), vp, vp, vp, vp, sz, C.POINTER(Timing), vp]
+    lib.msgs_bg_grad_scratch_bytes.restype = sz
+    lib.msgs_bg_grad_scratch_bytes.argtypes = [C.c_int32, C.c_int32]
+    lib.msgs_bg_grad.restype = C.c_int
+    lib.msgs_bg_grad.argtypes = [C.POINTER(View), vp, sz, vp, vp, vp, sz, vp]
     lib.msgs_backward_per_gaussian.restype = C.c_int
     lib.msgs_backward_per_gaussian.argtypes = [C.POINTER(View), C.POINTER(Gaussians), vp, vp, sz, vp, C.POINTER(Grads), vp]
     lib.msgs_sh_grad_from_views.restype = C.c_int
@@ -254,7 +263,8 @@ EXPORTS = ("msgs_abi_version", "msgs_error_string", "msgs_geom_bytes", "msgs_sta
            "msgs_set_occlusion", "msgs_occlusion_stats", "msgs_forward_info", "msgs_binning_bytes_slab",
            "msgs_stage2_scratch_bytes_slab", "msgs_slab_stats", "msgs_backward_with_depth",
            "msgs_backward_scratch_bytes_deterministic_depth", "msgs_backward_with_camera", "msgs_camera_grad_scratch_bytes",
-           "msgs_densify_scratch_bytes", "msgs_densify_select", "msgs_densify_apply")
+           "msgs_densify_scratch_bytes", "msgs_densify_select", "msgs_densify_apply",
+           "msgs_alpha_map", "msgs_backward_with_alpha", "msgs_bg_grad_scratch_bytes", "msgs_bg_grad")
 
 
 def check(rc, where):

@@ -112,3 +112,45 @@ def render_fused(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_mod
         occ_multiplier=pc.get_occ_multiplier, dc_delta=pc.get_dc_delta, base_mask=pc.get_base_mask)
     values = (image, acc_pixel_size, depth, viewspace, radii > 0, radii, pixel_sizes)
     return dict(zip(RESULT_KEYS, values))
+
+
+def render_with_alpha(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, override_color=None,
+                      filter_small=False, filter_large=False, fade_size=1.0, fused=False):
+    """render() — or, with fused=True, render_fused() (then without override_color) — plus the accumulated opacity of every
+    pixel: the seven keys of RESULT_KEYS and "alpha" [H,W] = 1 - final transmittance, differentiable like "render" and
+    "depth" (DESIGN.md 2, M9).  Mask / silhouette losses, sky and transparent backgrounds, opacity regularisers and
+    compositing read it instead of a second render with colour 1 over background 0.  A `bg_color` that requires grad
+    receives its gradient here as in render()."""
+    settings = _settings(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, filter_small, filter_large, fade_size)
+    rasterizer = GaussianRasterizer(raster_settings=settings, return_alpha=True)
+    if fused:
+        if override_color is not None:
+            raise ValueError("render_with_alpha: fused=True cannot be combined with override_color")
+        xyz = pc._xyz
+        viewspace = torch.empty_like(xyz, requires_grad=True)
+        image, acc_pixel_size, depth, radii, pixel_sizes, alpha = rasterizer.forward_raw(
+            xyz, viewspace, pc._features_dc, pc._features_rest, pc._opacity, pc._scaling, pc._rotation,
+            max_pixel_sizes=pc.get_max_pixel_sizes, min_pixel_sizes=pc.get_min_pixel_sizes,
+            occ_multiplier=pc.get_occ_multiplier, dc_delta=pc.get_dc_delta, base_mask=pc.get_base_mask)
+    else:
+        xyz = pc.get_xyz
+        viewspace = torch.zeros_like(xyz, requires_grad=True) + 0
+        try:
+            viewspace.retain_grad()
+        except Exception:
+            pass
+        image, acc_pixel_size, depth, radii, pixel_sizes, alpha = rasterizer(
+            means3D=xyz,
+            means2D=viewspace,
+            opacities=pc.get_opacity,
+            max_pixel_sizes=pc.get_max_pixel_sizes,
+            min_pixel_sizes=pc.get_min_pixel_sizes,
+            occ_multiplier=pc.get_occ_multiplier,
+            dc_delta=pc.get_dc_delta,
+            base_mask=pc.get_base_mask,
+            **_colour_inputs(viewpoint_camera, pc, pipe, override_color),
+            **_shape_inputs(pc, pipe, scaling_modifier))
+    values = (image, acc_pixel_size, depth, viewspace, radii > 0, radii, pixel_sizes)
+    out = dict(zip(RESULT_KEYS, values))
+    out["alpha"] = alpha
+    return out

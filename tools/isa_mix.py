@@ -119,7 +119,7 @@ def main():
                         "cycles_per_wave_entry": cycles(fwd),
                         "valu_mix": [fwd["plain"] / valu(fwd), fwd["half"] / valu(fwd), fwd["trans"] / valu(fwd)]}
 
-    a, b = kernel_range(lines, "blend_backward_tile_kernelILb0ELi3E")
+    a, b = kernel_range(lines, "blend_backward_tile_kernelILb0ELi3ELb0E")       # <COUNT = false, CH = 3, ALPHA = false>
     loops, lab = loops_of(lines, a, b)
     cand = [se for se in innermost(loops) if n_exp(lines, *se) >= 4]
     s, e = min(cand, key=lambda se: se[1] - se[0])
