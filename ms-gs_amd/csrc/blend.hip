@@ -23,7 +23,7 @@
 // instead of once per pixel here.
 //
 // Backward reduction: per (wave, record) the nine partial sums are reduced across the 64 lanes with a
-// hand-scheduled DPP reduce-scatter inside each 16-lane row (row_reduce_scatter9: 8 -> 4 -> 2 -> 1 values per
+// hand-scheduled DPP reduce-scatter inside each 16-lane row (row_reduce_scatter: 8 -> 4 -> 2 -> 1 values per
 // lane, the ninth riding on the duplicate lanes), one cross-row all-reduce of the single remaining value, and ONE
 // global_atomic_add_f64 instruction from nine lanes into the 80-byte per-Gaussian gradient record of double accumulators
 // (the tiles' float32 sums add up exactly, so the default backward is reproducible whatever order the atomics arrive in:
@@ -379,6 +379,15 @@ __global__ __launch_bounds__(64) void forward_feedback_kernel(const unsigned lon
     }
 }
 
+// Can record e of the staged batch reach the SB x SB sub-block whose first pixel is (bx0, by0)?  The exact alpha >= 1/255
+// level-set test of the fine-grained kernels, forward and backward alike (s_r0 holds the cross term doubled).
+template <int SB>
+__device__ __forceinline__ bool fine_hit(const float4* s_r0, const float4* s_r1, const float* s_tau, int e, float bx0, float by0) {
+    const float4 r0 = s_r0[e];
+    const float C = s_r1[e].x, tau2 = s_tau[e];
+    return !(tau2 > -1.0e38f) ||
+           levelset_hits_rect(r0.x, r0.y, r0.z, 0.5f * r0.w, C, tau2, bx0, bx0 + (float)(SB - 1), by0, by0 + (float)(SB - 1));
+}
 // Fine-grained variant for FEW tiles (low pyramid levels): one wave64 per 4x4 pixel sub-block (lanes 0..15) — sixteen per tile —
 // in workgroups of WAVES waves, G = 16 / WAVES workgroups per tile.  With fewer than ~300 tiles the quadrant kernel is latency-bound
 // — one wave per SIMD at best, and a pixel's list is inherently sequential — so its time is the length of the longest per-wave entry
@@ -458,14 +467,7 @@ __global__ __launch_bounds__(64 * WAVES) void blend_forward_fine_kernel(ViewPara
 #pragma unroll
         for (int c = 0; c < BATCH / 64; ++c) {
             const int e = c * 64 + lane;
-            bool hit = false;
-            if (e < n) {
-                const float4 r0 = s_r0[e];
-                const float C = s_r1[e].x, tau2 = s_tau[e];
-                hit = !(tau2 > -1.0e38f) ||
-                      levelset_hits_rect(r0.x, r0.y, r0.z, 0.5f * r0.w, C, tau2, bx0, bx0 + (float)(SB - 1), by0,
-                                         by0 + (float)(SB - 1));
-            }
+            const bool hit = e < n && fine_hit<SB>(s_r0, s_r1, s_tau, e, bx0, by0);
             const uint64_t b = __ballot(hit);
             if (hit) s_list[w][cnt + __popcll(b & lt_mask)] = (uint32_t)(e << 4);
             cnt += __popcll(b);
@@ -494,96 +496,151 @@ __global__ __launch_bounds__(64 * WAVES) void blend_forward_fine_kernel(ViewPara
 // the leading s_nop covers whatever the compiler scheduled right before it.
 template <class A> struct BwdSumsT { A v0, v1, v2, v3, v4, v5, v6, v7, v8; };
 using BwdSums = BwdSumsT<float>;
-__device__ __forceinline__ float row_reduce_scatter9(const BwdSums& v) {
+// Depth variant (ten sums, the tenth = sum alpha T dL/dD): v0..v7 as above; v8 and v9 share the lanes whose bit 1 is set —
+// the first exchange (lane parity) sends v9 from even lanes and v8 from odd ones, so the even lanes all-reduce v8 and the odd
+// lanes v9 with the same three row steps that follow.  Two selects more than the nine-sum block, still one value per lane:
+// lane l holds component comp(l) for (l & 2) == 0, component 8 + (l & 1) otherwise.
+// The two blocks differ in the leading selects and the first t8 step only; the rest of the text is shared.
+#define ROW_SCATTER_HALF_ROWS                                                             \
+    "v_add_f32_dpp %[a0], %[v0], %[v0] row_ror:8 row_mask:0xf bank_mask:0xf\n\t"          \
+    "v_add_f32_dpp %[a1], %[v1], %[v1] row_ror:8 row_mask:0xf bank_mask:0xf\n\t"          \
+    "v_add_f32_dpp %[a2], %[v2], %[v2] row_ror:8 row_mask:0xf bank_mask:0xf\n\t"          \
+    "v_add_f32_dpp %[a3], %[v3], %[v3] row_ror:8 row_mask:0xf bank_mask:0xf\n\t"          \
+    "v_add_f32_dpp %[a0], %[v4], %[v4] row_ror:8 row_mask:0xf bank_mask:0xc\n\t"          \
+    "v_add_f32_dpp %[a1], %[v5], %[v5] row_ror:8 row_mask:0xf bank_mask:0xc\n\t"          \
+    "v_add_f32_dpp %[a2], %[v6], %[v6] row_ror:8 row_mask:0xf bank_mask:0xc\n\t"          \
+    "v_add_f32_dpp %[a3], %[v7], %[v7] row_ror:8 row_mask:0xf bank_mask:0xc\n\t"
+#define ROW_SCATTER_QUADS_AND_LANES                                                       \
+    "v_add_f32_dpp %[b0], %[a0], %[a0] row_half_mirror row_mask:0xf bank_mask:0xf\n\t"    \
+    "v_add_f32_dpp %[b1], %[a1], %[a1] row_half_mirror row_mask:0xf bank_mask:0xf\n\t"    \
+    "v_add_f32_dpp %[b0], %[a2], %[a2] row_half_mirror row_mask:0xf bank_mask:0xa\n\t"    \
+    "v_add_f32_dpp %[b1], %[a3], %[a3] row_half_mirror row_mask:0xf bank_mask:0xa\n\t"    \
+    "v_add_f32_dpp %[t8], %[t8], %[t8] quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t" \
+    "v_cndmask_b32_e64 %[send], %[b1], %[b0], %[odd]\n\t"                                 \
+    "v_cndmask_b32_e64 %[keep], %[b0], %[b1], %[odd]\n\t"                                 \
+    "v_add_f32_dpp %[t8], %[t8], %[t8] row_ror:4 row_mask:0xf bank_mask:0xf\n\t"          \
+    "v_add_f32_dpp %[c], %[send], %[keep] quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t" \
+    "s_nop 0\n\t"                                                                         \
+    "v_add_f32_dpp %[t8], %[t8], %[t8] row_ror:8 row_mask:0xf bank_mask:0xf\n\t"          \
+    "v_add_f32_dpp %[c], %[c], %[c] quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"   \
+    "v_cndmask_b32_e64 %[c], %[c], %[t8], %[bit1]"
+#define ROW_SCATTER_OUTS                                                                                      \
+    [a0] "=&v"(a0), [a1] "=&v"(a1), [a2] "=&v"(a2), [a3] "=&v"(a3), [b0] "=&v"(b0), [b1] "=&v"(b1),           \
+    [t8] "=&v"(t8), [keep] "=&v"(keep), [send] "=&v"(send), [c] "=&v"(c)
+#define ROW_SCATTER_INS                                                                                       \
+    [v0] "v"(v.v0), [v1] "v"(v.v1), [v2] "v"(v.v2), [v3] "v"(v.v3), [v4] "v"(v.v4), [v5] "v"(v.v5),           \
+    [v6] "v"(v.v6), [v7] "v"(v.v7), [v8] "v"(v.v8)
+template <bool DEPTH>
+__device__ __forceinline__ float row_reduce_scatter(const BwdSums& v, float v9) {
     float a0, a1, a2, a3, b0, b1, t8, keep, send, c;
     const uint64_t odd = 0xAAAAAAAAAAAAAAAAull, bit1 = 0xCCCCCCCCCCCCCCCCull;
-    asm volatile(
-        "s_nop 1\n\t"
-        "v_add_f32_dpp %[a0], %[v0], %[v0] row_ror:8 row_mask:0xf bank_mask:0xf\n\t"
-        "v_add_f32_dpp %[a1], %[v1], %[v1] row_ror:8 row_mask:0xf bank_mask:0xf\n\t"
-        "v_add_f32_dpp %[a2], %[v2], %[v2] row_ror:8 row_mask:0xf bank_mask:0xf\n\t"
-        "v_add_f32_dpp %[a3], %[v3], %[v3] row_ror:8 row_mask:0xf bank_mask:0xf\n\t"
-        "v_add_f32_dpp %[a0], %[v4], %[v4] row_ror:8 row_mask:0xf bank_mask:0xc\n\t"
-        "v_add_f32_dpp %[a1], %[v5], %[v5] row_ror:8 row_mask:0xf bank_mask:0xc\n\t"
-        "v_add_f32_dpp %[a2], %[v6], %[v6] row_ror:8 row_mask:0xf bank_mask:0xc\n\t"
-        "v_add_f32_dpp %[a3], %[v7], %[v7] row_ror:8 row_mask:0xf bank_mask:0xc\n\t"
-        "v_add_f32_dpp %[t8], %[v8], %[v8] quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-        "v_add_f32_dpp %[b0], %[a0], %[a0] row_half_mirror row_mask:0xf bank_mask:0xf\n\t"
-        "v_add_f32_dpp %[b1], %[a1], %[a1] row_half_mirror row_mask:0xf bank_mask:0xf\n\t"
-        "v_add_f32_dpp %[b0], %[a2], %[a2] row_half_mirror row_mask:0xf bank_mask:0xa\n\t"
-        "v_add_f32_dpp %[b1], %[a3], %[a3] row_half_mirror row_mask:0xf bank_mask:0xa\n\t"
-        "v_add_f32_dpp %[t8], %[t8], %[t8] quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
-        "v_cndmask_b32_e64 %[send], %[b1], %[b0], %[odd]\n\t"
-        "v_cndmask_b32_e64 %[keep], %[b0], %[b1], %[odd]\n\t"
-        "v_add_f32_dpp %[t8], %[t8], %[t8] row_ror:4 row_mask:0xf bank_mask:0xf\n\t"
-        "v_add_f32_dpp %[c], %[send], %[keep] quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-        "s_nop 0\n\t"
-        "v_add_f32_dpp %[t8], %[t8], %[t8] row_ror:8 row_mask:0xf bank_mask:0xf\n\t"
-        "v_add_f32_dpp %[c], %[c], %[c] quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
-        "v_cndmask_b32_e64 %[c], %[c], %[t8], %[bit1]"
-        : [a0] "=&v"(a0), [a1] "=&v"(a1), [a2] "=&v"(a2), [a3] "=&v"(a3), [b0] "=&v"(b0), [b1] "=&v"(b1),
-          [t8] "=&v"(t8), [keep] "=&v"(keep), [send] "=&v"(send), [c] "=&v"(c)
-        : [v0] "v"(v.v0), [v1] "v"(v.v1), [v2] "v"(v.v2), [v3] "v"(v.v3), [v4] "v"(v.v4), [v5] "v"(v.v5),
-          [v6] "v"(v.v6), [v7] "v"(v.v7), [v8] "v"(v.v8), [odd] "s"(odd), [bit1] "s"(bit1));
+    if constexpr (DEPTH) {
+        float k89, s89;
+        asm volatile(
+            "s_nop 1\n\t"
+            "v_cndmask_b32_e64 %[s89], %[v9], %[v8], %[odd]\n\t"
+            "v_cndmask_b32_e64 %[k89], %[v8], %[v9], %[odd]\n\t"
+            ROW_SCATTER_HALF_ROWS
+            "v_add_f32_dpp %[t8], %[s89], %[k89] quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+            ROW_SCATTER_QUADS_AND_LANES
+            : ROW_SCATTER_OUTS, [k89] "=&v"(k89), [s89] "=&v"(s89)
+            : ROW_SCATTER_INS, [v9] "v"(v9), [odd] "s"(odd), [bit1] "s"(bit1));
+    } else {
+        asm volatile(
+            "s_nop 1\n\t"
+            ROW_SCATTER_HALF_ROWS
+            "v_add_f32_dpp %[t8], %[v8], %[v8] quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+            ROW_SCATTER_QUADS_AND_LANES
+            : ROW_SCATTER_OUTS
+            : ROW_SCATTER_INS, [odd] "s"(odd), [bit1] "s"(bit1));
+    }
     return c;
 }
-// component (0..8) that lane l of a row delivers after row_reduce_scatter9
+#undef ROW_SCATTER_HALF_ROWS
+#undef ROW_SCATTER_QUADS_AND_LANES
+#undef ROW_SCATTER_OUTS
+#undef ROW_SCATTER_INS
+// component (0..8; depth: 0..9) that lane l of a row delivers after row_reduce_scatter
+template <bool DEPTH>
 __device__ __forceinline__ uint32_t row_reduce_component(int l) {
-    return (l & 2) ? 8u : (uint32_t)(4 * ((l >> 3) & 1) + 2 * ((l >> 2) & 1) + (l & 1));
+    return (l & 2) ? (DEPTH ? 8u + (uint32_t)(l & 1) : 8u) : (uint32_t)(4 * ((l >> 3) & 1) + 2 * ((l >> 2) & 1) + (l & 1));
 }
-// Depth variant (ten sums, the tenth = sum alpha T dL/dD): v0..v7 as in row_reduce_scatter9; v8 and v9 share the lanes
-// whose bit 1 is set — the first exchange (lane parity) sends v9 from even lanes and v8 from odd ones, so the even lanes
-// all-reduce v8 and the odd lanes v9 with the same three row steps that follow.  Two selects more than row_reduce_scatter9,
-// still one value per lane: lane l holds component comp(l) for (l & 2) == 0, component 8 + (l & 1) otherwise.
-__device__ __forceinline__ float row_reduce_scatter10(const BwdSums& v, float v9) {
-    float a0, a1, a2, a3, b0, b1, t8, keep, send, c, k89, s89;
-    const uint64_t odd = 0xAAAAAAAAAAAAAAAAull, bit1 = 0xCCCCCCCCCCCCCCCCull;
-    asm volatile(
-        "s_nop 1\n\t"
-        "v_cndmask_b32_e64 %[s89], %[v9], %[v8], %[odd]\n\t"
-        "v_cndmask_b32_e64 %[k89], %[v8], %[v9], %[odd]\n\t"
-        "v_add_f32_dpp %[a0], %[v0], %[v0] row_ror:8 row_mask:0xf bank_mask:0xf\n\t"
-        "v_add_f32_dpp %[a1], %[v1], %[v1] row_ror:8 row_mask:0xf bank_mask:0xf\n\t"
-        "v_add_f32_dpp %[a2], %[v2], %[v2] row_ror:8 row_mask:0xf bank_mask:0xf\n\t"
-        "v_add_f32_dpp %[a3], %[v3], %[v3] row_ror:8 row_mask:0xf bank_mask:0xf\n\t"
-        "v_add_f32_dpp %[a0], %[v4], %[v4] row_ror:8 row_mask:0xf bank_mask:0xc\n\t"
-        "v_add_f32_dpp %[a1], %[v5], %[v5] row_ror:8 row_mask:0xf bank_mask:0xc\n\t"
-        "v_add_f32_dpp %[a2], %[v6], %[v6] row_ror:8 row_mask:0xf bank_mask:0xc\n\t"
-        "v_add_f32_dpp %[a3], %[v7], %[v7] row_ror:8 row_mask:0xf bank_mask:0xc\n\t"
-        "v_add_f32_dpp %[t8], %[s89], %[k89] quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-        "v_add_f32_dpp %[b0], %[a0], %[a0] row_half_mirror row_mask:0xf bank_mask:0xf\n\t"
-        "v_add_f32_dpp %[b1], %[a1], %[a1] row_half_mirror row_mask:0xf bank_mask:0xf\n\t"
-        "v_add_f32_dpp %[b0], %[a2], %[a2] row_half_mirror row_mask:0xf bank_mask:0xa\n\t"
-        "v_add_f32_dpp %[b1], %[a3], %[a3] row_half_mirror row_mask:0xf bank_mask:0xa\n\t"
-        "v_add_f32_dpp %[t8], %[t8], %[t8] quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
-        "v_cndmask_b32_e64 %[send], %[b1], %[b0], %[odd]\n\t"
-        "v_cndmask_b32_e64 %[keep], %[b0], %[b1], %[odd]\n\t"
-        "v_add_f32_dpp %[t8], %[t8], %[t8] row_ror:4 row_mask:0xf bank_mask:0xf\n\t"
-        "v_add_f32_dpp %[c], %[send], %[keep] quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-        "s_nop 0\n\t"
-        "v_add_f32_dpp %[t8], %[t8], %[t8] row_ror:8 row_mask:0xf bank_mask:0xf\n\t"
-        "v_add_f32_dpp %[c], %[c], %[c] quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
-        "v_cndmask_b32_e64 %[c], %[c], %[t8], %[bit1]"
-        : [a0] "=&v"(a0), [a1] "=&v"(a1), [a2] "=&v"(a2), [a3] "=&v"(a3), [b0] "=&v"(b0), [b1] "=&v"(b1),
-          [t8] "=&v"(t8), [keep] "=&v"(keep), [send] "=&v"(send), [c] "=&v"(c), [k89] "=&v"(k89), [s89] "=&v"(s89)
-        : [v0] "v"(v.v0), [v1] "v"(v.v1), [v2] "v"(v.v2), [v3] "v"(v.v3), [v4] "v"(v.v4), [v5] "v"(v.v5),
-          [v6] "v"(v.v6), [v7] "v"(v.v7), [v8] "v"(v.v8), [v9] "v"(v9), [odd] "s"(odd), [bit1] "s"(bit1));
-    return c;
+// the nine lanes that issue the per-entry atomics (depth: ten, lane 3 delivers component 9); lane l adds to record slot
+// row_reduce_component<DEPTH>(l).  (A macro: as a function the predicate is simplified on its own before it is inlined, and the
+// operands of one s_or_b64 then come out in another order in some of the kernels.)
+#define IS_ATOMIC_LANE(DEPTH, lane) \
+    ((DEPTH) ? (lane) < 16 && (!((lane) & 2) || (lane) == 2 || (lane) == 3) : (lane) < 16 && (!((lane) & 2) || (lane) == 2))
+// One reduction per (wave, entry): rows by DPP, the four rows by `cross_row` (v_permlane16/32_swap in the latency-bound
+// four-waves kernel, where they beat ds_bpermute — profiles/r1_notes.md; ds_bpermute in the one-wave-per-tile kernel; nothing in
+// the fine-grained kernel, whose pixels live in row 0), scalar record address from the wave-uniform id (`id()`: read from LDS
+// here, behind the reduction), ONE atomic instruction from the nine (depth: ten) lanes.
+template <bool DEPTH, class CrossRow, class Id>
+__device__ __forceinline__ void reduce_and_add(const BwdSums& v, float v9, CrossRow cross_row, Id id,
+                                               grad_acc_t* __restrict__ grad_rec, bool alane, uint32_t aoff) {
+    const float outv = cross_row(row_reduce_scatter<DEPTH>(v, v9));
+    const uint32_t gid = __builtin_amdgcn_readfirstlane(id());
+    grad_acc_t* gdst = grad_rec + (size_t)gid * GRAD_REC_FLOATS;
+    if (alane) unsafeAtomicAdd(gdst + aoff, (grad_acc_t)outv);
 }
-// component (0..9) that lane l of a row delivers after row_reduce_scatter10
-__device__ __forceinline__ uint32_t row_reduce_component10(int l) {
-    return (l & 2) ? 8u + (uint32_t)(l & 1) : (uint32_t)(4 * ((l >> 3) & 1) + 2 * ((l >> 2) & 1) + (l & 1));
-}
-// Per-pixel backward state and the walk over one wave's compacted entry list (back to front) — shared by the
-// four-waves-per-tile kernel (CROSS_ROW: the pixels of an 8x8 quadrant fill the wave, the four 16-lane rows are added
-// with v_permlane16/32_swap) and the fine-grained kernel (the sixteen pixels of a 4x4 sub-block live in row 0: the row
-// reduction is the whole reduction).  Same arithmetic per pixel in the same order in both.
-// DEPTH (the depth variants, msgs_backward_with_depth): the depth map is a fourth channel with colour z (s_z) and no
-// background — its share z dL/dD enters g_i (so S and dL/dalpha), and a tenth sum alpha T dL/dD = dL/dz goes to record slot 9.
+// Per-pixel backward state and the per-(pixel, Gaussian) step — shared by the three backward kernels.  Same arithmetic per
+// pixel in the same order in all of them.
+// DEPTH (the depth variants, msgs_backward_with_depth): the depth map is a fourth channel with colour z and no background —
+// its share z dL/dD enters g_i (so S and dL/dalpha), and a tenth sum alpha T dL/dD = dL/dz goes to record slot 9.
 struct BwdPix {
-    float T, S, dL0, dL1, dL2, dLd;
+    float T, S, dL0, dL1, dL2, dLd;  // S: see bwd_pix_start_S; dLd: dL/dD (depth variant)
     uint32_t last;
 };
+// S = sum_c dL/dC_c * (colour composited BEHIND the current entry, background included, normalised by the
+// transmittance in front of it).  dL/dalpha_i = T_i (g_i - S_i) with g_i = sum_c dL/dC_c colour_i,c, and
+// S_{i-1} = S_i + alpha_i (g_i - S_i): the three per-channel recurrences of the textbook form collapse into one
+// scalar, and starting it at bg . dL/dC absorbs the separate background term (-T_final bg.dL / (1 - alpha_i)).
+template <bool ALPHA>
+__device__ __forceinline__ void bwd_pix_start_S(BwdPix& st, const ViewParams& vp, bool inside, size_t pix,
+                                                const float* dL_dalpha) {
+    st.S = vp.bg[0] * st.dL0 + vp.bg[1] * st.dL1 + vp.bg[2] * st.dL2;
+    if constexpr (ALPHA) { if (inside) st.S -= dL_dalpha[pix]; }     // the alpha map's share (lanes outside the image do not read)
+}
+// First part of the step: the pair's monomials and its unclamped alpha.
+struct PairAlpha { PairEval ev; float a_raw; };
+__device__ __forceinline__ PairAlpha pair_alpha(const float4& r0, const float4& r1, float dx, float dy) {
+    PairAlpha a;
+    a.ev = eval_pair(r0.z, r0.w, r1.x, r1.y, dx, dy);
+    a.a_raw = __builtin_amdgcn_exp2f(a.ev.p);
+    return a;
+}
+// The lanes the pair counts for, as a SCALAR mask: three ballots of direct comparisons and scalar ANDs (a ballot of a derived
+// bool costs two VALU instructions).  pos = the entry's 0-based position in the tile list; `last` = the position behind the
+// last entry the pixel blended; bound: sign_test_bound.
+__device__ __forceinline__ uint64_t pair_valid(const PairAlpha& a, uint32_t pos, uint32_t last, float bound) {
+    return __builtin_amdgcn_ballot_w64(pos < last) & __builtin_amdgcn_ballot_w64(a.ev.p <= bound) &
+           __builtin_amdgcn_ballot_w64(a.a_raw >= ALPHA_MIN);   // alpha = min(0.99, a_raw) >= 1/255  <=>  a_raw >= 1/255
+}
+// Last part: the T and S recurrences of the pixel; returns q = alpha_raw dL/dalpha and dch = alpha T (the weight of dL/dC in
+// the colour sums).  z(): the entry's view depth (DEPTH only), read where g_i is formed.
+struct PairGrad { float q, dch; };
+template <bool DEPTH, class Z>
+__device__ __forceinline__ PairGrad pair_grad(BwdPix& s, const PairAlpha& a, uint64_t validm, const float4& r1, float cb, Z z) {
+    const bool valid = __builtin_amdgcn_inverse_ballot_w64(validm);
+    // ONE select masks the lane: with a_m = 0 everything downstream is the identity (alpha 0, 1/(1-0) = 1 exactly,
+    // T unchanged, zero contributions), so neither alpha nor T needs a select of its own
+    const float a_m = valid ? a.a_raw : 0.0f;
+    const float alpha_m = fminf(0.99f, a_m);
+    const float inv = __builtin_amdgcn_rcpf(1.0f - alpha_m);
+    const float Tn = s.T * inv;
+    s.T = Tn;
+    PairGrad g;
+    g.dch = alpha_m * Tn;
+    float gi = fmaf(cb, s.dL2, fmaf(r1.w, s.dL1, r1.z * s.dL0));
+    if constexpr (DEPTH) gi = fmaf(z(), s.dLd, gi);
+    const float sm = gi - s.S;
+    const float dL_dalpha = sm * Tn;
+    s.S = fmaf(alpha_m, sm, s.S);
+    g.q = a_m * dL_dalpha;                                    // Q6: gradient passes the 0.99 clamp
+    return g;
+}
+// The walk over one wave's compacted entry list (back to front) — shared by the four-waves-per-tile kernel (CROSS_ROW: the
+// pixels of an 8x8 quadrant fill the wave, the four 16-lane rows are added with v_permlane16/32_swap) and the fine-grained
+// kernel (the sixteen pixels of a 4x4 sub-block live in row 0: the row reduction is the whole reduction).
 template <bool CROSS_ROW, bool DEPTH = false>
 __device__ __forceinline__ void backward_walk(const uint16_t* lp, int cnt, int base, const float4* s_r0, const float4* s_r1,
                                               const float2* s_b, const uint32_t* s_id, float pxf, float pyf, BwdPix& st,
@@ -593,37 +650,15 @@ __device__ __forceinline__ void backward_walk(const uint16_t* lp, int cnt, int b
         const int e = lp[j];
         const float4 r0 = s_r0[e], r1 = s_r1[e];
         const float2 bl = s_b[e];                              // {blue, sign_test_bound}
-        const float cb = bl.x;
         const float dx = r0.x - pxf, dy = r0.y - pyf;
-        const PairEval ev = eval_pair(r0.z, r0.w, r1.x, r1.y, dx, dy);
-        const float a_raw = __builtin_amdgcn_exp2f(ev.p);
-        const uint64_t validm = __builtin_amdgcn_ballot_w64((uint32_t)(base + e) < st.last) &
-                                __builtin_amdgcn_ballot_w64(ev.p <= bl.y) &
-                                __builtin_amdgcn_ballot_w64(a_raw >= ALPHA_MIN);   // <=> min(0.99, a_raw) >= 1/255
+        const PairAlpha a = pair_alpha(r0, r1, dx, dy);
+        const uint64_t validm = pair_valid(a, (uint32_t)(base + e), st.last, bl.y);
         if (validm == 0) continue;
-        const bool valid = __builtin_amdgcn_inverse_ballot_w64(validm);
-        const float a_m = valid ? a_raw : 0.0f;                // the one select: a masked lane is the identity below
-        const float alpha_m = fminf(0.99f, a_m);
-        const float inv = __builtin_amdgcn_rcpf(1.0f - alpha_m);
-        const float Tn = st.T * inv;
-        st.T = Tn;
-        const float dch = alpha_m * Tn;
-        float gi = fmaf(cb, st.dL2, fmaf(r1.w, st.dL1, r1.z * st.dL0));
-        if constexpr (DEPTH) gi = fmaf(s_z[e], st.dLd, gi);
-        const float sm = gi - st.S;
-        const float dL_dalpha = sm * Tn;
-        st.S = fmaf(alpha_m, sm, st.S);
-        const float q = a_m * dL_dalpha;                       // Q6: gradient passes the 0.99 clamp
-        const BwdSums v = {q * dx, q * dy, q * ev.dxx, q * ev.dxy, q * ev.dyy, q, dch * st.dL0, dch * st.dL1, dch * st.dL2};
-        // rows by DPP; the four rows with v_permlane16/32_swap (in this latency-bound regime they beat ds_bpermute,
-        // profiles/r1_notes.md); scalar record address, one atomic instruction from nine (depth: ten) lanes
-        float rowv;
-        if constexpr (DEPTH) rowv = row_reduce_scatter10(v, dch * st.dLd);
-        else rowv = row_reduce_scatter9(v);
-        const float outv = CROSS_ROW ? cross_row_allreduce(rowv) : rowv;
-        const uint32_t gid = __builtin_amdgcn_readfirstlane(s_id[e]);
-        grad_acc_t* gdst = grad_rec + (size_t)gid * GRAD_REC_FLOATS;
-        if (alane) unsafeAtomicAdd(gdst + aoff, (grad_acc_t)outv);
+        const PairGrad g = pair_grad<DEPTH>(st, a, validm, r1, bl.x, [=] { return s_z[e]; });
+        const float q = g.q, dch = g.dch;
+        const BwdSums v = {q * dx, q * dy, q * a.ev.dxx, q * a.ev.dxy, q * a.ev.dyy, q, dch * st.dL0, dch * st.dL1, dch * st.dL2};
+        reduce_and_add<DEPTH>(v, DEPTH ? dch * st.dLd : 0.f, [](float x) { return CROSS_ROW ? cross_row_allreduce(x) : x; },
+                              [=] { return s_id[e]; }, grad_rec, alane, aoff);
     }
 }
 
@@ -681,15 +716,9 @@ __global__ __launch_bounds__(256) void blend_backward_kernel(ViewParams vp, cons
     __syncthreads();
     const uint32_t tile_last = max(max(s_wmax[0], s_wmax[1]), max(s_wmax[2], s_wmax[3]));
 
-    // S = sum_c dL/dC_c * (colour composited BEHIND the current entry, background included, normalised by the
-    // transmittance in front of it).  dL/dalpha_i = T_i (g_i - S_i) with g_i = sum_c dL/dC_c colour_i,c, and
-    // S_{i-1} = S_i + alpha_i (g_i - S_i): the three per-channel recurrences of the textbook form collapse into one
-    // scalar, and starting it at bg . dL/dC absorbs the separate background term (-T_final bg.dL / (1 - alpha_i)).
-    st.S = vp.bg[0] * st.dL0 + vp.bg[1] * st.dL1 + vp.bg[2] * st.dL2;
-    if constexpr (ALPHA) { if (inside) st.S -= dL_dalpha[pix]; }     // the alpha map's share (lanes outside the image do not read)
-    // the nine lanes that issue the per-entry atomics (depth: ten, lane 3 delivers component 9)
-    const bool alane = DEPTH ? lane < 16 && (!(lane & 2) || lane == 2 || lane == 3) : lane < 16 && (!(lane & 2) || lane == 2);
-    const uint32_t aoff = DEPTH ? row_reduce_component10(lane) : row_reduce_component(lane);
+    bwd_pix_start_S<ALPHA>(st, vp, inside, pix, dL_dalpha);
+    const bool alane = IS_ATOMIC_LANE(DEPTH, lane);
+    const uint32_t aoff = row_reduce_component<DEPTH>(lane);
 
     const int nb = ((int)tile_last + BATCH - 1) / BATCH;
     for (int b = nb - 1; b >= 0; --b) {
@@ -772,15 +801,9 @@ __global__ __launch_bounds__(64 * WAVES) void blend_backward_fine_kernel(ViewPar
 #pragma unroll
     for (int k = 0; k < WAVES; ++k) grp_last = max(grp_last, s_wmax[k]);
 
-    // S = sum_c dL/dC_c * (colour composited BEHIND the current entry, background included, normalised by the
-    // transmittance in front of it).  dL/dalpha_i = T_i (g_i - S_i) with g_i = sum_c dL/dC_c colour_i,c, and
-    // S_{i-1} = S_i + alpha_i (g_i - S_i): the three per-channel recurrences of the textbook form collapse into one
-    // scalar, and starting it at bg . dL/dC absorbs the separate background term (-T_final bg.dL / (1 - alpha_i)).
-    st.S = vp.bg[0] * st.dL0 + vp.bg[1] * st.dL1 + vp.bg[2] * st.dL2;
-    if constexpr (ALPHA) { if (inside) st.S -= dL_dalpha[pix]; }     // the alpha map's share (lanes outside the image do not read)
-    // the nine lanes that issue the per-entry atomics (depth: ten, lane 3 delivers component 9)
-    const bool alane = DEPTH ? lane < 16 && (!(lane & 2) || lane == 2 || lane == 3) : lane < 16 && (!(lane & 2) || lane == 2);
-    const uint32_t aoff = DEPTH ? row_reduce_component10(lane) : row_reduce_component(lane);
+    bwd_pix_start_S<ALPHA>(st, vp, inside, pix, dL_dalpha);
+    const bool alane = IS_ATOMIC_LANE(DEPTH, lane);
+    const uint32_t aoff = row_reduce_component<DEPTH>(lane);
 
     const int nb = ((int)grp_last + BATCH - 1) / BATCH;
     // register prefetch of the next (nearer) batch, as in blend_forward_fine_kernel
@@ -817,14 +840,7 @@ __global__ __launch_bounds__(64 * WAVES) void blend_backward_fine_kernel(ViewPar
 #pragma unroll
         for (int c = 0; c < BATCH / 64; ++c) {
             const int e = c * 64 + lane;
-            bool hit = false;
-            if (e < n && (uint32_t)(base + e) < wave_last) {
-                const float4 r0 = s_r0[e];
-                const float C = s_r1[e].x, tau2 = s_tau[e];
-                hit = !(tau2 > -1.0e38f) ||
-                      levelset_hits_rect(r0.x, r0.y, r0.z, 0.5f * r0.w, C, tau2, bx0, bx0 + (float)(SB - 1), by0,
-                                         by0 + (float)(SB - 1));
-            }
+            const bool hit = e < n && (uint32_t)(base + e) < wave_last && fine_hit<SB>(s_r0, s_r1, s_tau, e, bx0, by0);
             const uint64_t bal = __ballot(hit);
             if (hit) s_list[w][cnt + __popcll(bal & lt_mask)] = (uint16_t)e;
             cnt += __popcll(bal);
@@ -850,46 +866,22 @@ __device__ __forceinline__ void wave_fence() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-struct BwdQuad {
-    float T, S, dL0, dL1, dL2, dLd;  // S: see blend_backward_kernel; dLd: dL/dD (depth variant)
-    uint32_t last;
-};
-
-// one (pixel, Gaussian) backward step accumulated into the per-lane partial sums; returns the lane's validity
+// one (pixel, Gaussian) backward step accumulated into the per-lane partial sums; returns the lanes that contributed as a
+// scalar mask (the caller only needs "any lane?")
 // (no wave-level early-out here: every ballot-driven branch is a VALU -> SALU -> branch round trip, and the
 // quadrant hit masks already removed the quadrants the record cannot touch)
-// (returns the lanes that contributed as a scalar mask: three ballots of direct comparisons and scalar ANDs — a ballot
-//  of a derived bool costs two VALU instructions, and the caller only needs "any lane?")
-// (DEPTH: z is the entry's view depth and v9 the tenth sum, see backward_walk)
-template <bool DEPTH = false>
-__device__ __forceinline__ uint64_t bwd_quad_step(BwdQuad& s, BwdSums& v, const float4& r0, const float4& r1, float cb,
-                                                  float bound, float dx, float dy, uint32_t pos0, float z = 0.f,
-                                                  float* v9 = nullptr) {
-    const PairEval ev = eval_pair(r0.z, r0.w, r1.x, r1.y, dx, dy);
-    const float a_raw = __builtin_amdgcn_exp2f(ev.p);
-    // alpha = min(0.99, a_raw) >= 1/255  <=>  a_raw >= 1/255
-    const uint64_t validm = __builtin_amdgcn_ballot_w64(pos0 < s.last) & __builtin_amdgcn_ballot_w64(ev.p <= bound) &
-                            __builtin_amdgcn_ballot_w64(a_raw >= ALPHA_MIN);
-    const bool valid = __builtin_amdgcn_inverse_ballot_w64(validm);
-    // ONE select masks the lane: with a_m = 0 everything downstream is the identity (alpha 0, 1/(1-0) = 1 exactly,
-    // T unchanged, zero contributions), so neither alpha nor T needs a select of its own
-    const float a_m = valid ? a_raw : 0.0f;
-    const float alpha_m = fminf(0.99f, a_m);
-    const float inv = __builtin_amdgcn_rcpf(1.0f - alpha_m);
-    const float Tn = s.T * inv;
-    s.T = Tn;
-    const float dch = alpha_m * Tn;
-    float gi = fmaf(cb, s.dL2, fmaf(r1.w, s.dL1, r1.z * s.dL0));
-    if constexpr (DEPTH) gi = fmaf(z, s.dLd, gi);
-    const float sm = gi - s.S;
-    const float dL_dalpha = sm * Tn;
-    s.S = fmaf(alpha_m, sm, s.S);
-    const float qq = a_m * dL_dalpha;                         // Q6: gradient passes the 0.99 clamp
-    v.v0 = fmaf(qq, dx, v.v0); v.v1 = fmaf(qq, dy, v.v1);
-    v.v2 = fmaf(qq, ev.dxx, v.v2); v.v3 = fmaf(qq, ev.dxy, v.v3); v.v4 = fmaf(qq, ev.dyy, v.v4);
-    v.v5 += qq;
-    v.v6 = fmaf(dch, s.dL0, v.v6); v.v7 = fmaf(dch, s.dL1, v.v7); v.v8 = fmaf(dch, s.dL2, v.v8);
-    if constexpr (DEPTH) *v9 = fmaf(dch, s.dLd, *v9);
+// (DEPTH: z is the entry's view depth and v9 the tenth sum, see BwdPix)
+template <bool DEPTH>
+__device__ __forceinline__ uint64_t bwd_quad_step(BwdPix& s, BwdSums& v, float* v9, const float4& r0, const float4& r1, float cb,
+                                                  float bound, float dx, float dy, uint32_t pos0, float z) {
+    const PairAlpha a = pair_alpha(r0, r1, dx, dy);
+    const uint64_t validm = pair_valid(a, pos0, s.last, bound);
+    const PairGrad g = pair_grad<DEPTH>(s, a, validm, r1, cb, [=] { return z; });
+    v.v0 = fmaf(g.q, dx, v.v0); v.v1 = fmaf(g.q, dy, v.v1);
+    v.v2 = fmaf(g.q, a.ev.dxx, v.v2); v.v3 = fmaf(g.q, a.ev.dxy, v.v3); v.v4 = fmaf(g.q, a.ev.dyy, v.v4);
+    v.v5 += g.q;
+    v.v6 = fmaf(g.dch, s.dL0, v.v6); v.v7 = fmaf(g.dch, s.dL1, v.v7); v.v8 = fmaf(g.dch, s.dL2, v.v8);
+    if constexpr (DEPTH) *v9 = fmaf(g.dch, s.dLd, *v9);
     return validm;
 }
 
@@ -941,10 +933,10 @@ __global__ __launch_bounds__(64) void blend_backward_tile_kernel(ViewParams vp, 
     const unsigned long long trace_t0 = __builtin_amdgcn_s_memrealtime();
 #endif
     uint32_t cnt_visits = 0, cnt_steps = 0, cnt_lanes = 0, cnt_hits = 0;       // COUNT only
-    BwdQuad q0, q1, q2, q3;
+    BwdPix q0, q1, q2, q3;
     uint32_t ql0, ql1, ql2, ql3;                           // wave-uniform: last blended position per quadrant
     {
-        auto init = [&](BwdQuad& s, int qi) -> uint32_t {
+        auto init = [&](BwdPix& s, int qi) -> uint32_t {
             const int px = bx + (qi & 1) * 8, py = by + (qi >> 1) * 8;
             const bool inside = px < vp.W && py < vp.H;
             const size_t pix = (size_t)py * vp.W + px;
@@ -963,9 +955,8 @@ __global__ __launch_bounds__(64) void blend_backward_tile_kernel(ViewParams vp, 
         ql0 = init(q0, 0); ql1 = init(q1, 1); ql2 = init(q2, 2); ql3 = init(q3, 3);
     }
     const uint32_t tile_last = max(max(ql0, ql1), max(ql2, ql3));
-    // the nine lanes that issue the per-entry atomics (depth: ten, lane 3 delivers component 9)
-    const bool alane = DEPTH ? lane < 16 && (!(lane & 2) || lane == 2 || lane == 3) : lane < 16 && (!(lane & 2) || lane == 2);
-    const uint32_t aoff = DEPTH ? row_reduce_component10(lane) : row_reduce_component(lane);
+    const bool alane = IS_ATOMIC_LANE(DEPTH, lane);
+    const uint32_t aoff = row_reduce_component<DEPTH>(lane);
     const int xrow16 = (lane ^ 16) << 2, xrow32 = (lane ^ 32) << 2;     // ds_bpermute byte addresses of the partner lanes
 
     const int nb = ((int)tile_last + WB - 1) / WB;
@@ -999,49 +990,46 @@ __global__ __launch_bounds__(64) void blend_backward_tile_kernel(ViewParams vp, 
             const uint32_t pos0 = (uint32_t)(base + e);   // 0-based position in the tile list
             const float4 r0 = s_r0[e], r1 = s_r1[e];
             const float2 bl = *reinterpret_cast<const float2*>(&s_bi[e]);      // {blue, sign_test_bound}: one 8-byte read
-            const float cb = bl.x;
             const float dx = r0.x - bxf, dy = r0.y - byf;
             BwdSums v = {0, 0, 0, 0, 0, 0, 0, 0, 0};
             float v9 = 0.f;                                // depth variant: the tenth sum
+            float* const pv9 = DEPTH ? &v9 : nullptr;
+            const float z = DEPTH ? s_bi[e].w : 0.f;       // depth variant: the entry's view depth
             uint64_t any = 0;
+            if constexpr (COUNT) cnt_visits += 1u;
+            // the four quadrants, one list for every variant: DEPTH hands z and the tenth sum to the step, COUNT tallies its result
+            if (h0 & bit) {
+                const uint64_t m = bwd_quad_step<DEPTH>(q0, v, pv9, r0, r1, bl.x, bl.y, dx, dy, pos0, z);
+                any |= m;
+                if constexpr (COUNT) { cnt_steps += 1u; cnt_lanes += (uint32_t)__popcll(m); }
+            }
+            if (h1 & bit) {
+                const uint64_t m = bwd_quad_step<DEPTH>(q1, v, pv9, r0, r1, bl.x, bl.y, dx - 8.0f, dy, pos0, z);
+                any |= m;
+                if constexpr (COUNT) { cnt_steps += 1u; cnt_lanes += (uint32_t)__popcll(m); }
+            }
+            if (h2 & bit) {
+                const uint64_t m = bwd_quad_step<DEPTH>(q2, v, pv9, r0, r1, bl.x, bl.y, dx, dy - 8.0f, pos0, z);
+                any |= m;
+                if constexpr (COUNT) { cnt_steps += 1u; cnt_lanes += (uint32_t)__popcll(m); }
+            }
+            if (h3 & bit) {
+                const uint64_t m = bwd_quad_step<DEPTH>(q3, v, pv9, r0, r1, bl.x, bl.y, dx - 8.0f, dy - 8.0f, pos0, z);
+                any |= m;
+                if constexpr (COUNT) { cnt_steps += 1u; cnt_lanes += (uint32_t)__popcll(m); }
+            }
             if constexpr (COUNT) {
-                uint64_t m;
-                cnt_visits += 1u;
-                if (h0 & bit) { m = bwd_quad_step(q0, v, r0, r1, cb, bl.y, dx, dy, pos0); any |= m; cnt_steps += 1u; cnt_lanes += (uint32_t)__popcll(m); }
-                if (h1 & bit) { m = bwd_quad_step(q1, v, r0, r1, cb, bl.y, dx - 8.0f, dy, pos0); any |= m; cnt_steps += 1u; cnt_lanes += (uint32_t)__popcll(m); }
-                if (h2 & bit) { m = bwd_quad_step(q2, v, r0, r1, cb, bl.y, dx, dy - 8.0f, pos0); any |= m; cnt_steps += 1u; cnt_lanes += (uint32_t)__popcll(m); }
-                if (h3 & bit) { m = bwd_quad_step(q3, v, r0, r1, cb, bl.y, dx - 8.0f, dy - 8.0f, pos0); any |= m; cnt_steps += 1u; cnt_lanes += (uint32_t)__popcll(m); }
                 if (any) cnt_hits += 1u;
                 continue;
             }
-            if constexpr (DEPTH) {
-                const float z = s_bi[e].w;                 // the entry's view depth
-                if (h0 & bit) any |= bwd_quad_step<true>(q0, v, r0, r1, cb, bl.y, dx, dy, pos0, z, &v9);
-                if (h1 & bit) any |= bwd_quad_step<true>(q1, v, r0, r1, cb, bl.y, dx - 8.0f, dy, pos0, z, &v9);
-                if (h2 & bit) any |= bwd_quad_step<true>(q2, v, r0, r1, cb, bl.y, dx, dy - 8.0f, pos0, z, &v9);
-                if (h3 & bit) any |= bwd_quad_step<true>(q3, v, r0, r1, cb, bl.y, dx - 8.0f, dy - 8.0f, pos0, z, &v9);
-            } else {
-                if (h0 & bit) any |= bwd_quad_step(q0, v, r0, r1, cb, bl.y, dx, dy, pos0);
-                if (h1 & bit) any |= bwd_quad_step(q1, v, r0, r1, cb, bl.y, dx - 8.0f, dy, pos0);
-                if (h2 & bit) any |= bwd_quad_step(q2, v, r0, r1, cb, bl.y, dx, dy - 8.0f, pos0);
-                if (h3 & bit) any |= bwd_quad_step(q3, v, r0, r1, cb, bl.y, dx - 8.0f, dy - 8.0f, pos0);
-            }
             if (any == 0) continue;                        // no lane contributed: nothing to reduce
-            // ---- one 64-lane reduction per (tile, Gaussian): rows by DPP (row_reduce_scatter9), then the four rows
-            // through the LDS crossbar (ds_bpermute lane ^ 16, lane ^ 32: two adds on the VALU; v_permlane16/32_swap are
-            // multi-cycle there).  Lanes 0,1,4,5,8,9,12,13 then hold components 0..7 and lane 2 component 8 (depth: lane 3
-            // component 9): one atomic instruction; the record id is wave-uniform (scalar address arithmetic).
-            {
-                float rowv;
-                if constexpr (DEPTH) rowv = row_reduce_scatter10(v, v9);
-                else rowv = row_reduce_scatter9(v);
-                const float outv = cross_row_allreduce_bperm(rowv, xrow16, xrow32);
-                // (record id through v_readlane of a register copy and a scalar-base atomic — no 64-bit VALU multiply-add —
-                //  were measured: no difference, 357..382 us for all four combinations)
-                const uint32_t gid = __builtin_amdgcn_readfirstlane(__float_as_uint(s_bi[e].z));
-                grad_acc_t* gdst = (grad_acc_t*)grad_out + (size_t)gid * GRAD_REC_FLOATS;
-                if (alane) unsafeAtomicAdd(gdst + aoff, (grad_acc_t)outv);
-            }
+            // one 64-lane reduction per (tile, Gaussian), the four rows through the LDS crossbar (ds_bpermute lane ^ 16,
+            // lane ^ 32: two adds on the VALU; v_permlane16/32_swap are multi-cycle there).  Lanes 0,1,4,5,8,9,12,13 then hold
+            // components 0..7 and lane 2 component 8 (depth: lane 3 component 9).
+            // (record id through v_readlane of a register copy and a scalar-base atomic — no 64-bit VALU multiply-add —
+            //  were measured: no difference, 357..382 us for all four combinations)
+            reduce_and_add<DEPTH>(v, v9, [=](float x) { return cross_row_allreduce_bperm(x, xrow16, xrow32); },
+                                  [=] { return __float_as_uint(s_bi[e].z); }, (grad_acc_t*)grad_out, alane, aoff);
         }
     }
     if constexpr (COUNT) {
