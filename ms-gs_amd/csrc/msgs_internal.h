@@ -110,7 +110,7 @@ struct SlabHeader {
 static_assert(sizeof(SlabHeader) == 64, "SlabHeader layout");
 
 struct GeomLayout {
-    size_t rec, binrec, tiles, key, flags, weight, order, offs, nvalid, skey, slab_hdr, occ_hdr, occ_cut, offs_b, scan_b, litrec, total;
+    size_t rec, binrec, tiles, key, flags, weight, order, offs, nvalid, skey, slab_hdr, occ_hdr, occ_cut, offs_b, scan_b, litrec, shjac, total;
     __host__ __device__ explicit GeomLayout(int64_t P) {
         size_t o = 0;
         rec = o;    o = align256(o + sizeof(GaussRec) * P);
@@ -132,6 +132,8 @@ struct GeomLayout {
         offs_b = o; o = align256(o + 4 * P);        // slab B: per depth rank, instances in open tiles -> their exclusive scan
         scan_b = o; o = align256(o + 8 * (size_t)((P + SLAB_SCAN_CHUNK - 1) / SLAB_SCAN_CHUNK + 2));   // block totals of that scan
         litrec = o; o = align256(o + 16 * P);       // verification mode (literal.hip): raw conic A, B, C and effective opacity
+        shjac = o;  o = align256(o + 36 * P);       // SH direction Jacobian J[c][j] = sum_k dB_k/dd_j sh[k][c] (K1 -> K9, preprocess.hip):
+                                                    // nine floats per Gaussian as two planes of P float4 and one of P floats
         total = o;
     }
 };

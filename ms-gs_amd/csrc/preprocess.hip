@@ -9,7 +9,9 @@
 // Replaces the per-Gaussian kernels of the reference's un-vendored CUDA module
 // (/root/reference/.gitmodules:4-6; call site gaussian_renderer/__init__.py:94-108).
 //
-// Both kernels are HBM-streaming (309 B in / ~80 B out per Gaussian forward at SH degree 3).
+// Both kernels are HBM-streaming (309 B in / ~80 B out per Gaussian forward at SH degree 3, + 36 B out for the SH direction
+// Jacobian; backward 605 - 156 B per rendered Gaussian: the 192-byte SH row is read by the forward only, the backward takes
+// the direction term of dL/dmeans3D from the 36-byte Jacobian the forward left — "SH direction Jacobian" below).
 // One thread per Gaussian; floating-point contraction is OFF in this file so that every float32
 // operation is individually rounded and the discrete outputs (radii, tile rects, depth sort keys)
 // are bit-reproducible against the CPU oracle.
@@ -183,12 +185,129 @@ __device__ __forceinline__ void sh_basis(int deg, float x, float y, float z, flo
     }
 }
 
+// The basis again, with its derivatives by the (normalised) direction: coef(k, B_k, dB_k/dx, dB_k/dy, dB_k/dz) for the
+// coefficients K_LO <= k < K_HI of the active degree, k ascending.  ONE table for both users — K9's dSH rows (B_k) and direction
+// gradient of the per-thread path, and K1's SH direction Jacobian (the derivatives) — so that the two can never drift apart.
+template <int K_LO, int K_HI, class F>
+__device__ __forceinline__ void sh_coef_table(int deg, float x, float y, float z, F&& coef) {
+    auto at = [&](int k, float basis, float bx, float by, float bz) {
+        if (k >= K_LO && k < K_HI) coef(k, basis, bx, by, bz);
+    };
+    at(0, SH_C0, 0.f, 0.f, 0.f);
+    if (deg > 0) {
+        at(1, -SH_C1 * y, 0.f, -SH_C1, 0.f);
+        at(2, SH_C1 * z, 0.f, 0.f, SH_C1);
+        at(3, -SH_C1 * x, -SH_C1, 0.f, 0.f);
+        if (deg > 1) {
+            const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
+            at(4, SH_C2[0] * xy, SH_C2[0] * y, SH_C2[0] * x, 0.f);
+            at(5, SH_C2[1] * yz, 0.f, SH_C2[1] * z, SH_C2[1] * y);
+            at(6, SH_C2[2] * (2.f * zz - xx - yy), SH_C2[2] * -2.f * x, SH_C2[2] * -2.f * y, SH_C2[2] * 4.f * z);
+            at(7, SH_C2[3] * xz, SH_C2[3] * z, 0.f, SH_C2[3] * x);
+            at(8, SH_C2[4] * (xx - yy), SH_C2[4] * 2.f * x, SH_C2[4] * -2.f * y, 0.f);
+            if (deg > 2) {
+                at(9, SH_C3[0] * y * (3.f * xx - yy), SH_C3[0] * 6.f * xy, SH_C3[0] * (3.f * xx - 3.f * yy), 0.f);
+                at(10, SH_C3[1] * xy * z, SH_C3[1] * yz, SH_C3[1] * xz, SH_C3[1] * xy);
+                at(11, SH_C3[2] * y * (4.f * zz - xx - yy), SH_C3[2] * -2.f * xy, SH_C3[2] * (4.f * zz - xx - 3.f * yy), SH_C3[2] * 8.f * yz);
+                at(12, SH_C3[3] * z * (2.f * zz - 3.f * xx - 3.f * yy), SH_C3[3] * -6.f * xz, SH_C3[3] * -6.f * yz, SH_C3[3] * (6.f * zz - 3.f * xx - 3.f * yy));
+                at(13, SH_C3[4] * x * (4.f * zz - xx - yy), SH_C3[4] * (4.f * zz - 3.f * xx - yy), SH_C3[4] * -2.f * xy, SH_C3[4] * 8.f * xz);
+                at(14, SH_C3[5] * z * (xx - yy), SH_C3[5] * 2.f * xz, SH_C3[5] * -2.f * yz, SH_C3[5] * (xx - yy));
+                at(15, SH_C3[6] * x * (xx - 3.f * yy), SH_C3[6] * (3.f * xx - 3.f * yy), SH_C3[6] * -6.f * xy, 0.f);
+            }
+        }
+    }
+}
+
+// ---- SH direction Jacobian (GeomLayout::shjac) ----
+// The colour reaches dL/dmeans3D through the direction d only:  dL/dd_j = sum_k dB_k/dd_j (sum_c sh[k][c] g_c),  g = dL/drgb
+// with the clamped channels zeroed (Q8).  Summed over k first this is  sum_c J[c][j] g_c  with
+//   J[c][j] = sum_k dB_k/dd_j sh[k][c]      (k below the active degree's coefficient count; all zero at degree 0)
+// — nine floats that depend on the forward's inputs alone.  K1 has the SH row and the direction in hand and forms J; K9 reads
+// 48 bytes instead of fetching the 192-byte row a second time.
+//
+// Where K1 stages the SH rows through LDS, and so where J exists: a function of the call's inputs only, the same in K1 and K9.
+__device__ __forceinline__ bool sh_jacobian_stored(const msgs_gaussians_t& g, const ViewParams& vp) {
+    return g.raw_params != 0 || (g.shs != nullptr && vp.sh_coeffs == 16);
+}
+
+struct ShJacobian { float j[3][3]; };      // [channel c][direction component j]
+
+// GeomLayout::shjac: the nine floats of Gaussian i in row-major order as two planes of P float4 (entries 0..3, 4..7) and one of P
+// floats (entry 8) — 36 bytes per Gaussian, every wave access one contiguous run.  A wave of K1 that renders anything writes
+// the rows of ALL its lanes (zeros for the others): whole cache lines leave the chip; a wave that renders nothing writes
+// nothing.  Measured at C3, K1 over the parent's 81 us: + 13 us with three padded float4 planes written for the rendered
+// Gaussians only (partial lines), + 7.5 us with the same planes written whole, + 8.5 us with this 36-byte form written
+// partially, + 4 us as built, + 0 with J formed and not stored — the cost is the store traffic alone
+// (profiles/k9_sh_jacobian_notes.md).  K9 reads the rows of the rendered Gaussians only.
+
+// K1: the coefficients K_LO .. K_HI - 1 of one Gaussian (row[3 (k - K_ROW) + c], a half row in LDS) enter its colour — the terms
+// of sh_channel in their order, (C * poly) * coefficient — and J: k ascending, one fmaf chain per entry
+template <int K_LO, int K_HI, int K_ROW>
+__device__ __forceinline__ void sh_colour_accumulate(float* rgb, ShJacobian& J, int deg, float x, float y, float z,
+                                                     const float* row) {
+    sh_coef_table<K_LO, K_HI>(deg, x, y, z, [&](int k, float basis, float bx, float by, float bz) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float v = row[3 * (k - K_ROW) + c];
+            rgb[c] = rgb[c] + basis * v;
+            J.j[c][0] = fmaf(bx, v, J.j[c][0]);
+            J.j[c][1] = fmaf(by, v, J.j[c][1]);
+            J.j[c][2] = fmaf(bz, v, J.j[c][2]);
+        }
+    });
+}
+
+__device__ __forceinline__ void sh_jacobian_store(char* geom, const GeomLayout& L, int P, int i, const ShJacobian& J) {
+    float4* pl = reinterpret_cast<float4*>(geom + L.shjac);
+    pl[i] = make_float4(J.j[0][0], J.j[0][1], J.j[0][2], J.j[1][0]);
+    pl[(size_t)P + i] = make_float4(J.j[1][1], J.j[1][2], J.j[2][0], J.j[2][1]);
+    reinterpret_cast<float*>(pl + 2 * (size_t)P)[i] = J.j[2][2];
+}
+
+__device__ __forceinline__ void sh_jacobian_load(const char* geom, const GeomLayout& L, int P, int i, ShJacobian& J) {
+    const float4* pl = reinterpret_cast<const float4*>(geom + L.shjac);
+    const float4 a = pl[i], b = pl[(size_t)P + i];
+    J.j[0][0] = a.x; J.j[0][1] = a.y; J.j[0][2] = a.z; J.j[1][0] = a.w;
+    J.j[1][1] = b.x; J.j[1][2] = b.y; J.j[2][0] = b.z; J.j[2][1] = b.w;
+    J.j[2][2] = reinterpret_cast<const float*>(pl + 2 * (size_t)P)[i];
+}
+
+// K9: dL/dd_j = sum_c J[c][j] g_c, c = 0, 1, 2 in this order
+__device__ __forceinline__ void sh_ddir_from_jacobian(const ShJacobian& J, const float* g, float* ddir) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) ddir[j] = fmaf(J.j[2][j], g[2], fmaf(J.j[1][j], g[1], J.j[0][j] * g[0]));
+}
+
+// the view direction of a Gaussian as K1 and K9 both form it (the same expressions: the same bits)
+struct ViewDir { float x, y, z, len; };
+__device__ __forceinline__ ViewDir view_dir(const float* p, const float* campos) {
+    const float dox = p[0] - campos[0], doy = p[1] - campos[1], doz = p[2] - campos[2];
+    const float len = sqrtf(dox * dox + doy * doy + doz * doz);
+    return {dox / len, doy / len, doz / len, len};
+}
+
+// dL/d(p - campos) from dL/dd, d = (p - campos) / |p - campos|
+__device__ __forceinline__ void direction_backward(const ViewDir& d, const float* ddir, float* dm) {
+    const float dotv = d.x * ddir[0] + d.y * ddir[1] + d.z * ddir[2];
+    dm[0] = (ddir[0] - d.x * dotv) / d.len;
+    dm[1] = (ddir[1] - d.y * dotv) / d.len;
+    dm[2] = (ddir[2] - d.z * dotv) / d.len;
+}
+
+// Q8: a colour channel that was clamped at zero passes no gradient (GeomLayout::flags bits 0..2)
+__device__ __forceinline__ void clamp_mask(float* dcolr, uint32_t fl) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+        if (fl & (1u << c)) dcolr[c] = 0.f;
+}
+
 // ---------------------------------------------------------------------------------------------
 // Wave-cooperative movement of 192-byte SH rows (K = 16 coefficients x 3 channels) between HBM and
 // LDS.  A thread-per-Gaussian float4 access at a 192-B stride touches 64 different cache lines per
 // instruction (TA-bound, measured 25 % of HBM rate); here n4 consecutive lanes move one row's n4
 // float4 so every instruction covers 64/n4 whole rows.  LDS rows have a stride of 49 floats so the
-// later one-thread-per-row 4-byte accesses are bank-conflict free.
+// later one-thread-per-row 4-byte accesses are bank-conflict free.  (K1 loads rows and K9 stores gradient rows this way; K9
+// loads none: it takes the direction term from the SH direction Jacobian above.)
 // ---------------------------------------------------------------------------------------------
 // LDS hand-off between lanes of ONE wave: the hardware executes a wave's LDS operations in order; this
 // keeps the compiler from reordering across the phase boundary as well.
@@ -203,22 +322,6 @@ constexpr int ROW_LDS = 49;        // floats per row in LDS
 constexpr int K9_STAGE_ROWS = 32;  // Gaussians of a wave whose SH rows are in LDS at a time (preprocess_backward_kernel)
 
 __device__ __forceinline__ int sh_row_float4s(int deg) { return deg == 0 ? 1 : deg == 1 ? 3 : deg == 2 ? 7 : 12; }
-
-// rows listed in idx[0..nrow) (lane numbers inside the wave) are loaded from g_rows + lane*48 into LDS row (lane - row0)
-__device__ __forceinline__ void coop_load_rows(float* lds_rows, const float* g_rows, const uint8_t* idx, int nrow,
-                                               int n4, int lane, int row0 = 0) {
-    const int rpi = 64 / n4;
-    const int sub = lane / n4, c = lane - sub * n4;
-    for (int it = 0; it * rpi < nrow; ++it) {
-        const int slot = it * rpi + sub;
-        if (sub < rpi && slot < nrow) {
-            const int sl = idx[slot];
-            const float4 v = *reinterpret_cast<const float4*>(g_rows + (size_t)sl * ROW_F + 4 * c);
-            float* d = lds_rows + (sl - row0) * ROW_LDS + 4 * c;
-            d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
-        }
-    }
-}
 
 // half rows: float4s [f4_first, f4_first + n4) of every listed row into LDS rows of HALF_LDS floats.  K1 keeps only
 // 24 coefficients-floats per Gaussian in LDS at a time: 25.6 KB per workgroup instead of 50 KB, i.e. six workgroups per CU
@@ -328,25 +431,6 @@ __device__ __forceinline__ void coop_load_split_half_listed(float* lds_rows, con
             float* d = lds_rows + sl * HALF_LDS + 3 * c;
             // half 0: lane c holds coefficient c (c = 0: dc); half 1: coefficient 8 + c
             const float* src = (half == 0 && c == 0) ? dc + gi * 3 : rest + gi * 45 + 3 * (8 * half + c - 1);
-            const msgs_f3 v = *reinterpret_cast<const msgs_f3_u*>(src);
-            d[0] = v.x; d[1] = v.y; d[2] = v.z;
-        }
-    }
-}
-
-// Whole rows [dc(3) | rest(45)] of the listed Gaussians (K9: the rendered ones) into LDS rows of ROW_LDS floats: sixteen lanes
-// serve one row with 12-byte loads (fifteen on the rest row, one on dc), four rows per instruction.  idx[0..nlisted) = wave-local
-// row numbers, LDS row = number - row0.
-__device__ __forceinline__ void coop_load_split_rows_listed(float* lds_rows, const float* dc, const float* rest, int wave_first,
-                                                            const uint8_t* idx, int nlisted, int lane, int row0) {
-    const int sub = lane >> 4, c = lane & 15;
-    for (int it = 0; it * 4 < nlisted; ++it) {
-        const int slot = it * 4 + sub;
-        if (slot < nlisted) {
-            const int sl = idx[slot];
-            const size_t gi = (size_t)wave_first + sl;
-            float* d = lds_rows + (sl - row0) * ROW_LDS + 3 * c;
-            const float* src = c == 0 ? dc + gi * 3 : rest + gi * REST_F + 3 * (c - 1);
             const msgs_f3 v = *reinterpret_cast<const msgs_f3_u*>(src);
             d[0] = v.x; d[1] = v.y; d[2] = v.z;
         }
@@ -488,7 +572,7 @@ __device__ __forceinline__ void coop_adam_split_rows(const float* lds_rows, floa
 // `shs`): whole 48-float rows in LDS.  false: every other input form; a concatenated K = 16 `shs` goes through LDS in
 // two 24-float halves.
 template <bool SPLIT_ROWS>
-__global__ __launch_bounds__(256) void preprocess_kernel(ViewParams vp, msgs_gaussians_t g,
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void preprocess_kernel(ViewParams vp, msgs_gaussians_t g,
                                                          int32_t* __restrict__ radii,
                                                          float* __restrict__ pixel_sizes,
                                                          char* __restrict__ geom, ZeroJob zj,
@@ -580,22 +664,19 @@ __global__ __launch_bounds__(256) void preprocess_kernel(ViewParams vp, msgs_gau
     // chained mode may also hand over the concatenated `shs` the reference built: 16-byte aligned 192-byte rows, of
     // which only the surviving Gaussians' are fetched (the split leaves are read as one run per wave, all 64 rows)
     const bool split_in = SPLIT_ROWS && raw && g.shs == nullptr;
-    const bool staged_sh = raw || (g.shs != nullptr && vp.sh_coeffs == 16);   // wave-uniform
+    const bool staged_sh = sh_jacobian_stored(g, vp);                         // wave-uniform (raw, or a K = 16 `shs`)
     float rgb[3] = {0.f, 0.f, 0.f};
     float dirx = 0.f, diry = 0.f, dirz = 0.f;
     if (alive) {
-        const float dx = p[0] - cm.cam[0], dy = p[1] - cm.cam[1], dz = p[2] - cm.cam[2];
-        const float len = sqrtf(dx * dx + dy * dy + dz * dz);
-        dirx = dx / len; diry = dy / len; dirz = dz / len;
+        const ViewDir d = view_dir(p, cm.cam);
+        dirx = d.x; diry = d.y; dirz = d.z;
     }
-    if (split_in || staged_sh) {
+    if (staged_sh) {
         const uint64_t need = __ballot(alive);
         if (alive) s_idx[wv][__popcll(need & ((1ull << lane) - 1ull))] = (uint8_t)lane;
         const int wave_first = blockIdx.x * blockDim.x + wv * 64;
-        const int ncoef = (vp.sh_degree + 1) * (vp.sh_degree + 1);
-        float basis[16];
-        sh_basis(vp.sh_degree, dirx, diry, dirz, basis);
         const int n4_total = sh_row_float4s(vp.sh_degree);
+        ShJacobian J = {};                                 // what K9 needs of this row (sh_jacobian_stored): formed while it is here
         for (int half = 0; half * HALF_F4 < n4_total; ++half) {
             wave_lds_fence();                              // s_idx visible / previous half consumed
             if (split_in) {
@@ -608,17 +689,24 @@ __global__ __launch_bounds__(256) void preprocess_kernel(ViewParams vp, msgs_gau
             }
             wave_lds_fence();
             if (alive) {
+                // colour and Jacobian from the half row, k ascending.  Basis and derivatives are formed per half, from a
+                // direction the compiler cannot see through: hoisted out of the loop, the values of both halves would be
+                // live at once (102 registers, four waves per SIMD instead of six)
                 const float* row = (const float*)&s_rows[wv][lane * HALF_LDS];
-#pragma unroll
-                for (int k = 0; k < 8; ++k) {
-                    const int kk = 8 * half + k;
-                    if (kk < ncoef) {
-#pragma unroll
-                        for (int c = 0; c < 3; ++c) rgb[c] = rgb[c] + basis[kk] * row[3 * k + c];
-                    }
+                asm volatile("" : "+v"(dirx), "+v"(diry), "+v"(dirz));
+                // (four coefficients at a time, the scheduler held to that: 80 registers without a spill)
+                if (half == 0) {
+                    sh_colour_accumulate<0, 4, 0>(rgb, J, vp.sh_degree, dirx, diry, dirz, row);
+                    __builtin_amdgcn_sched_barrier(0);
+                    sh_colour_accumulate<4, 8, 0>(rgb, J, vp.sh_degree, dirx, diry, dirz, row);
+                } else {
+                    sh_colour_accumulate<8, 12, 8>(rgb, J, vp.sh_degree, dirx, diry, dirz, row);
+                    __builtin_amdgcn_sched_barrier(0);
+                    sh_colour_accumulate<12, 16, 8>(rgb, J, vp.sh_degree, dirx, diry, dirz, row);
                 }
             }
         }
+        if (in_range && need != 0) sh_jacobian_store(geom, L, P, i, J);   // (whole waves: see ShJacobian)
     } else if (alive && !(g.colors_precomp && !raw)) {
         const float* sh = g.shs + (size_t)3 * vp.sh_coeffs * i;
 #pragma unroll
@@ -725,7 +813,8 @@ __device__ __forceinline__ float (&camera_dir_lds())[3][256] {
 }
 
 // (held to 96 registers = 5 waves per SIMD: measured 116 us with the compiler's 102 registers / 4 waves, 112 us with 5 waves and
-//  one spilled register, 125 us with 6 waves and 22 spills; 121 us before the rows were staged in two runs)
+//  one spilled register, 125 us with 6 waves and 22 spills; 121 us before the rows were staged in two runs — all with the SH
+//  row fetch.  Without it the kernel needs 82-90 registers and no spill at 5 waves, 83 us; 6 waves would still spill 1-12)
 // TEXTBOOK = true (msgs_backward_per_gaussian, the K8 + K9 isolation entry of the parity tests): grad_rec is NOT this
 // library's record of monomial sums but [P,9] doubles holding the textbook 2-D gradients {dL/dmean2D x, y (NDC-ish units),
 // dL/dconic A, B, C, dL/dopacity_eff, dL/drgb[3]}; the per-Gaussian factors that turn the one into the other are skipped
@@ -749,11 +838,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CAMERA ? 4 
                                                                   msgs_grads_t grads,
                                                                   std::conditional_t<CAMERA, CamPartials, AdamInBackward> ad) {
     static_assert(!(CAMERA && ADAM), "camera gradients are not offered with the optimizer step in the backward");
-    // 32 rows per wave: the SH rows of a wave's 64 Gaussians pass through LDS in two runs of 32 (below).  25 KB per workgroup
+    // 32 rows per wave: the SH gradient rows of a wave's 64 Gaussians pass through LDS in two runs of 32 (below).  25 KB per workgroup
     // instead of 50: the kernel is latency-bound and its time follows the occupancy (measured at C3 with 1 / 2 / 3 workgroups
     // per CU: 252 / 147 / 121 us)
     __shared__ float s_rows[4][K9_STAGE_ROWS * ROW_LDS];
-    __shared__ uint8_t s_idx[4][64];
     const int P = g.P;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -773,8 +861,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CAMERA ? 4 
     // SH rows in / dSH rows out through LDS with coalesced wave-cooperative transfers (K == 16 only;
     // other layouts take the direct per-thread path)
     const bool raw = g.raw_params != 0;
-    const bool split_in = raw && g.shs == nullptr;
-    const bool staged_sh = raw || (g.shs != nullptr && grads.dL_dshs != nullptr && K == 16);   // wave-uniform
+    // K1 left the SH direction Jacobian wherever it staged the rows (sh_jacobian_stored): the direction gradient then comes from
+    // those nine floats and no SH coefficient is read here
+    const bool use_jac = sh_jacobian_stored(g, vp);                                            // wave-uniform
+    const bool staged_sh = use_jac && (raw || grads.dL_dshs != nullptr);                       // rows to write through LDS
+    const bool do_colour = !g.colors_precomp;                                                  // wave-uniform
     // factored SH gradient (view-parallel exchange, msgs_sh_grad_from_views): dL/dSH of one view is the outer product
     // basis(direction) x dL/drgb, so only the (clamp-masked) dL/drgb is delivered and the 192-byte rows are not written
     const bool factored_sh = !ADAM && raw && grads.dL_dfeatures_dc == nullptr;
@@ -783,11 +874,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CAMERA ? 4 
     const bool accum = !ADAM && grads.accumulate != 0;
     const int wave_first = blockIdx.x * blockDim.x + wv * 64;
     const uint64_t live = __ballot(rendered);
-    if (staged_sh) {                         // list of the rendered lanes, ascending: the rows to fetch
-        if (rendered) s_idx[wv][__popcll(live & ((1ull << lane) - 1ull))] = (uint8_t)lane;
-    }
     uint32_t fl = 0;
     float p[3] = {0.f, 0.f, 0.f};
+    float shdm[3] = {0.f, 0.f, 0.f};         // the SH share of dL/dmeans3D where it comes from the Jacobian (added last, as ever)
     // CAMERA: dL/dt (view-space point), dL/dh_{0,1,3} (clip-space point) and (J dT)[c][k] = dL/dWr through T = J Wr (the
     // un-normalised SH direction gradient dL/d(p - campos) goes to LDS where colour_backward forms it)
     float cdt[3] = {0.f, 0.f, 0.f}, cdh[3] = {0.f, 0.f, 0.f}, cjt[9] = {};
@@ -829,6 +918,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CAMERA ? 4 
         dcolr[0] = gb.z; dcolr[1] = gb.w; dcolr[2] = gc.x;
         fl = flags[i];
         p[0] = g.means3D[3 * i]; p[1] = g.means3D[3 * i + 1]; p[2] = g.means3D[3 * i + 2];
+        if (use_jac && do_colour) {
+            ShJacobian J;
+            sh_jacobian_load(geom, L, P, i, J);
+            clamp_mask(dcolr, fl);
+            float ddir[3];
+            sh_ddir_from_jacobian(J, dcolr, ddir);
+            const ViewDir d = view_dir(p, vp.campos);
+            direction_backward(d, ddir, shdm);
+        }
 
         float cov3D[6];
         float R[3][3], S[3] = {0.f, 0.f, 0.f};
@@ -1012,77 +1110,51 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CAMERA ? 4 
         } else if (lane < 24) {
             s_cam[wv][lane] = 0.0;
         }
-        float(&s_dir)[3][256] = camera_dir_lds();                          // (lanes not rendered: 0)
-        s_dir[0][threadIdx.x] = 0.f; s_dir[1][threadIdx.x] = 0.f; s_dir[2][threadIdx.x] = 0.f;
+        float(&s_dir)[3][256] = camera_dir_lds();                          // (lanes not rendered: 0; the per-thread path: below)
+        s_dir[0][threadIdx.x] = shdm[0]; s_dir[1][threadIdx.x] = shdm[1]; s_dir[2][threadIdx.x] = shdm[2];
     }
+    dmean[0] += shdm[0]; dmean[1] += shdm[1]; dmean[2] += shdm[2];        // (zero unless the Jacobian path formed it)
     // ---- colour backward (the last contribution to dL/dmean) ----
-    // sh: this Gaussian's 48 (or 3K) coefficients, dsh: where their gradient goes (the same LDS row when staged; nullptr = the
-    // factored path, rows not formed)
+    // staged rows: only the gradient row basis_k * dL/drgb_c is formed, in this Gaussian's LDS row (the direction term is in shdm)
+    auto colour_rows = [&](float* dsh) {
+        const ViewDir d = view_dir(p, vp.campos);
+        sh_coef_table<0, 16>(deg, d.x, d.y, d.z, [&](int k, float basis, float, float, float) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) dsh[k * 3 + c] = basis * dcolr[c];
+        });
+    };
+    // the per-thread path (K != 16): sh = this Gaussian's 3K coefficients, dsh = where their gradient goes (nullptr: not wanted)
     auto colour_backward = [&](const float* sh, float* dsh) {
-        {
+        clamp_mask(dcolr, fl);
+        const ViewDir d = view_dir(p, vp.campos);
+        float ddir[3] = {0.f, 0.f, 0.f};
+        sh_coef_table<0, 16>(deg, d.x, d.y, d.z, [&](int k, float basis, float bx, float by, float bz) {
+            float s = 0.f;
 #pragma unroll
-            for (int c = 0; c < 3; ++c)
-                if (fl & (1u << c)) dcolr[c] = 0.f;                                // Q8
-            const float dox = p[0] - vp.campos[0], doy = p[1] - vp.campos[1], doz = p[2] - vp.campos[2];
-            const float len = sqrtf(dox * dox + doy * doy + doz * doz);
-            const float x = dox / len, y = doy / len, z = doz / len;
-            float ddir[3] = {0.f, 0.f, 0.f};
-            // k-th coefficient: basis value and its direction derivatives
-            auto coef = [&](int k, float basis, float bx, float by, float bz) {
-                float s = 0.f;
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    const float shv = sh[k * 3 + c];          // read first: sh and dsh share the LDS row
-                    if (dsh) dsh[k * 3 + c] = basis * dcolr[c];
-                    s += shv * dcolr[c];
-                }
-                ddir[0] += bx * s; ddir[1] += by * s; ddir[2] += bz * s;
-            };
-            coef(0, SH_C0, 0.f, 0.f, 0.f);
-            if (deg > 0) {
-                coef(1, -SH_C1 * y, 0.f, -SH_C1, 0.f);
-                coef(2, SH_C1 * z, 0.f, 0.f, SH_C1);
-                coef(3, -SH_C1 * x, -SH_C1, 0.f, 0.f);
-                if (deg > 1) {
-                    const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
-                    coef(4, SH_C2[0] * xy, SH_C2[0] * y, SH_C2[0] * x, 0.f);
-                    coef(5, SH_C2[1] * yz, 0.f, SH_C2[1] * z, SH_C2[1] * y);
-                    coef(6, SH_C2[2] * (2.f * zz - xx - yy), SH_C2[2] * -2.f * x, SH_C2[2] * -2.f * y, SH_C2[2] * 4.f * z);
-                    coef(7, SH_C2[3] * xz, SH_C2[3] * z, 0.f, SH_C2[3] * x);
-                    coef(8, SH_C2[4] * (xx - yy), SH_C2[4] * 2.f * x, SH_C2[4] * -2.f * y, 0.f);
-                    if (deg > 2) {
-                        coef(9, SH_C3[0] * y * (3.f * xx - yy), SH_C3[0] * 6.f * xy, SH_C3[0] * (3.f * xx - 3.f * yy), 0.f);
-                        coef(10, SH_C3[1] * xy * z, SH_C3[1] * yz, SH_C3[1] * xz, SH_C3[1] * xy);
-                        coef(11, SH_C3[2] * y * (4.f * zz - xx - yy), SH_C3[2] * -2.f * xy, SH_C3[2] * (4.f * zz - xx - 3.f * yy), SH_C3[2] * 8.f * yz);
-                        coef(12, SH_C3[3] * z * (2.f * zz - 3.f * xx - 3.f * yy), SH_C3[3] * -6.f * xz, SH_C3[3] * -6.f * yz, SH_C3[3] * (6.f * zz - 3.f * xx - 3.f * yy));
-                        coef(13, SH_C3[4] * x * (4.f * zz - xx - yy), SH_C3[4] * (4.f * zz - 3.f * xx - yy), SH_C3[4] * -2.f * xy, SH_C3[4] * 8.f * xz);
-                        coef(14, SH_C3[5] * z * (xx - yy), SH_C3[5] * 2.f * xz, SH_C3[5] * -2.f * yz, SH_C3[5] * (xx - yy));
-                        coef(15, SH_C3[6] * x * (xx - 3.f * yy), SH_C3[6] * (3.f * xx - 3.f * yy), SH_C3[6] * -6.f * xy, 0.f);
-                    }
-                }
+            for (int c = 0; c < 3; ++c) {
+                const float shv = sh[k * 3 + c];
+                if (dsh) dsh[k * 3 + c] = basis * dcolr[c];
+                s += shv * dcolr[c];
             }
-            const int ncoef = (deg + 1) * (deg + 1);
-            if (dsh && !staged_sh)
-                for (int k = ncoef; k < K; ++k) { dsh[k * 3] = 0.f; dsh[k * 3 + 1] = 0.f; dsh[k * 3 + 2] = 0.f; }
-            const float dotv = x * ddir[0] + y * ddir[1] + z * ddir[2];
-            dmean[0] += (ddir[0] - x * dotv) / len;
-            dmean[1] += (ddir[1] - y * dotv) / len;
-            dmean[2] += (ddir[2] - z * dotv) / len;
-            if constexpr (CAMERA) {       // to LDS at once: no register stays live across the SH section
-                float(&s_dir)[3][256] = camera_dir_lds();
-                s_dir[0][threadIdx.x] = (ddir[0] - x * dotv) / len;
-                s_dir[1][threadIdx.x] = (ddir[1] - y * dotv) / len;
-                s_dir[2][threadIdx.x] = (ddir[2] - z * dotv) / len;
-            }
+            ddir[0] += bx * s; ddir[1] += by * s; ddir[2] += bz * s;
+        });
+        const int ncoef = (deg + 1) * (deg + 1);
+        if (dsh)
+            for (int k = ncoef; k < K; ++k) { dsh[k * 3] = 0.f; dsh[k * 3 + 1] = 0.f; dsh[k * 3 + 2] = 0.f; }
+        float dm[3];
+        direction_backward(d, ddir, dm);
+        dmean[0] += dm[0]; dmean[1] += dm[1]; dmean[2] += dm[2];
+        if constexpr (CAMERA) {
+            float(&s_dir)[3][256] = camera_dir_lds();
+            s_dir[0][threadIdx.x] = dm[0]; s_dir[1][threadIdx.x] = dm[1]; s_dir[2][threadIdx.x] = dm[2];
         }
     };
-    const bool do_colour = !g.colors_precomp;                 // wave-uniform
     if (do_colour && staged_sh) {
-        // the wave's SH rows in two runs of K9_STAGE_ROWS = 32 Gaussians: load (cooperative, coalesced) -> the lanes of that
-        // run work on their LDS row in place -> store (cooperative, coalesced)
+        // the wave's gradient rows in two runs of K9_STAGE_ROWS = 32 Gaussians: the lanes of that run fill their LDS row ->
+        // store (cooperative, coalesced).  Nothing is loaded; the factored path forms no rows at all.
         const int nfloat = 3 * (deg + 1) * (deg + 1);
 #pragma unroll 1
-        for (int h = 0; h < 64 / K9_STAGE_ROWS; ++h) {
+        for (int h = 0; h < 64 / K9_STAGE_ROWS && !factored_sh; ++h) {
             const int row0 = h * K9_STAGE_ROWS;
             const int first = wave_first + row0;
             const int nrow = min(K9_STAGE_ROWS, P - first);
@@ -1090,22 +1162,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CAMERA ? 4 
             const uint64_t live_h = (live >> row0) & ((1ull << K9_STAGE_ROWS) - 1ull);
             const bool mine = (lane / K9_STAGE_ROWS) == h;
             const int lrow = lane - row0;
-            wave_lds_fence();                                              // s_idx visible / previous run stored
-            if (split_in) {
-                if (live_h != 0)
-                    coop_load_split_rows_listed(s_rows[wv], g.features_dc, g.features_rest, wave_first,
-                                                s_idx[wv] + __popcll(live & ((1ull << row0) - 1ull)), __popcll(live_h), lane, row0);
-            } else {
-                coop_load_rows(s_rows[wv], g.shs + (size_t)wave_first * ROW_F,
-                               s_idx[wv] + __popcll(live & ((1ull << row0) - 1ull)), __popcll(live_h), sh_row_float4s(deg),
-                               lane, row0);
-            }
-            wave_lds_fence();
-            if (rendered && mine) {
-                float* row = &s_rows[wv][lrow * ROW_LDS];
-                colour_backward(row, factored_sh ? nullptr : row);
-            }
-            if (factored_sh) continue;
+            wave_lds_fence();                                              // previous run stored (CAMERA: its sums read)
+            if (rendered && mine) colour_rows(&s_rows[wv][lrow * ROW_LDS]);
             wave_lds_fence();
             if constexpr (ADAM)
                 coop_adam_split_rows(s_rows[wv], const_cast<float*>(g.features_dc), const_cast<float*>(g.features_rest), ad, i,
@@ -1116,7 +1174,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CAMERA ? 4 
             else
                 coop_store_rows(s_rows[wv], grads.dL_dshs + (size_t)first * ROW_F, nrow, live_h, nfloat, lane, accum);
         }
-    } else if (do_colour) {
+    } else if (do_colour && !use_jac) {
         // (direct per-thread rows, K != 16: accumulate mode is not offered on this path — msgs_backward refuses it)
         float* dsh = grads.dL_dshs && in_range ? grads.dL_dshs + (size_t)3 * K * i : nullptr;
         if (rendered) colour_backward(g.shs + (size_t)3 * K * i, dsh);
