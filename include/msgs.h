@@ -362,6 +362,26 @@ size_t msgs_bg_grad_scratch_bytes(int32_t width, int32_t height);
 int msgs_bg_grad(const msgs_view_t* view, const void* image_state, size_t image_bytes, const float* dL_dcolor,
                  float* dL_dbg, void* scratch, size_t scratch_bytes, void* stream);
 
+/* ---- absgrad: absolute screen-space gradients for densification (DESIGN.md SPEC M10, 4.10) ------ */
+/* msgs_absgrad: out_absgrad [P,3] float32 = {ln2 W sum_p |q_ip u_ip|, ln2 H sum_p |q_ip w_ip|, 0} — dL/dmean2D with the
+ * absolute value of every pixel's contribution summed instead of the signed one (AbsGS; gsplat's absgrad), in the units of
+ * msgs_grads_t.dL_dmeans2D.  A Gaussian that some pixels pull one way and others the other cancels in dL_dmeans2D and not here;
+ * |absgrad| >= |dL_dmeans2D| componentwise, equality for a loss on one pixel, 0 for a Gaussian in no tile list.  One replay of
+ * the blend backward's walk over exactly the pairs msgs_backward* counts, with dL_ddepth / dL_dalpha (NULL = none) entering as
+ * they do there.  Reads what the forward of this view left in geom / binning / image_state (single pass, depth slabs or
+ * occlusion cut-off alike); independent of the msgs_backward* calls, before or behind them on the same stream.  `scratch`
+ * (>= msgs_absgrad_scratch_bytes(P), 8-byte aligned, no clearing needed) holds [P,2] doubles: float32 totals per (tile
+ * quadrant, entry) are added there, which is exact — the same bits on every run.  P == 0: nothing is launched. */
+size_t msgs_absgrad_scratch_bytes(int32_t P);
+int msgs_absgrad(const msgs_view_t* view, int32_t P,
+                 const void* geom, size_t geom_bytes,
+                 int64_t num_instances,
+                 const void* binning, size_t binning_bytes,
+                 const void* image_state, size_t image_bytes,
+                 const float* dL_dcolor, const float* dL_ddepth, const float* dL_dalpha,
+                 void* scratch, size_t scratch_bytes,
+                 float* out_absgrad, void* stream);
+
 /* msgs_backward_per_gaussian: the per-Gaussian half of msgs_backward ALONE (2-D covariance backward, projection, SH,
  * scale / quaternion chain — upstream's computeCov2DCUDA + preprocessCUDA backward, SURVEY 2.2 K8 + K9) on per-Gaussian
  * 2-D gradients supplied by the caller instead of the blend backward's sums: sums2d [P,9] DOUBLES (device) =

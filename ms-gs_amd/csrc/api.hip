@@ -805,6 +805,31 @@ int msgs_bg_grad(const msgs_view_t* view, const void* image_v, size_t image_byte
                            (double*)scratch, s));
     return debug_sync(view, s);
 }
+
+size_t msgs_absgrad_scratch_bytes(int32_t P) { return 2 * sizeof(double) * (size_t)(P > 0 ? P : 1); }
+
+int msgs_absgrad(const msgs_view_t* view, int32_t P, const void* geom_v, size_t geom_bytes, int64_t D, const void* binning_v,
+                 size_t binning_bytes, const void* image_v, size_t image_bytes, const float* dL_dcolor, const float* dL_ddepth,
+                 const float* dL_dalpha, void* scratch, size_t scratch_bytes, float* out_absgrad, void* stream) {
+    if (!view || P < 0 || D < 0 || view->image_width < 1 || view->image_height < 1) return MSGS_ERR_INVALID_ARG;
+    if (P == 0) return MSGS_OK;                                              // nothing to zero: out is [0, 3]
+    if (!out_absgrad || !dL_dcolor || !geom_v || !binning_v || !image_v || !scratch || !view->bg) return MSGS_ERR_INVALID_ARG;
+    if ((uintptr_t)scratch & 7) return MSGS_ERR_INVALID_ARG;                 // rows of doubles
+    const int W = view->image_width, H = view->image_height;
+    if (geom_bytes < msgs_geom_bytes(P) || binning_bytes < msgs_binning_bytes(D, W, H) || image_bytes < msgs_image_bytes(W, H) ||
+        scratch_bytes < msgs_absgrad_scratch_bytes(P))
+        return MSGS_ERR_CAPACITY;
+    hipStream_t s = (hipStream_t)stream;
+    const ViewParams vp = make_view_params(view);
+    const BinningLayout BL(D, vp.gx * vp.gy);
+    const ImageLayout IL(W, H);
+    const char* binning = (const char*)binning_v;
+    const char* image = (const char*)image_v;
+    HIP_TRY(launch_blend_absgrad(vp, P, (const char*)geom_v, (const uint32_t*)(binning + BL.ids), (const uint2*)(binning + BL.ranges),
+                                 (const float*)(image + IL.final_T), (const uint32_t*)(image + IL.n_contrib), dL_dcolor, dL_ddepth,
+                                 dL_dalpha, (double*)scratch, out_absgrad, s));
+    return debug_sync(view, s);
+}
 }  // extern "C"
 
 namespace {

@@ -1052,6 +1052,135 @@ __global__ __launch_bounds__(64) void blend_backward_tile_kernel(ViewParams vp, 
 }
 
 // ---------------------------------------------------------------------------------------------
+// Absgrad (DESIGN.md SPEC M10, 4.10; msgs_absgrad): sum_p |dL/dmean2D contribution of pixel p| per Gaussian, the densification
+// statistic of AbsGS.  The per-pixel terms exist only here, in front of the cross-pixel reduction, so this is ONE more replay of
+// the back-to-front walk of blend_backward_kernel (same staging, same quadrant lists, same pair_alpha / pair_valid / pair_grad,
+// hence the same pairs and the same q as the gradient itself) with a two-sum tail in the place of the nine-sum scatter:
+//     u = A' dx + Bh' dy,  w = C' dy + Bh' dx   (the log2-scaled conic of the staged record; r0.w holds 2 Bh')
+//     acc[id] += { sum_lanes |q u|, sum_lanes |q w| }
+// The factors ln2 W and ln2 H of dL/dmean2D (preprocess_backward_kernel) are applied once per Gaussian by absgrad_finish_kernel.
+// Opt-in: nothing of the default path calls or shares a kernel with it.
+// ---------------------------------------------------------------------------------------------
+// Two partial sums per lane -> their wave totals in lanes 0 (a) and 1 (b), a fixed tree: the lane-parity exchange leaves a on
+// the even and b on the odd lanes, three row steps and the cross-row all-reduce then serve both at once (4 DPP adds, 2 selects).
+__device__ __forceinline__ float wave_reduce_pair(float a, float b, int lane) {
+    const bool odd = lane & 1;
+    const float keep = odd ? b : a, send = odd ? a : b;
+    float c = keep + dpp_mov<0xB1>(send);     // quad_perm [1,0,3,2]
+    c += dpp_mov<0x4E>(c);                    // quad_perm [2,3,0,1]
+    c += dpp_mov<0x124>(c);                   // row_ror:4
+    c += dpp_mov<0x128>(c);                   // row_ror:8: every lane = the row total of its parity's sum
+    return cross_row_allreduce(c);
+}
+
+// The walk of backward_walk<true> with the absgrad tail: float32 totals per (quadrant, entry), ONE global_atomic_add_f64 from
+// two lanes into the [P, 2] double accumulator (the float32 totals add up exactly there: reproducible).
+template <bool DEPTH>
+__device__ __forceinline__ void absgrad_walk(const uint16_t* lp, int cnt, int base, const float4* s_r0, const float4* s_r1,
+                                             const float2* s_b, const uint32_t* s_id, float pxf, float pyf, BwdPix& st,
+                                             int lane, double* __restrict__ acc, const float* s_z) {
+    for (int j = cnt - 1; j >= 0; --j) {
+        const int e = lp[j];
+        const float4 r0 = s_r0[e], r1 = s_r1[e];
+        const float2 bl = s_b[e];                              // {blue, sign_test_bound}
+        const float dx = r0.x - pxf, dy = r0.y - pyf;
+        const PairAlpha a = pair_alpha(r0, r1, dx, dy);
+        const uint64_t validm = pair_valid(a, (uint32_t)(base + e), st.last, bl.y);
+        if (validm == 0) continue;
+        const PairGrad g = pair_grad<DEPTH>(st, a, validm, r1, bl.x, [=] { return s_z[e]; });   // q = 0 on the masked lanes
+        const float bh = 0.5f * r0.w;
+        const float u = fmaf(r0.z, dx, bh * dy), w = fmaf(r1.x, dy, bh * dx);
+        const float tot = wave_reduce_pair(fabsf(g.q * u), fabsf(g.q * w), lane);
+        const uint32_t gid = __builtin_amdgcn_readfirstlane(s_id[e]);
+        if (lane < 2) unsafeAtomicAdd(acc + (size_t)gid * 2 + lane, (double)tot);
+    }
+}
+
+// One 256-thread workgroup per tile, one 8x8 quadrant per wave, as blend_backward_kernel (one shape for every tile count).
+template <bool DEPTH, bool ALPHA>
+__global__ __launch_bounds__(256) void blend_absgrad_kernel(ViewParams vp, const GaussRec* __restrict__ rec,
+                                                            const uint32_t* __restrict__ ids,
+                                                            const uint2* __restrict__ ranges,
+                                                            const float* __restrict__ final_T,
+                                                            const uint32_t* __restrict__ n_contrib,
+                                                            const float* __restrict__ dL_dcolor,
+                                                            double* __restrict__ acc,
+                                                            const float* __restrict__ dL_ddepth,
+                                                            const float* __restrict__ dL_dalpha) {
+    __shared__ float4 s_r0[BATCH], s_r1[BATCH];
+    __shared__ float2 s_b[BATCH];                          // {blue, sign_test_bound}
+    __shared__ float s_z[DEPTH ? BATCH : 1];               // view depth (depth variant)
+    __shared__ uint32_t s_id[BATCH];
+    __shared__ uint32_t s_mask[BATCH];
+    __shared__ uint16_t s_list[4][BATCH];
+    __shared__ uint32_t s_wmax[4];
+
+    const int num_tiles = vp.gx * vp.gy;
+    const int tile = swizzled_tile(blockIdx.x, num_tiles);
+    const int tx = tile % vp.gx, ty = tile / vp.gx;
+    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
+    const int px = tx * TILE + (w & 1) * 8 + (lane & 7);
+    const int py = ty * TILE + (w >> 1) * 8 + (lane >> 3);
+    const bool inside = px < vp.W && py < vp.H;
+    const float pxf = (float)px, pyf = (float)py;
+    const float tx0 = (float)(tx * TILE), ty0 = (float)(ty * TILE);
+    const uint2 range = ranges[tile];
+    const uint64_t lt_mask = (1ull << lane) - 1ull;
+    const size_t N = (size_t)vp.W * vp.H;
+    const size_t pix = (size_t)py * vp.W + px;
+
+    BwdPix st;
+    st.T = inside ? final_T[pix] : 1.0f;
+    st.last = inside ? n_contrib[pix] : 0u;
+    st.dL0 = st.dL1 = st.dL2 = 0.f;
+    if (inside) { st.dL0 = dL_dcolor[pix]; st.dL1 = dL_dcolor[N + pix]; st.dL2 = dL_dcolor[2 * N + pix]; }
+    st.dLd = (DEPTH && inside) ? dL_ddepth[pix] : 0.f;
+
+    const uint32_t wave_last = wave_max_u32(st.last);
+    if (lane == 0) s_wmax[w] = wave_last;
+    __syncthreads();
+    const uint32_t tile_last = max(max(s_wmax[0], s_wmax[1]), max(s_wmax[2], s_wmax[3]));
+
+    bwd_pix_start_S<ALPHA>(st, vp, inside, pix, dL_dalpha);
+
+    const int nb = ((int)tile_last + BATCH - 1) / BATCH;
+    for (int b = nb - 1; b >= 0; --b) {
+        __syncthreads();                              // previous batch fully consumed
+        const int base = b * BATCH;
+        const int n = min(BATCH, (int)tile_last - base);
+        if (tid < n) {
+            const uint32_t id = ids[range.x + base + tid];
+            const float4 r0 = rec[id].r0, r1 = rec[id].r1;
+            const float4 r2 = rec[id].r2;
+            s_r0[tid] = doubled_w(r0); s_r1[tid] = r1; s_b[tid] = make_float2(r2.x, sign_test_bound(r1.y)); s_id[tid] = id;
+            if constexpr (DEPTH) s_z[tid] = r2.y;
+            s_mask[tid] = quadrant_mask(r0, r1.x, r2.w, tx0, ty0);
+        }
+        __syncthreads();
+        int cnt = 0;
+#pragma unroll
+        for (int c = 0; c < BATCH / 64; ++c) {
+            const int e = c * 64 + lane;
+            const bool hit = e < n && (uint32_t)(base + e) < wave_last && ((s_mask[e] >> w) & 1u);
+            const uint64_t bal = __ballot(hit);
+            if (hit) s_list[w][cnt + __popcll(bal & lt_mask)] = (uint16_t)e;
+            cnt += __popcll(bal);
+        }
+        absgrad_walk<DEPTH>(s_list[w], cnt, base, s_r0, s_r1, s_b, s_id, pxf, pyf, st, lane, acc, s_z);
+    }
+}
+
+// out [P, 3] float32 = { ln2 W acc.x, ln2 H acc.y, 0 }: the units of dL/dmean2D (preprocess_backward_kernel)
+__global__ __launch_bounds__(256) void absgrad_finish_kernel(int P, float sx, float sy, const double* __restrict__ acc,
+                                                             float* __restrict__ out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= P) return;
+    out[3 * (size_t)i + 0] = (float)acc[2 * (size_t)i + 0] * sx;
+    out[3 * (size_t)i + 1] = (float)acc[2 * (size_t)i + 1] * sy;
+    out[3 * (size_t)i + 2] = 0.f;
+}
+
+// ---------------------------------------------------------------------------------------------
 // statistics for the algorithmic-bytes formula: D_trav = sum_tiles max_pixels n_contrib, V = #radii>0
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void tile_stats_kernel(ViewParams vp, const uint32_t* __restrict__ n_contrib,
@@ -1291,6 +1420,26 @@ hipError_t launch_blend_backward(const ViewParams& vp, const char* geom, const u
             hipLaunchKernelGGL((blend_backward_kernel<CH, AL>), dim3(tiles), dim3(256), 0, s, vp, rec, ids, ranges, final_T, n_contrib,
                                dL_dcolor, grad_rec, dL_ddepth, dL_dalpha);
     }); });
+    return hipGetLastError();
+}
+
+// msgs_absgrad: zero fill of the [P, 2] double accumulator, the replay (one of four <DEPTH, ALPHA> instantiations, the four-waves-
+// per-tile shape whatever the tile count and whatever route the main backward takes), the finish.  P == 0 is the caller's.
+hipError_t launch_blend_absgrad(const ViewParams& vp, int P, const char* geom, const uint32_t* ids, const uint2* ranges,
+                                const float* final_T, const uint32_t* n_contrib, const float* dL_dcolor, const float* dL_ddepth,
+                                const float* dL_dalpha, double* acc, float* out, hipStream_t s) {
+    const int tiles = vp.gx * vp.gy;
+    hipError_t e = launch_zero(acc, 2 * sizeof(double) * (size_t)P, s);
+    if (e != hipSuccess) return e;
+    const GaussRec* rec = reinterpret_cast<const GaussRec*>(geom);
+    if (tiles > 0)
+        with_bool(dL_ddepth != nullptr, [&](auto DEPTH) { with_bool(dL_dalpha != nullptr, [&](auto ALPHA) {
+            hipLaunchKernelGGL((blend_absgrad_kernel<decltype(DEPTH)::value, decltype(ALPHA)::value>), dim3(tiles), dim3(256), 0, s,
+                               vp, rec, ids, ranges, final_T, n_contrib, dL_dcolor, acc, dL_ddepth, dL_dalpha);
+        }); });
+    constexpr float LN2 = 0.69314718055994530942f;
+    hipLaunchKernelGGL(absgrad_finish_kernel, dim3((P + 255) / 256), dim3(256), 0, s, P, LN2 * vp.W, LN2 * vp.H,
+                       (const double*)acc, out);
     return hipGetLastError();
 }
 

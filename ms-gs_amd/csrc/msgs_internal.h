@@ -773,6 +773,10 @@ hipError_t launch_blend_backward(const ViewParams& vp, const char* geom, const u
                                  grad_acc_t* grad_rec, hipStream_t s, const uint32_t* tile_order = nullptr,
                                  const float* dL_ddepth = nullptr,    // non-null: the depth variants (record slot 9 = dL/dz)
                                  const float* dL_dalpha = nullptr);   // non-null: the alpha variants (S starts at bg.dL/dC - dL/dA)
+// msgs_absgrad (SPEC M10): out [P, 3] float32 = {ln2 W sum_p |q u|, ln2 H sum_p |q w|, 0}; acc: [P, 2] doubles, cleared inside
+hipError_t launch_blend_absgrad(const ViewParams& vp, int P, const char* geom, const uint32_t* ids, const uint2* ranges,
+                                const float* final_T, const uint32_t* n_contrib, const float* dL_dcolor, const float* dL_ddepth,
+                                const float* dL_dalpha, double* acc, float* out, hipStream_t s);
 // heaviest-first launch order of the one-wave-per-tile backward from the forward's per-tile traversal lengths
 hipError_t launch_tile_order(const ViewParams& vp, const uint32_t* tile_last, uint32_t* tile_order, hipStream_t s);
 hipError_t launch_blend_lane_stats(const ViewParams& vp, const char* geom, const uint32_t* ids, const uint2* ranges,

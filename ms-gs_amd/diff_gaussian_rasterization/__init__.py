@@ -329,7 +329,8 @@ def _note_camera(ctx, camera, behind=0):
 #   [viewmatrix, projmatrix, campos]   _camera_inputs: three tensors or nothing
 #   [bg]                               grad mode on and settings.bg requires grad: the background colour, for its gradient
 #   [_ALPHA]                           return_alpha=True: a marker (not a tensor) — the Function returns alpha as a sixth output
-# A call that asks for neither new thing passes exactly what it passed before them.
+#   [_AbsgradMarker]                   absgrad=True: a marker holding a weak reference to the caller's means2D
+# A call that asks for none of the new things passes exactly what it passed before them.
 class _AlphaMarker:
     def __repr__(self):
         return "return_alpha"
@@ -338,28 +339,64 @@ class _AlphaMarker:
 _ALPHA = _AlphaMarker()
 
 
-def _extra_inputs(rs, return_alpha=False):
+# Absgrad (AbsGS, gsplat's absgrad=True).  The backward of a call made with absgrad=True also runs msgs_absgrad
+# — one more launch chain on the backward's stream, fed the same dL/dcolor, dL/ddepth and dL/dalpha, independent of whatever the
+# main backward does with its gradients (sinks, accumulators, the optimizer step) — and ASSIGNS the result [P,3] float32, in
+# means2D's shape, to `means2D.absgrad` of the tensor object the caller passed: beside .grad, where densification reads it.
+# Assigned on every backward (retain_graph: the latest one), never accumulated.
+class _AbsgradMarker:
+    def __init__(self, means2D):
+        self.means2D = weakref.ref(means2D)
+
+    def __repr__(self):
+        return "absgrad"
+
+
+def _extra_inputs(rs, return_alpha=False, absgrad=False, means2D=None):
+    if absgrad and _C.lib.msgs_get_deterministic():
+        raise ValueError("absgrad=True is not offered in the verification mode (set_deterministic): that mode checks the "
+                         "gradients, it does not train")
     extra = _camera_inputs(rs)
     if torch.is_grad_enabled() and torch.is_tensor(rs.bg) and rs.bg.requires_grad:
         extra = tuple(extra) + (rs.bg,)
-    return tuple(extra) + (_ALPHA,) if return_alpha else extra
+    if return_alpha:
+        extra = tuple(extra) + (_ALPHA,)
+    return tuple(extra) + (_AbsgradMarker(means2D),) if absgrad else extra
 
 
 def _note_extra(ctx, extra):
     """forward: split the trailing inputs; leaves ctx.camera (_note_camera), ctx.bg ((shape, dtype, device) when the
-    background wants a gradient, else None), ctx.n_extra_tail (inputs behind the camera's) and returns return_alpha"""
-    alpha = bool(extra) and extra[-1] is _ALPHA
-    rest = extra[:-1] if alpha else extra
+    background wants a gradient, else None), ctx.n_extra_tail (inputs behind the camera's), ctx.absgrad (the marker or None)
+    and returns return_alpha"""
+    ctx.absgrad = extra[-1] if extra and isinstance(extra[-1], _AbsgradMarker) else None
+    n_abs = int(ctx.absgrad is not None)
+    rest = extra[:-1] if n_abs else extra
+    alpha = bool(rest) and rest[-1] is _ALPHA
+    rest = rest[:-1] if alpha else rest
     bg = rest[-1] if len(rest) in (1, 4) else None
     camera = rest[:3] if len(rest) >= 3 else ()
     ctx.n_extra_tail = len(extra) - len(camera)
     ctx.has_bg = bg is not None
     ctx.bg = None
-    if bg is not None and ctx.needs_input_grad[len(ctx.needs_input_grad) - 1 - int(alpha)]:
+    if bg is not None and ctx.needs_input_grad[len(ctx.needs_input_grad) - 1 - int(alpha) - n_abs]:
         ctx.bg = (bg.shape, bg.dtype, bg.device)
     _note_camera(ctx, camera, ctx.n_extra_tail)
     ctx.return_alpha = alpha
     return camera, alpha
+
+
+def _absgrad(ctx, call, geom, binning, image, D, dL, dLd, dLa, dev, stream):
+    """backward of an absgrad=True call: msgs_absgrad on the backward's stream, the result assigned to means2D.absgrad"""
+    m2 = ctx.absgrad.means2D()
+    if m2 is None:                          # the caller dropped the tensor: nobody can read the attribute
+        return
+    P = call.P
+    out = torch.empty(P, 3, dtype=torch.float32, device=dev)
+    scratch = _bytes(_C.lib.msgs_absgrad_scratch_bytes(P), dev)
+    _C.check(_C.lib.msgs_absgrad(call.view_ref, P, _ptr(geom), geom.numel(), D, _ptr(binning), binning.numel(), _ptr(image),
+                                 image.numel(), _ptr(dL), _ptr(dLd), _ptr(dLa), _ptr(scratch), scratch.numel(), _ptr(out), stream),
+             "msgs_absgrad")
+    m2.absgrad = out.view(m2.shape) if out.shape != m2.shape and out.numel() == m2.numel() else out
 
 
 def _alpha_map(call, image, alpha, stream):
@@ -379,8 +416,9 @@ def _bg_grad(ctx, view_ref, image, dL, W, H, dev, stream):
 
 
 def _extra_grads(ctx, g_cam, g_bg):
-    """gradients of the trailing inputs in their order: camera, bg, the alpha marker"""
-    return tuple(g_cam) + ((g_bg,) if ctx.has_bg else ()) + ((None,) if ctx.return_alpha else ())
+    """gradients of the trailing inputs in their order: camera, bg, the alpha marker, the absgrad marker"""
+    return tuple(g_cam) + ((g_bg,) if ctx.has_bg else ()) + ((None,) if ctx.return_alpha else ()) + \
+        ((None,) if ctx.absgrad is not None else ())
 
 
 def _refuse_camera_with(camera):
@@ -418,7 +456,8 @@ def set_deterministic(on=True):
     grouping by Gaussian): bitwise reproducible by construction, and — against the CPU checker of the tests evaluated the same
     way (exp in double) — every gradient tensor within 1e-4, the north star's sentence as written
     (tests/test_literal_gpu.py).  Several times slower than the default path.  Must not change between a forward and its
-    backward.  Returns the previous setting.  Also: MSGS_DETERMINISTIC=1 in the environment."""
+    backward.  A checker, not a trainer: absgrad=True raises ValueError at the forward while it is on.  Returns the previous
+    setting.  Also: MSGS_DETERMINISTIC=1 in the environment."""
     return bool(_C.lib.msgs_set_deterministic(1 if on else 0))
 
 
@@ -875,6 +914,9 @@ class _RasterizeGaussians(torch.autograd.Function):
                 with _on_device(ctx.dev):
                     stream = C.c_void_p(torch.cuda.current_stream(ctx.dev).cuda_stream)
                     g_bg = _bg_grad(ctx, C.byref(view), None, _f32c(grad_color), W, H, ctx.dev, stream)
+            m2 = ctx.absgrad.means2D() if ctx.absgrad is not None else None
+            if m2 is not None:              # no Gaussian: zeros [0, 3], no launch
+                m2.absgrad = torch.zeros(ctx.in_shapes[1], dtype=torch.float32, device=ctx.dev)
             return tuple(torch.zeros(s, device=ctx.dev) for s in ctx.in_shapes) + (None,) * 6 + _extra_grads(ctx, cam, g_bg)
         _check_saved(ctx)
         call = ctx.call
@@ -902,6 +944,8 @@ class _RasterizeGaussians(torch.autograd.Function):
             dLa = _f32c(grad_alpha) if grad_alpha is not None else None
             _run_backward(lib, call, ctx, geom, binning, image, D, dL, dLd, dLa, scratch, grads, stream, cam)
             g_bg = _bg_grad(ctx, call.view_ref, image, dL, call.W, call.H, dev, stream) if ctx.bg is not None else None
+            if ctx.absgrad is not None:
+                _absgrad(ctx, call, geom, binning, image, D, dL, dLd, dLa, dev, stream)
         m2_shape, op_shape = ctx.shapes
         # occ_multiplier / dc_delta / pixel-size inputs / masks receive no gradient (DESIGN.md SPEC M5)
         return (g_means3D, g_means2D.view(m2_shape) if g_means2D.shape == m2_shape else g_means2D,
@@ -1162,6 +1206,8 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
             if adam is not None:
                 step_opt.commit_step_in_backward(ctx.leaves)
             g_bg = _bg_grad(ctx, call.view_ref, image, dL, call.W, call.H, dev, stream) if ctx.bg is not None else None
+            if ctx.absgrad is not None:
+                _absgrad(ctx, call, geom, binning, image, D, dL, dLd, dLa, dev, stream)
         g_cam = _extra_grads(ctx, cam.grads(ctx) if cam is not None else (), g_bg)
         if accum is not None or adam is not None:   # the leaf gradients live in the accumulator / were consumed by the step
             return (None, g_m2.view(m2_shape), None, None, None, None, None, None, None, None, None, None, None) + g_cam
@@ -1282,31 +1328,40 @@ def sh_grad_from_views(means3D, gathered, n_views, sh_degree, scale, out_dc, out
 
 def rasterize_gaussians_raw(xyz, means2D, features_dc, features_rest, opacity_raw, scaling_raw, rotation_raw,
                             max_pixel_sizes, min_pixel_sizes, occ_multiplier, dc_delta, base_mask, raster_settings,
-                            return_alpha=False):
-    """return_alpha=True: a sixth output, the alpha map [H,W] (1 - final transmittance), differentiable"""
+                            absgrad=False, return_alpha=False):
+    """return_alpha=True: a sixth output, the alpha map [H,W] (1 - final transmittance), differentiable
+    absgrad=True: every backward also assigns means2D.absgrad.  Pass both flags by keyword."""
     _note_grad_mode()
     return _RasterizeGaussiansRaw.apply(xyz, means2D, features_dc, features_rest, opacity_raw, scaling_raw,
                                         rotation_raw, max_pixel_sizes, min_pixel_sizes, occ_multiplier, dc_delta,
-                                        base_mask, raster_settings, *_extra_inputs(raster_settings, return_alpha))
+                                        base_mask, raster_settings,
+                                        *_extra_inputs(raster_settings, return_alpha, absgrad, means2D))
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                         max_pixel_sizes, min_pixel_sizes, occ_multiplier, dc_delta, base_mask, raster_settings,
-                        return_alpha=False):
-    """return_alpha=True: a sixth output, the alpha map [H,W] (1 - final transmittance), differentiable"""
+                        absgrad=False, return_alpha=False):
+    """return_alpha=True: a sixth output, the alpha map [H,W] (1 - final transmittance), differentiable
+    absgrad=True: every backward also assigns means2D.absgrad.  Pass both flags by keyword."""
     _note_grad_mode()
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
                                      cov3Ds_precomp, max_pixel_sizes, min_pixel_sizes, occ_multiplier, dc_delta,
-                                     base_mask, raster_settings, *_extra_inputs(raster_settings, return_alpha))
+                                     base_mask, raster_settings,
+                                     *_extra_inputs(raster_settings, return_alpha, absgrad, means2D))
 
 
 class GaussianRasterizer(nn.Module):
-    def __init__(self, raster_settings, return_alpha=False):
+    def __init__(self, raster_settings, return_alpha=False, absgrad=False):
         """return_alpha=True: forward / forward_raw return the 6-tuple (color, acc_pixel_size, depth, radii, pixel_sizes, alpha)
-        with alpha [H,W] float32 = 1 - final transmittance, differentiable; default: the reference's 5-tuple"""
+        with alpha [H,W] float32 = 1 - final transmittance, differentiable; default: the reference's 5-tuple.
+        absgrad=True: every backward through a forward / forward_raw of this module also assigns `means2D.absgrad`, float32
+        in means2D's shape: (sum over pixels of |that pixel's share of dL/dmean2D| in x and y, 0) — the densification statistic
+        of AbsGS, in the units of means2D.grad.  Outputs and gradients are those of the call without it.
+        Not offered in the verification mode (set_deterministic): ValueError at the forward."""
         super().__init__()
         self.raster_settings = raster_settings
         self.return_alpha = bool(return_alpha)
+        self.absgrad = bool(absgrad)
 
     def markVisible(self, positions):
         """Boolean mask of points in front of the near plane (upstream markVisible; unused by the
@@ -1358,7 +1413,8 @@ class GaussianRasterizer(nn.Module):
         o = lambda t: t if t is not None else empty
         return rasterize_gaussians_raw(xyz, means2D, features_dc, features_rest, opacity_raw, scaling_raw,
                                        rotation_raw, o(max_pixel_sizes), o(min_pixel_sizes), o(occ_multiplier),
-                                       o(dc_delta), o(base_mask), self.raster_settings, self.return_alpha)
+                                       o(dc_delta), o(base_mask), self.raster_settings, absgrad=self.absgrad,
+                                       return_alpha=self.return_alpha)
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
                 cov3D_precomp=None, max_pixel_sizes=None, min_pixel_sizes=None, occ_multiplier=None,
@@ -1389,7 +1445,7 @@ class GaussianRasterizer(nn.Module):
                     means3D, means2D, *leaves, shs.detach() if _chain_reads_cat else empty, opacities.detach(), scales.detach(),
                     rotations.detach(),
                     o(max_pixel_sizes), o(min_pixel_sizes), o(occ_multiplier), o(dc_delta), o(base_mask), rs,
-                    *_extra_inputs(rs, self.return_alpha))
+                    *_extra_inputs(rs, self.return_alpha, self.absgrad, means2D))
         return rasterize_gaussians(
             means3D, means2D,
             shs if shs is not None else empty,
@@ -1403,4 +1459,4 @@ class GaussianRasterizer(nn.Module):
             occ_multiplier if occ_multiplier is not None else empty,
             dc_delta if dc_delta is not None else empty,
             base_mask if base_mask is not None else empty,
-            rs, self.return_alpha)
+            rs, absgrad=self.absgrad, return_alpha=self.return_alpha)

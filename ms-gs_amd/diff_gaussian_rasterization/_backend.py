@@ -193,6 +193,10 @@ def _load():
     lib.msgs_bg_grad_scratch_bytes.argtypes = [C.c_int32, C.c_int32]
     lib.msgs_bg_grad.restype = C.c_int
     lib.msgs_bg_grad.argtypes = [C.POINTER(View), vp, sz, vp, vp, vp, sz, vp]
+    lib.msgs_absgrad_scratch_bytes.restype = sz
+    lib.msgs_absgrad_scratch_bytes.argtypes = [C.c_int32]
+    lib.msgs_absgrad.restype = C.c_int
+    lib.msgs_absgrad.argtypes = [C.POINTER(View), C.c_int32, vp, sz, C.c_int64, vp, sz, vp, sz, vp, vp, vp, vp, sz, vp, vp]
     lib.msgs_backward_per_gaussian.restype = C.c_int
     lib.msgs_backward_per_gaussian.argtypes = [C.POINTER(View), C.POINTER(Gaussians), vp, vp, sz, vp, C.POINTER(Grads), vp]
     lib.msgs_sh_grad_from_views.restype = C.c_int
@@ -264,7 +268,8 @@ EXPORTS = ("msgs_abi_version", "msgs_error_string", "msgs_geom_bytes", "msgs_sta
            "msgs_stage2_scratch_bytes_slab", "msgs_slab_stats", "msgs_backward_with_depth",
            "msgs_backward_scratch_bytes_deterministic_depth", "msgs_backward_with_camera", "msgs_camera_grad_scratch_bytes",
            "msgs_densify_scratch_bytes", "msgs_densify_select", "msgs_densify_apply",
-           "msgs_alpha_map", "msgs_backward_with_alpha", "msgs_bg_grad_scratch_bytes", "msgs_bg_grad")
+           "msgs_alpha_map", "msgs_backward_with_alpha", "msgs_bg_grad_scratch_bytes", "msgs_bg_grad",
+           "msgs_absgrad_scratch_bytes", "msgs_absgrad")
 
 
 def check(rc, where):

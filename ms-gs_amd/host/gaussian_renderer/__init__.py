@@ -154,3 +154,49 @@ def render_with_alpha(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scalin
     out = dict(zip(RESULT_KEYS, values))
     out["alpha"] = alpha
     return out
+
+
+def render_with_absgrad(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, override_color=None,
+                        filter_small=False, filter_large=False, fade_size=1.0, fused=False, alpha=False):
+    """render() — or, with fused=True, render_fused() (then without override_color) — whose backward also leaves the absolute
+    screen-space gradient of AbsGS beside the signed one: after loss.backward(), out["viewspace_points"].absgrad is [P,3]
+    float32 = (sum over pixels of |that pixel's share of dL/dmean2D| in x and y, 0), in the units of
+    out["viewspace_points"].grad.  A Gaussian that some pixels pull left and others right — the blurry,
+    over-large one — cancels itself out of .grad and not out of .absgrad: train_epilogue.update_training_stats(absgrad=True)
+    accumulates its norm in the place of .grad's.  Same keys as render(), plus "alpha" (render_with_alpha) with alpha=True.
+    Image, maps and gradients are those of the call without it, bit for bit."""
+    settings = _settings(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, filter_small, filter_large, fade_size)
+    rasterizer = GaussianRasterizer(raster_settings=settings, return_alpha=alpha, absgrad=True)
+    if fused:
+        if override_color is not None:
+            raise ValueError("render_with_absgrad: fused=True cannot be combined with override_color")
+        xyz = pc._xyz
+        viewspace = torch.empty_like(xyz, requires_grad=True)
+        outs = rasterizer.forward_raw(
+            xyz, viewspace, pc._features_dc, pc._features_rest, pc._opacity, pc._scaling, pc._rotation,
+            max_pixel_sizes=pc.get_max_pixel_sizes, min_pixel_sizes=pc.get_min_pixel_sizes,
+            occ_multiplier=pc.get_occ_multiplier, dc_delta=pc.get_dc_delta, base_mask=pc.get_base_mask)
+    else:
+        xyz = pc.get_xyz
+        viewspace = torch.zeros_like(xyz, requires_grad=True) + 0
+        try:
+            viewspace.retain_grad()
+        except Exception:
+            pass
+        outs = rasterizer(
+            means3D=xyz,
+            means2D=viewspace,
+            opacities=pc.get_opacity,
+            max_pixel_sizes=pc.get_max_pixel_sizes,
+            min_pixel_sizes=pc.get_min_pixel_sizes,
+            occ_multiplier=pc.get_occ_multiplier,
+            dc_delta=pc.get_dc_delta,
+            base_mask=pc.get_base_mask,
+            **_colour_inputs(viewpoint_camera, pc, pipe, override_color),
+            **_shape_inputs(pc, pipe, scaling_modifier))
+    image, acc_pixel_size, depth, radii, pixel_sizes = outs[:5]
+    values = (image, acc_pixel_size, depth, viewspace, radii > 0, radii, pixel_sizes)
+    out = dict(zip(RESULT_KEYS, values))
+    if alpha:
+        out["alpha"] = outs[5]
+    return out

@@ -104,6 +104,9 @@ class ViewPipeline:
                 g = obj.grad if obj.is_leaf else None
                 if g is not None and g.is_cuda:
                     g.record_stream(cur)
+                a = getattr(obj, "absgrad", None)       # (a render with absgrad=True: allocated by the backward likewise)
+                if torch.is_tensor(a) and a.is_cuda:
+                    a.record_stream(cur)
         elif isinstance(obj, dict):
             for v in obj.values():
                 ViewPipeline._hand_over(v, cur)

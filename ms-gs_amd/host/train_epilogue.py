@@ -132,14 +132,17 @@ class FusedAdam(torch.optim.Optimizer):
 
 
 def update_training_stats(model, viewspace_points, radii, pixel_sizes, reso_lvl=0, *, base_mask=False,
-                          update_pixel_sizes=True, densify=True):
+                          update_pixel_sizes=True, densify=True, absgrad=False):
     """One launch for the reference's per-iteration statistics (train.py:239-250).  `model` carries the reference's
     attribute names: xyz_gradient_accum / denom [P, reso_lvls, 1], max_radii2D, max_pixel_sizes, min_pixel_sizes [P]
     float32, base_gaussian_mask [P] bool, target_reso_lvl [P] int64, reso_lvls.  `viewspace_points` is
     render_pkg["viewspace_points"] (its .grad is read), `radii` / `pixel_sizes` the render outputs.
       base_mask           train.py:239-241  (caller decides: preserve_large and past densify_until_iter, coarsest level)
       update_pixel_sizes  train.py:244-245
-      densify             train.py:247-250  (iteration < densify_until_iter)"""
+      densify             train.py:247-250  (iteration < densify_until_iter)
+      absgrad             the densification statistic accumulates the norm of viewspace_points.absgrad (the absolute screen-space
+                          gradient a render with absgrad=True leaves there, gaussian_renderer.render_with_absgrad) in the place
+                          of viewspace_points.grad: the AbsGS criterion.  Same kernel, another pointer."""
     flags = (_C.STATS_BASE_MASK if base_mask else 0) | (_C.STATS_PIXEL_SIZES if update_pixel_sizes else 0) | \
             (_C.STATS_DENSIFY if densify else 0)
     if flags == 0:
@@ -170,9 +173,15 @@ def update_training_stats(model, viewspace_points, radii, pixel_sizes, reso_lvl=
         d.pixel_sizes, d.target_reso_lvl = _ptr(pixel_sizes), _ptr(lvl)
         d.max_pixel_sizes, d.min_pixel_sizes = _ptr(model.max_pixel_sizes), _ptr(model.min_pixel_sizes)
     if densify:
-        g = viewspace_points.grad
-        if g is None:
-            raise RuntimeError("viewspace_points.grad is None: call loss.backward() first")
+        if absgrad:
+            g = getattr(viewspace_points, "absgrad", None)
+            if g is None:
+                raise RuntimeError("viewspace_points.absgrad is missing: render with absgrad=True (render_with_absgrad) and call "
+                                   "loss.backward() first")
+        else:
+            g = viewspace_points.grad
+            if g is None:
+                raise RuntimeError("viewspace_points.grad is None: call loss.backward() first")
         if g.dtype != torch.float32 or not g.is_contiguous():
             g = g.to(torch.float32).contiguous()
         keep.append(g)
