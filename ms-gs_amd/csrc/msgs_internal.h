@@ -175,6 +175,9 @@ struct SortGeom {
             // a scatter block reads `ngroups` group sums + on average gsize/2 block histograms per digit: balance them
             gsize = 8;
             while ((int64_t)gsize * gsize < nb) gsize += 8;
+            // (a bound on ngroups for thresholds other than the present ones: it needs nb > SORT_MAX_GROUPS^2 = 16 384 to raise
+            // gsize, and the scanned route takes over at SORT_SCANNED_MIN_BLOCKS = 4096 — tests/test_sort_reference_cpu.py checks
+            // every block count)
             const int64_t floor_g = (nb + SORT_MAX_GROUPS - 1) / SORT_MAX_GROUPS;
             if (floor_g > gsize) gsize = (int)floor_g;
         }
@@ -670,6 +673,7 @@ hipError_t exclusive_scan_u32(const uint32_t* in, const uint32_t* gather, uint32
                               uint32_t* overflow_flag = nullptr, uint32_t in_mask = 0xFFFFFFFFu, uint32_t* side_out = nullptr,
                               uint32_t* side_flag = nullptr);    // overflow_flag: set to 1 when the total exceeds `clamp`;
                                                                   // side_flag: set to 1 when side_out is written, to 0 otherwise
+                                                                  // (by the first pass: a launch with n <= 0 leaves it alone)
 // a run-time bool as a compile-time one: f(std::true_type{}) or f(std::false_type{}).  A launcher picks a kernel's bool
 // template arguments with it — one launch expression in a generic lambda, `decltype(B)::value` as the argument — instead of
 // one copy of the launch per value

@@ -54,6 +54,15 @@ __device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t* s
     return base + inc - v;
 }
 
+// block-wide sum of one 64-bit value per thread (256 threads), returned to every thread
+__device__ __forceinline__ uint64_t block_sum_u64(uint64_t v, uint64_t* s_sum /*[4]*/) {
+    for (int off = 32; off > 0; off >>= 1)
+        v += ((uint64_t)(uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), off) << 32) | (uint32_t)__shfl_xor((int)(uint32_t)v, off);
+    if ((threadIdx.x & 63) == 0) s_sum[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3];
+}
+
 // SCAN_ITEMS consecutive values of one thread: 16-byte accesses when the run is complete and aligned
 __device__ __forceinline__ void scan_load_items(const uint32_t* in, int64_t base, int64_t n, uint32_t v[SCAN_ITEMS]) {
     static_assert(SCAN_ITEMS % 4 == 0, "uint4 runs");
@@ -87,7 +96,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_reduce_kernel(const uint32_
                                                                    uint32_t* __restrict__ staged,
                                                                    const uint32_t* __restrict__ n_ptr, uint32_t in_mask,
                                                                    uint32_t* __restrict__ side_out, uint32_t* __restrict__ side_flag) {
-    __shared__ uint32_t s_wave[4];
+    __shared__ uint64_t s_sum[4];
     if (n_ptr) n = (int64_t)*n_ptr;
     // side_flag: 1 when this scan delivers the side values, 0 when it scans over them (they are counts from here on)
     if (side_flag && blockIdx.x == 0 && threadIdx.x == 0) *side_flag = side_out ? 1u : 0u;
@@ -109,11 +118,11 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_reduce_kernel(const uint32_
     } else {
         scan_load_items(in, base, n, v);
     }
-    uint32_t sum = 0;
+    // the block total in 64 bits: one chunk of values near 2^32 passes 2^32 on its own, and the grand total is exact
+    uint64_t sum = 0;
 #pragma unroll
     for (int k = 0; k < SCAN_ITEMS; ++k) sum += v[k];
-    uint32_t total;
-    block_exclusive_scan(sum, s_wave, &total);
+    const uint64_t total = block_sum_u64(sum, s_sum);
     if (threadIdx.x == 0) partials[blockIdx.x] = total;
 }
 
@@ -134,18 +143,13 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_apply_fused_kernel(const ui
     __shared__ uint32_t s_wave[4];
     __shared__ uint64_t s_sum[4];
     if (n_ptr) n = (int64_t)*n_ptr;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     // blocks behind the data (n_ptr < grid capacity) still need nothing; block 0 always runs (it owns the publication)
     const int64_t chunk0 = (int64_t)blockIdx.x * SCAN_CHUNK;
     if (blockIdx.x != 0 && chunk0 >= n) return;
     const int64_t upto = blockIdx.x == 0 ? nb : (int64_t)blockIdx.x;       // block 0: the grand total
     uint64_t acc = 0;
     for (int64_t q = threadIdx.x; q < upto; q += SCAN_THREADS) acc += partials[q];
-    for (int off = 32; off > 0; off >>= 1)
-        acc += ((uint64_t)(uint32_t)__shfl_xor((int)(uint32_t)(acc >> 32), off) << 32) | (uint32_t)__shfl_xor((int)(uint32_t)acc, off);
-    if (lane == 0) s_sum[w] = acc;
-    __syncthreads();
-    const uint64_t sum = s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3];
+    const uint64_t sum = block_sum_u64(acc, s_sum);
     uint64_t base = sum;
     if (blockIdx.x == 0) {
         base = 0;
