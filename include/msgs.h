@@ -382,6 +382,30 @@ int msgs_absgrad(const msgs_view_t* view, int32_t P,
                  void* scratch, size_t scratch_bytes,
                  float* out_absgrad, void* stream);
 
+/* ---- contribution scores: what a Gaussian did to the images, for pruning (DESIGN.md SPEC M11, 4.11) ------ */
+/* With w_ip = alpha_ip T_ip the blend weight of Gaussian i in pixel p (the weight of dL/dC in the colour gradient) and an
+ * optional weight map m_p >= 0 (pixel_weights [H,W] float32, device; NULL = 1 everywhere; a negative or NaN weight counts as 0):
+ *     weight_sum_i = sum_p m_p w_ip,   weight_max_i = max_p m_p w_ip,   pixel_count_i = #{p : m_p > 0, pair (i,p) blended}
+ * over exactly the pairs msgs_backward* counts.  A Gaussian in no tile list, or with radii = 0, gets (0, 0, 0).  No gradients.
+ * msgs_contrib_accumulate adds ONE view to the caller's accumulator `acc` (>= msgs_contrib_scratch_bytes(P), 8-byte aligned):
+ * clear_first != 0 zero-fills it first, clear_first == 0 adds to what it holds — sum, max and sum across views, so N views need
+ * one accumulator and no per-view [P] arrays.  One replay of the blend backward's walk; reads what the forward of this view
+ * left in geom / binning / image_state (single pass, speculative stage 2 or its redo, depth slabs, occlusion cut-off, quadrant
+ * or fine forward alike); independent of msgs_backward* and msgs_absgrad.  Per (tile quadrant, entry) a float32 total goes to a
+ * double, a maximum to an unsigned integer maximum of the float's bits, a count to a 64-bit integer: all three exact and
+ * independent of the order of arrival — the same bits on every run.  P == 0 or num_instances == 0: no replay, only the clear.
+ * msgs_contrib_finish converts the accumulator: weight_sum [P] float32, weight_max [P] float32, pixel_count [P] int64. */
+size_t msgs_contrib_scratch_bytes(int32_t P);
+int msgs_contrib_accumulate(const msgs_view_t* view, int32_t P,
+                            const void* geom, size_t geom_bytes,
+                            int64_t num_instances,
+                            const void* binning, size_t binning_bytes,
+                            const void* image_state, size_t image_bytes,
+                            const float* pixel_weights, /* [H,W] or NULL */
+                            void* acc, size_t acc_bytes, int32_t clear_first, void* stream);
+int msgs_contrib_finish(int32_t P, const void* acc, size_t acc_bytes,
+                        float* weight_sum, float* weight_max, int64_t* pixel_count, void* stream);
+
 /* msgs_backward_per_gaussian: the per-Gaussian half of msgs_backward ALONE (2-D covariance backward, projection, SH,
  * scale / quaternion chain — upstream's computeCov2DCUDA + preprocessCUDA backward, SURVEY 2.2 K8 + K9) on per-Gaussian
  * 2-D gradients supplied by the caller instead of the blend backward's sums: sums2d [P,9] DOUBLES (device) =

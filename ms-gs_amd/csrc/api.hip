@@ -830,6 +830,44 @@ int msgs_absgrad(const msgs_view_t* view, int32_t P, const void* geom_v, size_t 
                                  dL_dalpha, (double*)scratch, out_absgrad, s));
     return debug_sync(view, s);
 }
+
+size_t msgs_contrib_scratch_bytes(int32_t P) { return CONTRIB_ACC_BYTES * (size_t)(P > 0 ? P : 1); }
+
+int msgs_contrib_accumulate(const msgs_view_t* view, int32_t P, const void* geom_v, size_t geom_bytes, int64_t D,
+                            const void* binning_v, size_t binning_bytes, const void* image_v, size_t image_bytes,
+                            const float* pixel_weights, void* acc, size_t acc_bytes, int32_t clear_first, void* stream) {
+    if (!view || P < 0 || D < 0 || view->image_width < 1 || view->image_height < 1 || !acc) return MSGS_ERR_INVALID_ARG;
+    if ((uintptr_t)acc & 7) return MSGS_ERR_INVALID_ARG;                     // rows of {double, uint64, uint32}
+    if (acc_bytes < msgs_contrib_scratch_bytes(P)) return MSGS_ERR_CAPACITY;
+    const bool replay = P > 0 && D > 0;                                      // no instance: no pair, nothing to add
+    const int W = view->image_width, H = view->image_height;
+    if (replay) {
+        if (!geom_v || !binning_v || !image_v) return MSGS_ERR_INVALID_ARG;
+        if (geom_bytes < msgs_geom_bytes(P) || binning_bytes < msgs_binning_bytes(D, W, H) || image_bytes < msgs_image_bytes(W, H))
+            return MSGS_ERR_CAPACITY;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    if (clear_first && P > 0) HIP_TRY(launch_zero(acc, CONTRIB_ACC_BYTES * (size_t)P, s));
+    if (!replay) return debug_sync(view, s);
+    const ViewParams vp = make_view_params(view);
+    const BinningLayout BL(D, vp.gx * vp.gy);
+    const ImageLayout IL(W, H);
+    const char* binning = (const char*)binning_v;
+    const char* image = (const char*)image_v;
+    HIP_TRY(launch_blend_contrib(vp, (const char*)geom_v, (const uint32_t*)(binning + BL.ids), (const uint2*)(binning + BL.ranges),
+                                 (const float*)(image + IL.final_T), (const uint32_t*)(image + IL.n_contrib), pixel_weights, acc, s));
+    return debug_sync(view, s);
+}
+
+int msgs_contrib_finish(int32_t P, const void* acc, size_t acc_bytes, float* weight_sum, float* weight_max, int64_t* pixel_count,
+                        void* stream) {
+    if (P < 0) return MSGS_ERR_INVALID_ARG;
+    if (P == 0) return MSGS_OK;                                              // the outputs are [0]
+    if (!acc || !weight_sum || !weight_max || !pixel_count || ((uintptr_t)acc & 7)) return MSGS_ERR_INVALID_ARG;
+    if (acc_bytes < msgs_contrib_scratch_bytes(P)) return MSGS_ERR_CAPACITY;
+    HIP_TRY(launch_contrib_finish(P, acc, weight_sum, weight_max, pixel_count, (hipStream_t)stream));
+    return MSGS_OK;
+}
 }  // extern "C"
 
 namespace {

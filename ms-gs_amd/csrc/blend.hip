@@ -1181,6 +1181,163 @@ __global__ __launch_bounds__(256) void absgrad_finish_kernel(int P, float sx, fl
 }
 
 // ---------------------------------------------------------------------------------------------
+// Contribution scores (DESIGN.md SPEC M11, 4.11; msgs_contrib_accumulate): per Gaussian, over the pixels p of a view with an
+// optional weight map m_p >= 0,
+//     weight_sum = sum_p m_p w_ip,   weight_max = max_p m_p w_ip,   pixel_count = #{p : m_p > 0, pair (i, p) blended}
+// with w_ip = alpha_ip T_ip = PairGrad::dch, the weight of dL/dC in the colour gradient.  Like absgrad, w_ip exists only in front
+// of the cross-pixel reduction: one more replay of the back-to-front walk of blend_backward_kernel (same staging, quadrant lists,
+// pair_alpha / pair_valid, and pair_grad on a zero dL/dC — only its T recurrence and dch stay alive), with a three-value tail.
+// No dL inputs, no gradients.  Opt-in: nothing of the default path calls or shares a kernel with it.
+// ---------------------------------------------------------------------------------------------
+// One accumulator row per Gaussian (CONTRIB_ACC_BYTES): the caller owns it across views.
+struct ContribAcc {
+    double sum;                     // +0: float32 wave totals, added exactly
+    unsigned long long count;       // +8: 64 bits — a 4K view adds at most 8.3e6 per Gaussian
+    uint32_t max_bits;              // +16: bit pattern of a non-negative float: orders like the float
+    uint32_t pad;
+};
+static_assert(sizeof(ContribAcc) == CONTRIB_ACC_BYTES, "msgs_contrib_scratch_bytes");
+
+// every lane receives the wave maximum (the tree of wave_allreduce_sum); unsigned, for bit patterns of non-negative floats
+__device__ __forceinline__ uint32_t wave_allreduce_max_u32(uint32_t v) {
+    typedef unsigned u2 __attribute__((ext_vector_type(2)));
+    v = max(v, dpp_mov_u<0xB1>(v));           // quad_perm [1,0,3,2]
+    v = max(v, dpp_mov_u<0x4E>(v));           // quad_perm [2,3,0,1]
+    v = max(v, dpp_mov_u<0x124>(v));          // row_ror:4
+    v = max(v, dpp_mov_u<0x128>(v));          // row_ror:8: every lane = its row's maximum
+    const u2 a = __builtin_amdgcn_permlane16_swap(v, v, false, false);
+    v = max(a.x, a.y);
+    const u2 b = __builtin_amdgcn_permlane32_swap(v, v, false, false);
+    return max(b.x, b.y);
+}
+
+// wave_allreduce_sum whose adds stay adds: without this the first one is contracted with the multiply that produced the lane's
+// term (an FMA on the unrounded product), and the total is no longer the sum of the float32 terms the maximum sees — a weight
+// map of ones would then give other bits than no map.
+__device__ __forceinline__ float wave_allreduce_sum_of_terms(float v) {
+#pragma clang fp contract(off)
+    v = v + dpp_mov<0xB1>(v);                 // quad_perm [1,0,3,2]
+    v = v + dpp_mov<0x4E>(v);                 // quad_perm [2,3,0,1]
+    v = v + dpp_mov<0x124>(v);                // row_ror:4
+    v = v + dpp_mov<0x128>(v);                // row_ror:8: every lane = its row's total
+    return cross_row_allreduce(v);
+}
+
+// The walk of backward_walk<true> with the contribution tail.  m: the lane's pixel weight (0 outside the image); wmask: the lanes
+// with m > 0.  Per (quadrant, entry) with a counted pair: the wave total and the wave maximum of t = m dch (two fixed trees),
+// the count as a scalar popcount, and three atomics from three lanes — every one independent of the order of arrival.
+template <bool WEIGHTED>
+__device__ __forceinline__ void contrib_walk(const uint16_t* lp, int cnt, int base, const float4* s_r0, const float4* s_r1,
+                                             const float* s_bound, const uint32_t* s_id, float pxf, float pyf, BwdPix& st,
+                                             float m, uint64_t wmask, uint32_t aoff, ContribAcc* __restrict__ acc) {
+    for (int j = cnt - 1; j >= 0; --j) {
+        const int e = lp[j];
+        const float4 r0 = s_r0[e], r1 = s_r1[e];
+        const float dx = r0.x - pxf, dy = r0.y - pyf;
+        const PairAlpha a = pair_alpha(r0, r1, dx, dy);
+        const uint64_t validm = pair_valid(a, (uint32_t)(base + e), st.last, s_bound[e]);
+        if (validm == 0) continue;
+        const PairGrad g = pair_grad<false>(st, a, validm, r1, 0.f, [] { return 0.f; });   // dch = 0 on the masked lanes
+        const uint64_t counted = validm & wmask;
+        if (counted == 0) continue;                            // (T has moved on; nothing to add)
+        const float t = WEIGHTED ? m * g.dch : g.dch;
+        const float tot = wave_allreduce_sum_of_terms(t);
+        const uint32_t mx = wave_allreduce_max_u32(__float_as_uint(t));
+        const uint32_t gid = __builtin_amdgcn_readfirstlane(s_id[e]);
+        // lane k < 3 owns the 8-byte slot k of the row (sum, count, max): the address is the lane's own, as in reduce_and_add
+        char* slot = reinterpret_cast<char*>(acc + gid) + aoff;
+        if (aoff == 0) unsafeAtomicAdd(reinterpret_cast<double*>(slot), (double)tot);
+        else if (aoff == 8) atomicAdd(reinterpret_cast<unsigned long long*>(slot), (unsigned long long)__popcll(counted));
+        else if (aoff == 16) atomicMax(reinterpret_cast<uint32_t*>(slot), mx);
+    }
+}
+
+// One 256-thread workgroup per tile, one 8x8 quadrant per wave, as blend_absgrad_kernel (one shape for every tile count).
+// pixel_weights [H,W] (WEIGHTED): a negative or NaN weight counts as 0; finite weights only reach the products.
+template <bool WEIGHTED>
+__global__ __launch_bounds__(256) void blend_contrib_kernel(ViewParams vp, const GaussRec* __restrict__ rec,
+                                                            const uint32_t* __restrict__ ids,
+                                                            const uint2* __restrict__ ranges,
+                                                            const float* __restrict__ final_T,
+                                                            const uint32_t* __restrict__ n_contrib,
+                                                            const float* __restrict__ pixel_weights,
+                                                            ContribAcc* __restrict__ acc) {
+    __shared__ float4 s_r0[BATCH], s_r1[BATCH];
+    __shared__ float s_bound[BATCH];                       // sign_test_bound
+    __shared__ uint32_t s_id[BATCH];
+    __shared__ uint32_t s_mask[BATCH];
+    __shared__ uint16_t s_list[4][BATCH];
+    __shared__ uint32_t s_wmax[4];
+
+    const int num_tiles = vp.gx * vp.gy;
+    const int tile = swizzled_tile(blockIdx.x, num_tiles);
+    const int tx = tile % vp.gx, ty = tile / vp.gx;
+    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
+    const int px = tx * TILE + (w & 1) * 8 + (lane & 7);
+    const int py = ty * TILE + (w >> 1) * 8 + (lane >> 3);
+    const bool inside = px < vp.W && py < vp.H;
+    const float pxf = (float)px, pyf = (float)py;
+    const float tx0 = (float)(tx * TILE), ty0 = (float)(ty * TILE);
+    const uint2 range = ranges[tile];
+    const uint64_t lt_mask = (1ull << lane) - 1ull;
+    const size_t pix = (size_t)py * vp.W + px;
+
+    BwdPix st;
+    st.T = inside ? final_T[pix] : 1.0f;
+    st.last = inside ? n_contrib[pix] : 0u;
+    st.dL0 = st.dL1 = st.dL2 = st.dLd = 0.f;
+    st.S = 0.f;
+    float m = inside ? 1.0f : 0.0f;
+    if constexpr (WEIGHTED) {
+        const float pw = inside ? pixel_weights[pix] : 0.0f;
+        m = pw > 0.0f ? fminf(pw, 3.4028234664e38f) : 0.0f;    // NaN and negatives fail the comparison
+    }
+    const uint64_t wmask = __builtin_amdgcn_ballot_w64(m > 0.0f);
+    const uint32_t aoff = lane < 3 ? 8u * (uint32_t)lane : 0xFFFFFFFFu;      // byte offset of the lane's slot; none: no atomic
+
+    const uint32_t wave_last = wave_max_u32(st.last);
+    if (lane == 0) s_wmax[w] = wave_last;
+    __syncthreads();
+    const uint32_t tile_last = max(max(s_wmax[0], s_wmax[1]), max(s_wmax[2], s_wmax[3]));
+
+    const int nb = ((int)tile_last + BATCH - 1) / BATCH;
+    for (int b = nb - 1; b >= 0; --b) {
+        __syncthreads();                              // previous batch fully consumed
+        const int base = b * BATCH;
+        const int n = min(BATCH, (int)tile_last - base);
+        if (tid < n) {
+            const uint32_t id = ids[range.x + base + tid];
+            const float4 r0 = rec[id].r0, r1 = rec[id].r1;
+            const float4 r2 = rec[id].r2;
+            s_r0[tid] = doubled_w(r0); s_r1[tid] = r1; s_bound[tid] = sign_test_bound(r1.y); s_id[tid] = id;
+            s_mask[tid] = quadrant_mask(r0, r1.x, r2.w, tx0, ty0);
+        }
+        __syncthreads();
+        int cnt = 0;
+#pragma unroll
+        for (int c = 0; c < BATCH / 64; ++c) {
+            const int e = c * 64 + lane;
+            const bool hit = e < n && (uint32_t)(base + e) < wave_last && ((s_mask[e] >> w) & 1u);
+            const uint64_t bal = __ballot(hit);
+            if (hit) s_list[w][cnt + __popcll(bal & lt_mask)] = (uint16_t)e;
+            cnt += __popcll(bal);
+        }
+        contrib_walk<WEIGHTED>(s_list[w], cnt, base, s_r0, s_r1, s_bound, s_id, pxf, pyf, st, m, wmask, aoff, acc);
+    }
+}
+
+__global__ __launch_bounds__(256) void contrib_finish_kernel(int P, const ContribAcc* __restrict__ acc,
+                                                             float* __restrict__ weight_sum, float* __restrict__ weight_max,
+                                                             long long* __restrict__ pixel_count) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= P) return;
+    const ContribAcc a = acc[i];
+    weight_sum[i] = (float)a.sum;
+    weight_max[i] = __uint_as_float(a.max_bits);
+    pixel_count[i] = (long long)a.count;
+}
+
+// ---------------------------------------------------------------------------------------------
 // statistics for the algorithmic-bytes formula: D_trav = sum_tiles max_pixels n_contrib, V = #radii>0
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void tile_stats_kernel(ViewParams vp, const uint32_t* __restrict__ n_contrib,
@@ -1440,6 +1597,27 @@ hipError_t launch_blend_absgrad(const ViewParams& vp, int P, const char* geom, c
     constexpr float LN2 = 0.69314718055994530942f;
     hipLaunchKernelGGL(absgrad_finish_kernel, dim3((P + 255) / 256), dim3(256), 0, s, P, LN2 * vp.W, LN2 * vp.H,
                        (const double*)acc, out);
+    return hipGetLastError();
+}
+
+// msgs_contrib_accumulate: the replay (the four-waves-per-tile shape whatever the tile count) adds one view to `acc`, which the
+// caller cleared or carries over from earlier views; msgs_contrib_finish: the accumulator as three [P] arrays.
+hipError_t launch_blend_contrib(const ViewParams& vp, const char* geom, const uint32_t* ids, const uint2* ranges,
+                                const float* final_T, const uint32_t* n_contrib, const float* pixel_weights, void* acc,
+                                hipStream_t s) {
+    const int tiles = vp.gx * vp.gy;
+    if (tiles <= 0) return hipSuccess;
+    const GaussRec* rec = reinterpret_cast<const GaussRec*>(geom);
+    with_bool(pixel_weights != nullptr, [&](auto WEIGHTED) {
+        hipLaunchKernelGGL((blend_contrib_kernel<decltype(WEIGHTED)::value>), dim3(tiles), dim3(256), 0, s, vp, rec, ids, ranges,
+                           final_T, n_contrib, pixel_weights, (ContribAcc*)acc);
+    });
+    return hipGetLastError();
+}
+
+hipError_t launch_contrib_finish(int P, const void* acc, float* weight_sum, float* weight_max, int64_t* pixel_count, hipStream_t s) {
+    hipLaunchKernelGGL(contrib_finish_kernel, dim3((P + 255) / 256), dim3(256), 0, s, P, (const ContribAcc*)acc, weight_sum,
+                       weight_max, (long long*)pixel_count);
     return hipGetLastError();
 }
 

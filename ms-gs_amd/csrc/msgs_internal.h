@@ -781,6 +781,13 @@ hipError_t launch_blend_backward(const ViewParams& vp, const char* geom, const u
 hipError_t launch_blend_absgrad(const ViewParams& vp, int P, const char* geom, const uint32_t* ids, const uint2* ranges,
                                 const float* final_T, const uint32_t* n_contrib, const float* dL_dcolor, const float* dL_ddepth,
                                 const float* dL_dalpha, double* acc, float* out, hipStream_t s);
+// msgs_contrib_* (SPEC M11): one accumulator row per Gaussian {double weight_sum, uint64 pixel_count, uint32 bits of weight_max,
+// pad}; the replay adds a view to it (pixel_weights [H,W] or NULL), the finish converts it to three [P] arrays
+constexpr size_t CONTRIB_ACC_BYTES = 24;
+hipError_t launch_blend_contrib(const ViewParams& vp, const char* geom, const uint32_t* ids, const uint2* ranges,
+                                const float* final_T, const uint32_t* n_contrib, const float* pixel_weights, void* acc,
+                                hipStream_t s);
+hipError_t launch_contrib_finish(int P, const void* acc, float* weight_sum, float* weight_max, int64_t* pixel_count, hipStream_t s);
 // heaviest-first launch order of the one-wave-per-tile backward from the forward's per-tile traversal lengths
 hipError_t launch_tile_order(const ViewParams& vp, const uint32_t* tile_last, uint32_t* tile_order, hipStream_t s);
 hipError_t launch_blend_lane_stats(const ViewParams& vp, const char* geom, const uint32_t* ids, const uint2* ranges,

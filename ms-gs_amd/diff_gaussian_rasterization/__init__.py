@@ -28,7 +28,7 @@ import torch.nn as nn
 from . import _backend as _C
 
 __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "rasterize_gaussians_raw",
-           "deferred_forward", "GradAccumulator", "set_grad_accumulator"]
+           "deferred_forward", "GradAccumulator", "set_grad_accumulator", "ContributionScores", "ContributionAccumulator"]
 
 
 class GaussianRasterizationSettings(NamedTuple):
@@ -1350,6 +1350,86 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
                                      *_extra_inputs(raster_settings, return_alpha, absgrad, means2D))
 
 
+# Contribution scores (4.11): what every Gaussian did to the images of one or many views, the criterion of
+# contribution-based pruning (LightGaussian's global significance, RadSplat's max contribution, Mini-Splatting's importance).
+# With w_ip = alpha_ip T_ip, the blend weight of Gaussian i in pixel p, and an optional per-pixel weight map m_p >= 0:
+#     weight_sum = sum_p m_p w_ip      weight_max = max_p m_p w_ip      pixel_count = #{p : m_p > 0, the pair was blended}
+# Across views they combine as sum, max, sum — in ONE accumulator that every view's replay adds to (msgs_contrib_accumulate).
+class ContributionScores(NamedTuple):
+    weight_sum: torch.Tensor       # [P] float32
+    weight_max: torch.Tensor       # [P] float32
+    pixel_count: torch.Tensor      # [P] int64
+
+
+_contrib_probe = None              # tests: a callable (call, state) run behind the forward of every contributions() call
+
+
+def _refuse_contrib_in_verification_mode():
+    if _C.lib.msgs_get_deterministic():
+        raise ValueError("contribution scores are not offered in the verification mode (set_deterministic): that mode checks the "
+                         "reference's arithmetic, it does not train or prune")
+
+
+class ContributionAccumulator:
+    """The scores of P Gaussians over any number of views: owns the accumulator (24 bytes per Gaussian), GaussianRasterizer.
+    contributions(..., into=acc) adds a view to it, scores() reads it, reset() starts over.  All on the current stream of the
+    caller: add and read on one stream, or order the streams yourself."""
+
+    def __init__(self, P, device):
+        _refuse_contrib_in_verification_mode()
+        self.P, self.device = int(P), torch.device(device)
+        if self.P < 0:
+            raise ValueError("P must be >= 0")
+        if self.P > 0 and self.device.type != "cuda":
+            raise RuntimeError("diff_gaussian_rasterization (MI355X build): the accumulator must live on a HIP device ('cuda')")
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.nbytes = int(_C.lib.msgs_contrib_scratch_bytes(self.P))
+        self.buf = torch.empty(self.nbytes, dtype=torch.uint8, device=self.device) if self.P > 0 else None
+        self.views = 0
+
+    def reset(self):
+        """forget every view: the next add clears the accumulator (no launch here)"""
+        self.views = 0
+
+    def _add(self, call, state, pixel_weights):
+        geom, binning, image, D = state
+        dev = self.device
+        with _on_device(dev):
+            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            _C.check(_C.lib.msgs_contrib_accumulate(
+                call.view_ref, self.P, _ptr(geom), geom.numel(), D, _ptr(binning), binning.numel() if binning is not None else 0,
+                _ptr(image), image.numel(), _ptr(pixel_weights), _ptr(self.buf), self.nbytes, int(self.views == 0), stream),
+                "msgs_contrib_accumulate")
+        self.views += 1
+
+    def scores(self):
+        """ContributionScores of the views added so far (zeros before the first)"""
+        dev, P = self.device, self.P
+        if P == 0 or self.views == 0:
+            return ContributionScores(torch.zeros(P, dtype=torch.float32, device=dev), torch.zeros(P, dtype=torch.float32, device=dev),
+                                      torch.zeros(P, dtype=torch.int64, device=dev))
+        ws = torch.empty(P, dtype=torch.float32, device=dev)
+        wm = torch.empty(P, dtype=torch.float32, device=dev)
+        pc = torch.empty(P, dtype=torch.int64, device=dev)
+        with _on_device(dev):
+            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            _C.check(_C.lib.msgs_contrib_finish(P, _ptr(self.buf), self.nbytes, _ptr(ws), _ptr(wm), _ptr(pc), stream),
+                     "msgs_contrib_finish")
+        return ContributionScores(ws, wm, pc)
+
+
+def _check_pixel_weights(pw, H, W, dev):
+    if pw is None:
+        return None
+    if not isinstance(pw, torch.Tensor) or pw.dtype != torch.float32 or tuple(pw.shape) != (H, W):
+        raise ValueError(f"pixel_weights must be a float32 tensor of shape [{H}, {W}], got "
+                         f"{getattr(pw, 'dtype', type(pw).__name__)} {tuple(getattr(pw, 'shape', ()))}")
+    if pw.device != dev:
+        raise ValueError(f"pixel_weights must live on {dev}, got {pw.device}")
+    return pw.detach() if pw.is_contiguous() else pw.detach().contiguous()
+
+
 class GaussianRasterizer(nn.Module):
     def __init__(self, raster_settings, return_alpha=False, absgrad=False):
         """return_alpha=True: forward / forward_raw return the 6-tuple (color, acc_pixel_size, depth, radii, pixel_sizes, alpha)
@@ -1405,6 +1485,50 @@ class GaussianRasterizer(nn.Module):
                 _C.check(lib.msgs_preprocess_only(C.byref(call.view), C.byref(call.g), _ptr(radii), _ptr(pixel_sizes),
                                                   _ptr(geom), geom.numel(), stream), "msgs_preprocess_only")
         return radii, pixel_sizes
+
+    def contributions(self, means3D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None,
+                      max_pixel_sizes=None, min_pixel_sizes=None, base_mask=None, *, pixel_weights=None, into=None):
+        """Contribution scores of this view: ContributionScores(weight_sum, weight_max, pixel_count), each
+        [P], with w = alpha T the blend weight of a Gaussian in a pixel — its sum and maximum over the pixels and the number of
+        pixels it was blended into.  pixel_weights [H,W] float32 (a mask, a per-pixel error ...) multiplies w per pixel and a
+        pixel with weight <= 0 (or NaN) does not count.  One ordinary forward of the view (culling, lists and termination are
+        the render's) and one replay of the blend walk; no gradients, and nothing of a surrounding render / backward changes.
+        Colours do not enter: with neither shs nor colors_precomp, zeros stand in.
+        into: a ContributionAccumulator for [P] on this device — the view is ADDED to it (sum, max, sum across views) and
+        nothing is returned; read into.scores() after the last view.  Without it: the scores of this one view.
+        Not offered in the verification mode (set_deterministic): ValueError before any launch."""
+        rs = self.raster_settings
+        if shs is not None and colors_precomp is not None:
+            raise Exception('Please provide at most one of either SHs or precomputed colors!')
+        if ((scales is None or rotations is None) and cov3D_precomp is None) or \
+                ((scales is not None or rotations is not None) and cov3D_precomp is not None):
+            raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
+        _refuse_contrib_in_verification_mode()
+        with torch.no_grad():
+            P, dev = int(means3D.shape[0]), means3D.device
+            if P > 0 and dev.type != "cuda":
+                raise RuntimeError("diff_gaussian_rasterization (MI355X build): tensors must live on a HIP device "
+                                   "('cuda'); there is no CPU path")
+            pw = _check_pixel_weights(pixel_weights, int(rs.image_height), int(rs.image_width), dev)
+            if into is not None and (not isinstance(into, ContributionAccumulator) or into.P != P or into.device != dev):
+                raise ValueError(f"into must be a ContributionAccumulator for {P} Gaussians on {dev}")
+            acc = into if into is not None else ContributionAccumulator(P, dev)
+            if P > 0:
+                if shs is None and colors_precomp is None:
+                    colors_precomp = torch.zeros(P, 3, dtype=torch.float32, device=dev)
+                call = _Call(rs, means3D, _opt(shs), _opt(colors_precomp), opacities, _opt(scales), _opt(rotations),
+                             _opt(cov3D_precomp), _opt(max_pixel_sizes), _opt(min_pixel_sizes), None, None, _opt(base_mask))
+                pending, _deferred.pending = getattr(_deferred, "pending", None), None      # not deferred: the replay reads D
+                try:
+                    state = _forward_impl(call)[-1]
+                finally:
+                    _deferred.pending = pending
+                if _contrib_probe is not None:
+                    _contrib_probe(call, state)
+                acc._add(call, state, pw)
+            else:
+                acc.views += 1
+            return None if into is not None else acc.scores()
 
     def forward_raw(self, xyz, means2D, features_dc, features_rest, opacity_raw, scaling_raw, rotation_raw,
                     max_pixel_sizes=None, min_pixel_sizes=None, occ_multiplier=None, dc_delta=None, base_mask=None):

@@ -197,6 +197,12 @@ def _load():
     lib.msgs_absgrad_scratch_bytes.argtypes = [C.c_int32]
     lib.msgs_absgrad.restype = C.c_int
     lib.msgs_absgrad.argtypes = [C.POINTER(View), C.c_int32, vp, sz, C.c_int64, vp, sz, vp, sz, vp, vp, vp, vp, sz, vp, vp]
+    lib.msgs_contrib_scratch_bytes.restype = sz
+    lib.msgs_contrib_scratch_bytes.argtypes = [C.c_int32]
+    lib.msgs_contrib_accumulate.restype = C.c_int
+    lib.msgs_contrib_accumulate.argtypes = [C.POINTER(View), C.c_int32, vp, sz, C.c_int64, vp, sz, vp, sz, vp, vp, sz, C.c_int32, vp]
+    lib.msgs_contrib_finish.restype = C.c_int
+    lib.msgs_contrib_finish.argtypes = [C.c_int32, vp, sz, vp, vp, vp, vp]
     lib.msgs_backward_per_gaussian.restype = C.c_int
     lib.msgs_backward_per_gaussian.argtypes = [C.POINTER(View), C.POINTER(Gaussians), vp, vp, sz, vp, C.POINTER(Grads), vp]
     lib.msgs_sh_grad_from_views.restype = C.c_int
@@ -269,7 +275,8 @@ EXPORTS = ("msgs_abi_version", "msgs_error_string", "msgs_geom_bytes", "msgs_sta
            "msgs_backward_scratch_bytes_deterministic_depth", "msgs_backward_with_camera", "msgs_camera_grad_scratch_bytes",
            "msgs_densify_scratch_bytes", "msgs_densify_select", "msgs_densify_apply",
            "msgs_alpha_map", "msgs_backward_with_alpha", "msgs_bg_grad_scratch_bytes", "msgs_bg_grad",
-           "msgs_absgrad_scratch_bytes", "msgs_absgrad")
+           "msgs_absgrad_scratch_bytes", "msgs_absgrad",
+           "msgs_contrib_scratch_bytes", "msgs_contrib_accumulate", "msgs_contrib_finish")
 
 
 def check(rc, where):
