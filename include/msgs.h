@@ -189,7 +189,9 @@ typedef struct msgs_grads {
                                 * the caller can start the all-gather of the factors while the rest of msgs_backward runs */
     int32_t scratch_is_clear;  /* non-zero: the first msgs_backward_scratch_bytes(P) bytes of `scratch` were handed to the
                                 * forward of THIS view as grad_records (it cleared them during the blend) and nothing has
-                                * written them since: msgs_backward skips its own fill launch.  0: msgs_backward clears them */
+                                * written them since: msgs_backward skips its own fill launch.  0: msgs_backward clears them.
+                                * Also non-zero when the records hold sums that are to be INCLUDED: msgs_features_backward adds
+                                * its geometry sums to cleared records in front of msgs_backward*, which then adds on top */
     int32_t accumulate;        /* non-zero: ADD this view's gradients to what the output tensors hold (dL_dmeans3D, dL_dshs /
                                 * dL_dfeatures_*, dL_dcolors, dL_dopacities, dL_dscales, dL_drotations, dL_dcov3D), leaving the
                                 * rows of Gaussians this view did not render untouched — the views of one optimizer step
@@ -405,6 +407,42 @@ int msgs_contrib_accumulate(const msgs_view_t* view, int32_t P,
                             void* acc, size_t acc_bytes, int32_t clear_first, void* stream);
 int msgs_contrib_finish(int32_t P, const void* acc, size_t acc_bytes,
                         float* weight_sum, float* weight_max, int64_t* pixel_count, void* stream);
+
+/* ---- feature channels: per-Gaussian vectors splatted with the blend weights (DESIGN.md SPEC M12, 4.12) ------ */
+/* features [P,C] float32 (device, C >= 1, 4-byte aligned; 16-byte row loads where C % 4 == 0 and the base allow).  With
+ * w_ip = alpha_ip T_ip the blend weight of Gaussian i in pixel p, over exactly the pairs msgs_backward* counts:
+ *     msgs_features_forward:   out [C,H,W] float32,  F[c,p] = sum_i f_ic w_ip
+ * with NO background term (a pixel with no blended entry gets 0.0f; compose a background outside with the alpha map).  Rows of
+ * Gaussians in no tile list are never read.
+ *     msgs_features_backward:  dL_dfeatures [P,C] float32 (always overwritten),  dL/df_ic = sum_p G_cp w_ip,  G = dL_dfeature_map
+ * exactly 0 for a Gaussian in no list.  grad_records (NULL = no geometry share; else >= msgs_backward_scratch_bytes(P), the
+ * buffer handed to msgs_backward* as `scratch`): the features act as C more colour channels over background 0, and the six
+ * sums of their q_f (sum q dx, q dy, q dx^2, q dx dy, q dy^2, q) are ADDED to record slots 0..5.  The records must already be
+ * zero (cleared by the forward of this view, or by the caller) or hold sums that are to be included; msgs_backward* is then
+ * called with msgs_grads_t.scratch_is_clear = 1, adds its own sums on top, and its per-Gaussian stage consumes the total:
+ * means, opacity, scales / rotations / cov3D and the camera receive the features' share, SH and colours nothing.
+ * `scratch` (>= msgs_features_scratch_bytes(P, C), 8-byte aligned, no clearing needed): one block of double accumulators.
+ * Both read what the forward of this view left in geom / binning / image_state (single pass, speculative stage 2 or its redo,
+ * depth slabs, occlusion cut-off alike).  P == 0 or num_instances == 0: the forward zero-fills out, the backward zero-fills
+ * dL_dfeatures, no replay runs.  Not offered in the verification mode (MSGS_ERR_INVALID_ARG). */
+size_t msgs_features_scratch_bytes(int32_t P, int32_t C);
+int msgs_features_forward(const msgs_view_t* view, int32_t P,
+                          const void* geom, size_t geom_bytes,
+                          int64_t num_instances,
+                          const void* binning, size_t binning_bytes,
+                          const void* image_state, size_t image_bytes,
+                          const float* features, int32_t C,
+                          float* out, void* stream);
+int msgs_features_backward(const msgs_view_t* view, int32_t P,
+                           const void* geom, size_t geom_bytes,
+                           int64_t num_instances,
+                           const void* binning, size_t binning_bytes,
+                           const void* image_state, size_t image_bytes,
+                           const float* features, int32_t C,
+                           const float* dL_dfeature_map,
+                           void* grad_records, size_t grad_records_bytes,
+                           void* scratch, size_t scratch_bytes,
+                           float* dL_dfeatures, void* stream);
 
 /* msgs_backward_per_gaussian: the per-Gaussian half of msgs_backward ALONE (2-D covariance backward, projection, SH,
  * scale / quaternion chain — upstream's computeCov2DCUDA + preprocessCUDA backward, SURVEY 2.2 K8 + K9) on per-Gaussian

@@ -868,6 +868,64 @@ int msgs_contrib_finish(int32_t P, const void* acc, size_t acc_bytes, float* wei
     HIP_TRY(launch_contrib_finish(P, acc, weight_sum, weight_max, pixel_count, (hipStream_t)stream));
     return MSGS_OK;
 }
+
+size_t msgs_features_scratch_bytes(int32_t P, int32_t C) { (void)C; return features_scratch_bytes(P); }
+
+int msgs_features_forward(const msgs_view_t* view, int32_t P, const void* geom_v, size_t geom_bytes, int64_t D,
+                          const void* binning_v, size_t binning_bytes, const void* image_v, size_t image_bytes,
+                          const float* features, int32_t C, float* out, void* stream) {
+    if (!view || P < 0 || D < 0 || C < 1 || view->image_width < 1 || view->image_height < 1 || !out) return MSGS_ERR_INVALID_ARG;
+    if (g_deterministic.load() != 0) return MSGS_ERR_INVALID_ARG;            // not offered in the verification mode
+    const int W = view->image_width, H = view->image_height;
+    hipStream_t s = (hipStream_t)stream;
+    if (P == 0 || D == 0) {                                                  // no instance: no pair, every pixel is 0
+        HIP_TRY(launch_zero(out, sizeof(float) * (size_t)C * W * H, s));
+        return debug_sync(view, s);
+    }
+    if (!geom_v || !binning_v || !image_v || !features || ((uintptr_t)features & 3)) return MSGS_ERR_INVALID_ARG;
+    if (geom_bytes < msgs_geom_bytes(P) || binning_bytes < msgs_binning_bytes(D, W, H) || image_bytes < msgs_image_bytes(W, H))
+        return MSGS_ERR_CAPACITY;
+    const ViewParams vp = make_view_params(view);
+    const BinningLayout BL(D, vp.gx * vp.gy);
+    const ImageLayout IL(W, H);
+    const char* binning = (const char*)binning_v;
+    const char* image = (const char*)image_v;
+    HIP_TRY(launch_blend_features_forward(vp, (const char*)geom_v, (const uint32_t*)(binning + BL.ids),
+                                          (const uint2*)(binning + BL.ranges), (const float*)(image + IL.final_T),
+                                          (const uint32_t*)(image + IL.n_contrib), features, C, out, s));
+    return debug_sync(view, s);
+}
+
+int msgs_features_backward(const msgs_view_t* view, int32_t P, const void* geom_v, size_t geom_bytes, int64_t D,
+                           const void* binning_v, size_t binning_bytes, const void* image_v, size_t image_bytes,
+                           const float* features, int32_t C, const float* dL_dfeature_map, void* grad_records,
+                           size_t grad_records_bytes, void* scratch, size_t scratch_bytes, float* dL_dfeatures, void* stream) {
+    if (!view || P < 0 || D < 0 || C < 1 || view->image_width < 1 || view->image_height < 1) return MSGS_ERR_INVALID_ARG;
+    if (g_deterministic.load() != 0) return MSGS_ERR_INVALID_ARG;            // its scratch holds another layout
+    if (P == 0) return MSGS_OK;                                              // dL_dfeatures is [0, C]
+    if (!dL_dfeatures) return MSGS_ERR_INVALID_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    if (D == 0) {                                                            // no pair: zero gradients, nothing for the records
+        HIP_TRY(launch_zero(dL_dfeatures, sizeof(float) * (size_t)P * C, s));
+        return debug_sync(view, s);
+    }
+    if (!geom_v || !binning_v || !image_v || !features || !dL_dfeature_map || !scratch) return MSGS_ERR_INVALID_ARG;
+    if (((uintptr_t)features & 3) || ((uintptr_t)scratch & 7) || ((uintptr_t)grad_records & 7)) return MSGS_ERR_INVALID_ARG;
+    const int W = view->image_width, H = view->image_height;
+    if (geom_bytes < msgs_geom_bytes(P) || binning_bytes < msgs_binning_bytes(D, W, H) || image_bytes < msgs_image_bytes(W, H) ||
+        scratch_bytes < features_scratch_bytes(P) || (grad_records && grad_records_bytes < msgs_backward_scratch_bytes(P)))
+        return MSGS_ERR_CAPACITY;
+    const ViewParams vp = make_view_params(view);
+    const BinningLayout BL(D, vp.gx * vp.gy);
+    const ImageLayout IL(W, H);
+    const char* binning = (const char*)binning_v;
+    const char* image = (const char*)image_v;
+    HIP_TRY(launch_blend_features_backward(vp, P, (const char*)geom_v, (const uint32_t*)(binning + BL.ids),
+                                           (const uint2*)(binning + BL.ranges), (const float*)(image + IL.final_T),
+                                           (const uint32_t*)(image + IL.n_contrib), features, C, dL_dfeature_map,
+                                           (grad_acc_t*)grad_records, (double*)scratch, dL_dfeatures, s));
+    return debug_sync(view, s);
+}
 }  // extern "C"
 
 namespace {

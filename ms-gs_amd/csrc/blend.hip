@@ -1338,6 +1338,276 @@ __global__ __launch_bounds__(256) void contrib_finish_kernel(int P, const Contri
 }
 
 // ---------------------------------------------------------------------------------------------
+// Feature channels (DESIGN.md SPEC M12, 4.12; msgs_features_forward / msgs_features_backward): per-Gaussian vectors f_i [C]
+// splatted with the blend weights w_ip = alpha_ip T_ip = PairGrad::dch, over background 0:
+//     F[c,p] = sum_i f_ic w_ip          dL/df_ic = sum_p G_cp w_ip          (G = dL/dF)
+// and, as C more colour channels, a share of dL/dalpha: q_f from e_ip = sum_c G_cp f_ic in the place of g_i with a recurrence S_f
+// of its own that starts at 0; its six geometry sums are ADDED to record slots 0..5 in front of the ordinary blend backward.
+// Two more replays of the back-to-front walk of blend_backward_kernel (quadrant lists, pair_alpha / pair_valid / pair_grad as
+// in blend_contrib_kernel: the same pairs, the same weights).  Staging as there, except that no colour is read here: the two
+// colour slots of the staged r1 carry the sign-test bound and the quadrant mask bits instead of arrays of their own — the 2 KB
+// of LDS that keep eight waves per SIMD beside the feature block.  Channels go in blocks of CB, one launch per block — every
+// block is linear and independent, the geometry sums included.  A block's CB features of each staged entry lie in LDS and are
+// read at a wave-uniform address.  Opt-in: nothing of the default path calls or shares a kernel with them.
+// ---------------------------------------------------------------------------------------------
+constexpr int FEAT_CB = 8;          // channels per launch (the resource table behind the choice)
+
+// Channels c0 .. c0 + CB - 1 of row `id` of features [P, C] -> dst[0 .. CB/4); channels at or behind C are staged as zeros.
+// vec: C % 4 == 0 and a 16-byte aligned base (c0 is a multiple of CB): 16-byte loads; the same values either way.
+template <int CB>
+__device__ __forceinline__ void stage_feature_row(float4* dst, const float* __restrict__ features, uint32_t id, int C, int c0,
+                                                  bool vec) {
+    const float* row = features + (size_t)id * C + c0;
+#pragma unroll
+    for (int k = 0; k < CB / 4; ++k) {
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        const int c = c0 + 4 * k;
+        if (vec) {
+            if (c < C) v = *reinterpret_cast<const float4*>(row + 4 * k);
+        } else {
+            if (c + 0 < C) v.x = row[4 * k + 0];
+            if (c + 1 < C) v.y = row[4 * k + 1];
+            if (c + 2 < C) v.z = row[4 * k + 2];
+            if (c + 3 < C) v.w = row[4 * k + 3];
+        }
+        dst[k] = v;
+    }
+}
+
+// The walk of contrib_walk with CB accumulators per lane: one FMA per (pair, channel), back to front.  pair_grad on a zero dL/dC
+// (only its T recurrence and dch stay alive); dch = 0 on the masked lanes.
+template <int CB>
+__device__ __forceinline__ void features_forward_walk(const uint16_t* lp, int cnt, int base, const float4* s_r0, const float4* s_r1,
+                                                      const float4* s_f, float pxf, float pyf, BwdPix& st,
+                                                      float (&acc)[CB]) {
+    for (int j = cnt - 1; j >= 0; --j) {
+        const int e = lp[j];
+        const float4 r0 = s_r0[e], r1 = s_r1[e];
+        const float dx = r0.x - pxf, dy = r0.y - pyf;
+        const PairAlpha a = pair_alpha(r0, r1, dx, dy);
+        const uint64_t validm = pair_valid(a, (uint32_t)(base + e), st.last, r1.z);
+        if (validm == 0) continue;
+        const PairGrad g = pair_grad<false>(st, a, validm, make_float4(r1.x, r1.y, 0.f, 0.f), 0.f, [] { return 0.f; });
+#pragma unroll
+        for (int k = 0; k < CB / 4; ++k) {
+            const float4 f = s_f[e * (CB / 4) + k];
+            acc[4 * k + 0] = fmaf(f.x, g.dch, acc[4 * k + 0]); acc[4 * k + 1] = fmaf(f.y, g.dch, acc[4 * k + 1]);
+            acc[4 * k + 2] = fmaf(f.z, g.dch, acc[4 * k + 2]); acc[4 * k + 3] = fmaf(f.w, g.dch, acc[4 * k + 3]);
+        }
+    }
+}
+
+// out [C,H,W]: channels c0 .. c0 + CB - 1 (the real ones) of every inside pixel, plain stores; a pixel with no counted pair
+// stores 0.  One 256-thread workgroup per tile, one 8x8 quadrant per wave, as blend_contrib_kernel.
+template <int CB>
+__global__ __launch_bounds__(256) void blend_features_forward_kernel(ViewParams vp, const GaussRec* __restrict__ rec,
+                                                                     const uint32_t* __restrict__ ids,
+                                                                     const uint2* __restrict__ ranges,
+                                                                     const float* __restrict__ final_T,
+                                                                     const uint32_t* __restrict__ n_contrib,
+                                                                     const float* __restrict__ features, int C, int c0, int vec,
+                                                                     float* __restrict__ out) {
+    static_assert(CB % 4 == 0, "rows are staged as float4");
+    __shared__ float4 s_r0[BATCH], s_r1[BATCH];           // s_r1: {C', p0', sign_test_bound, quadrant mask bits}: no colour here
+    __shared__ float4 s_f[BATCH * (CB / 4)];               // the block's CB features of every staged entry
+    __shared__ uint16_t s_list[4][BATCH];
+    __shared__ uint32_t s_wmax[4];
+
+    const int num_tiles = vp.gx * vp.gy;
+    const int tile = swizzled_tile(blockIdx.x, num_tiles);
+    const int tx = tile % vp.gx, ty = tile / vp.gx;
+    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
+    const int px = tx * TILE + (w & 1) * 8 + (lane & 7);
+    const int py = ty * TILE + (w >> 1) * 8 + (lane >> 3);
+    const bool inside = px < vp.W && py < vp.H;
+    const float pxf = (float)px, pyf = (float)py;
+    const float tx0 = (float)(tx * TILE), ty0 = (float)(ty * TILE);
+    const uint2 range = ranges[tile];
+    const uint64_t lt_mask = (1ull << lane) - 1ull;
+    const size_t N = (size_t)vp.W * vp.H;
+    const size_t pix = (size_t)py * vp.W + px;
+
+    BwdPix st;
+    st.T = inside ? final_T[pix] : 1.0f;
+    st.last = inside ? n_contrib[pix] : 0u;
+    st.dL0 = st.dL1 = st.dL2 = st.dLd = 0.f;
+    st.S = 0.f;
+    float acc[CB];
+#pragma unroll
+    for (int c = 0; c < CB; ++c) acc[c] = 0.f;
+
+    const uint32_t wave_last = wave_max_u32(st.last);
+    if (lane == 0) s_wmax[w] = wave_last;
+    __syncthreads();
+    const uint32_t tile_last = max(max(s_wmax[0], s_wmax[1]), max(s_wmax[2], s_wmax[3]));
+
+    const int nb = ((int)tile_last + BATCH - 1) / BATCH;
+    for (int b = nb - 1; b >= 0; --b) {
+        __syncthreads();                              // previous batch fully consumed
+        const int base = b * BATCH;
+        const int n = min(BATCH, (int)tile_last - base);
+        if (tid < n) {
+            const uint32_t id = ids[range.x + base + tid];
+            const float4 r0 = rec[id].r0, r1 = rec[id].r1;
+            const float4 r2 = rec[id].r2;
+            s_r0[tid] = doubled_w(r0);
+            s_r1[tid] = make_float4(r1.x, r1.y, sign_test_bound(r1.y), __uint_as_float(quadrant_mask(r0, r1.x, r2.w, tx0, ty0)));
+            stage_feature_row<CB>(s_f + tid * (CB / 4), features, id, C, c0, vec != 0);
+        }
+        __syncthreads();
+        int cnt = 0;
+#pragma unroll
+        for (int c = 0; c < BATCH / 64; ++c) {
+            const int e = c * 64 + lane;
+            const bool hit = e < n && (uint32_t)(base + e) < wave_last && ((__float_as_uint(s_r1[e].w) >> w) & 1u);
+            const uint64_t bal = __ballot(hit);
+            if (hit) s_list[w][cnt + __popcll(bal & lt_mask)] = (uint16_t)e;
+            cnt += __popcll(bal);
+        }
+        features_forward_walk<CB>(s_list[w], cnt, base, s_r0, s_r1, s_f, pxf, pyf, st, acc);
+    }
+    if (inside) {
+#pragma unroll
+        for (int c = 0; c < CB; ++c)
+            if (c0 + c < C) out[(size_t)(c0 + c) * N + pix] = acc[c];
+    }
+}
+
+// The backward walk.  G: the lane's CB values of dL/dF (0 outside the image and for the channels behind C).
+// GEOM: e = sum_c G_c f_c enters pair_grad as the only colour (red = e under dL/dC = (1, 0, 0), so g_i = e), st.S is S_f; the
+// six sums of q_f go to record slots 0..5 with the ordinary reduce_and_add (zeros to 6..8: still one atomic instruction).
+// Always: the CB products G_c dch are reduce-scattered by row_reduce_scatter (components 0..7 of its nine) so that the eight
+// lanes 0, 1, 4, 5, 8, 9, 12, 13 each own one wave total, and ONE atomic instruction adds them at the lanes' own addresses into
+// the entry's row of the [P, CB] double accumulator (float32 totals add up exactly there: the same bits on every run).
+template <int CB, bool GEOM>
+__device__ __forceinline__ void features_backward_walk(const uint16_t* lp, int cnt, int base, const float4* s_r0,
+                                                       const float4* s_r1, const uint32_t* s_id,
+                                                       const float4* s_f, float pxf, float pyf, BwdPix& st, const float (&G)[CB],
+                                                       bool alane, uint32_t aoff, grad_acc_t* __restrict__ grad_rec, bool flane,
+                                                       uint32_t foff, double* __restrict__ acc) {
+    static_assert(CB == 8, "the reduce-scatter of row_reduce_scatter delivers eight components");
+    for (int j = cnt - 1; j >= 0; --j) {
+        const int e = lp[j];
+        const float4 r0 = s_r0[e], r1 = s_r1[e];
+        const float dx = r0.x - pxf, dy = r0.y - pyf;
+        const PairAlpha a = pair_alpha(r0, r1, dx, dy);
+        const uint64_t validm = pair_valid(a, (uint32_t)(base + e), st.last, r1.z);
+        if (validm == 0) continue;
+        PairGrad g;
+        if constexpr (GEOM) {
+            const float4 f0 = s_f[e * 2], f1 = s_f[e * 2 + 1];
+            float ef = G[0] * f0.x;
+            ef = fmaf(G[1], f0.y, ef); ef = fmaf(G[2], f0.z, ef); ef = fmaf(G[3], f0.w, ef);
+            ef = fmaf(G[4], f1.x, ef); ef = fmaf(G[5], f1.y, ef); ef = fmaf(G[6], f1.z, ef); ef = fmaf(G[7], f1.w, ef);
+            g = pair_grad<false>(st, a, validm, make_float4(r1.x, r1.y, ef, 0.f), 0.f, [] { return 0.f; });
+            const BwdSums v = {g.q * dx, g.q * dy, g.q * a.ev.dxx, g.q * a.ev.dxy, g.q * a.ev.dyy, g.q, 0.f, 0.f, 0.f};
+            reduce_and_add<false>(v, 0.f, [](float x) { return cross_row_allreduce(x); }, [=] { return s_id[e]; }, grad_rec,
+                                  alane, aoff);
+        } else {
+            g = pair_grad<false>(st, a, validm, make_float4(r1.x, r1.y, 0.f, 0.f), 0.f, [] { return 0.f; });
+        }
+        const BwdSums u = {G[0] * g.dch, G[1] * g.dch, G[2] * g.dch, G[3] * g.dch, G[4] * g.dch, G[5] * g.dch, G[6] * g.dch,
+                           G[7] * g.dch, 0.f};
+        const float tot = cross_row_allreduce(row_reduce_scatter<false>(u, 0.f));
+        const uint32_t gid = __builtin_amdgcn_readfirstlane(s_id[e]);
+        if (flane) unsafeAtomicAdd(acc + (size_t)gid * CB + foff, (double)tot);
+    }
+}
+
+// dL_dF [C,H,W]; acc [P, CB] doubles (this block's channels; cleared by the caller).  GEOM = false (no geometry input requires
+// grad): no feature is staged or read, no S_f, no q_f, no record atomic.
+template <int CB, bool GEOM>
+__global__ __launch_bounds__(256) void blend_features_backward_kernel(ViewParams vp, const GaussRec* __restrict__ rec,
+                                                                      const uint32_t* __restrict__ ids,
+                                                                      const uint2* __restrict__ ranges,
+                                                                      const float* __restrict__ final_T,
+                                                                      const uint32_t* __restrict__ n_contrib,
+                                                                      const float* __restrict__ features, int C, int c0, int vec,
+                                                                      const float* __restrict__ dL_dF,
+                                                                      grad_acc_t* __restrict__ grad_rec,
+                                                                      double* __restrict__ acc) {
+    static_assert(CB % 4 == 0, "rows are staged as float4");
+    __shared__ float4 s_r0[BATCH], s_r1[BATCH];           // s_r1: {C', p0', sign_test_bound, quadrant mask bits}: no colour here
+    __shared__ float4 s_f[GEOM ? BATCH * (CB / 4) : 1];    // the block's CB features of every staged entry
+    __shared__ uint32_t s_id[BATCH];
+    __shared__ uint16_t s_list[4][BATCH];
+    __shared__ uint32_t s_wmax[4];
+
+    const int num_tiles = vp.gx * vp.gy;
+    const int tile = swizzled_tile(blockIdx.x, num_tiles);
+    const int tx = tile % vp.gx, ty = tile / vp.gx;
+    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
+    const int px = tx * TILE + (w & 1) * 8 + (lane & 7);
+    const int py = ty * TILE + (w >> 1) * 8 + (lane >> 3);
+    const bool inside = px < vp.W && py < vp.H;
+    const float pxf = (float)px, pyf = (float)py;
+    const float tx0 = (float)(tx * TILE), ty0 = (float)(ty * TILE);
+    const uint2 range = ranges[tile];
+    const uint64_t lt_mask = (1ull << lane) - 1ull;
+    const size_t N = (size_t)vp.W * vp.H;
+    const size_t pix = (size_t)py * vp.W + px;
+
+    BwdPix st;
+    st.T = inside ? final_T[pix] : 1.0f;
+    st.last = inside ? n_contrib[pix] : 0u;
+    st.dL0 = GEOM ? 1.f : 0.f;                             // g_i = red = e (features_backward_walk)
+    st.dL1 = st.dL2 = st.dLd = 0.f;
+    st.S = 0.f;                                            // S_f: no background term
+    float G[CB];
+#pragma unroll
+    for (int c = 0; c < CB; ++c) G[c] = (inside && c0 + c < C) ? dL_dF[(size_t)(c0 + c) * N + pix] : 0.f;
+
+    const uint32_t wave_last = wave_max_u32(st.last);
+    if (lane == 0) s_wmax[w] = wave_last;
+    __syncthreads();
+    const uint32_t tile_last = max(max(s_wmax[0], s_wmax[1]), max(s_wmax[2], s_wmax[3]));
+
+    const bool alane = IS_ATOMIC_LANE(false, lane);
+    const uint32_t aoff = row_reduce_component<false>(lane);
+    const bool flane = lane < 16 && !(lane & 2);           // the eight lanes that own components 0..7
+    const uint32_t foff = aoff;
+
+    const int nb = ((int)tile_last + BATCH - 1) / BATCH;
+    for (int b = nb - 1; b >= 0; --b) {
+        __syncthreads();                              // previous batch fully consumed
+        const int base = b * BATCH;
+        const int n = min(BATCH, (int)tile_last - base);
+        if (tid < n) {
+            const uint32_t id = ids[range.x + base + tid];
+            const float4 r0 = rec[id].r0, r1 = rec[id].r1;
+            const float4 r2 = rec[id].r2;
+            s_r0[tid] = doubled_w(r0); s_id[tid] = id;
+            s_r1[tid] = make_float4(r1.x, r1.y, sign_test_bound(r1.y), __uint_as_float(quadrant_mask(r0, r1.x, r2.w, tx0, ty0)));
+            if constexpr (GEOM) stage_feature_row<CB>(s_f + tid * (CB / 4), features, id, C, c0, vec != 0);
+        }
+        __syncthreads();
+        int cnt = 0;
+#pragma unroll
+        for (int c = 0; c < BATCH / 64; ++c) {
+            const int e = c * 64 + lane;
+            const bool hit = e < n && (uint32_t)(base + e) < wave_last && ((__float_as_uint(s_r1[e].w) >> w) & 1u);
+            const uint64_t bal = __ballot(hit);
+            if (hit) s_list[w][cnt + __popcll(bal & lt_mask)] = (uint16_t)e;
+            cnt += __popcll(bal);
+        }
+        features_backward_walk<CB, GEOM>(s_list[w], cnt, base, s_r0, s_r1, s_id, s_f, pxf, pyf, st, G, alane, aoff,
+                                         grad_rec, flane, foff, acc);
+    }
+}
+
+// columns c0 .. c0 + CB - 1 (the real ones) of dL_dfeatures [P, C] from the accumulator block, which is cleared for the next one
+template <int CB>
+__global__ __launch_bounds__(256) void features_finish_kernel(int P, int C, int c0, double* __restrict__ acc,
+                                                              float* __restrict__ dL_dfeatures) {
+    const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= (size_t)P * CB) return;
+    const size_t i = k / CB;
+    const int c = c0 + (int)(k % CB);
+    if (c < C) dL_dfeatures[i * (size_t)C + c] = (float)acc[k];
+    acc[k] = 0.0;
+}
+
+// ---------------------------------------------------------------------------------------------
 // statistics for the algorithmic-bytes formula: D_trav = sum_tiles max_pixels n_contrib, V = #radii>0
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void tile_stats_kernel(ViewParams vp, const uint32_t* __restrict__ n_contrib,
@@ -1620,6 +1890,46 @@ hipError_t launch_contrib_finish(int P, const void* acc, float* weight_sum, floa
                        weight_max, (long long*)pixel_count);
     return hipGetLastError();
 }
+
+// msgs_features_forward / _backward: one launch per block of FEAT_CB channels (the four-waves-per-tile shape whatever the tile
+// count).  16-byte row loads where every row of the block starts on a 16-byte boundary.
+static bool feature_rows_vectorise(const float* features, int C) { return C % 4 == 0 && ((uintptr_t)features & 15) == 0; }
+
+hipError_t launch_blend_features_forward(const ViewParams& vp, const char* geom, const uint32_t* ids, const uint2* ranges,
+                                         const float* final_T, const uint32_t* n_contrib, const float* features, int C,
+                                         float* out, hipStream_t s) {
+    const int tiles = vp.gx * vp.gy;
+    if (tiles <= 0) return hipSuccess;
+    const GaussRec* rec = reinterpret_cast<const GaussRec*>(geom);
+    const int vec = feature_rows_vectorise(features, C);
+    for (int c0 = 0; c0 < C; c0 += FEAT_CB)
+        hipLaunchKernelGGL((blend_features_forward_kernel<FEAT_CB>), dim3(tiles), dim3(256), 0, s, vp, rec, ids, ranges, final_T,
+                           n_contrib, features, C, c0, vec, out);
+    return hipGetLastError();
+}
+
+// acc: [P, FEAT_CB] doubles, cleared here and again by every finish; grad_rec: NULL = no geometry share
+hipError_t launch_blend_features_backward(const ViewParams& vp, int P, const char* geom, const uint32_t* ids, const uint2* ranges,
+                                          const float* final_T, const uint32_t* n_contrib, const float* features, int C,
+                                          const float* dL_dF, grad_acc_t* grad_rec, double* acc, float* dL_dfeatures,
+                                          hipStream_t s) {
+    const int tiles = vp.gx * vp.gy;
+    if (tiles <= 0 || P <= 0) return hipSuccess;
+    const GaussRec* rec = reinterpret_cast<const GaussRec*>(geom);
+    const int vec = feature_rows_vectorise(features, C);
+    hipError_t e = launch_zero(acc, sizeof(double) * FEAT_CB * (size_t)P, s);
+    if (e != hipSuccess) return e;
+    const unsigned finish_blocks = (unsigned)(((size_t)P * FEAT_CB + 255) / 256);
+    for (int c0 = 0; c0 < C; c0 += FEAT_CB) {
+        with_bool(grad_rec != nullptr, [&](auto GEOM) {
+            hipLaunchKernelGGL((blend_features_backward_kernel<FEAT_CB, decltype(GEOM)::value>), dim3(tiles), dim3(256), 0, s, vp,
+                               rec, ids, ranges, final_T, n_contrib, features, C, c0, vec, dL_dF, grad_rec, acc);
+        });
+        hipLaunchKernelGGL((features_finish_kernel<FEAT_CB>), dim3(finish_blocks), dim3(256), 0, s, P, C, c0, acc, dL_dfeatures);
+    }
+    return hipGetLastError();
+}
+size_t features_scratch_bytes(int P) { return sizeof(double) * FEAT_CB * (size_t)(P > 0 ? P : 1); }
 
 // ---------------------------------------------------------------------------------------------
 // Deterministic backward (msgs_set_deterministic): no float atomics.  K7 stores the nine sums of every tile entry;

@@ -788,6 +788,16 @@ hipError_t launch_blend_contrib(const ViewParams& vp, const char* geom, const ui
                                 const float* final_T, const uint32_t* n_contrib, const float* pixel_weights, void* acc,
                                 hipStream_t s);
 hipError_t launch_contrib_finish(int P, const void* acc, float* weight_sum, float* weight_max, int64_t* pixel_count, hipStream_t s);
+// msgs_features_* (SPEC M12): features [P,C] splatted with the blend weights into out [C,H,W]; the backward adds the six
+// geometry sums of q_f into grad_rec (NULL = none) and writes dL_dfeatures [P,C] through acc (features_scratch_bytes(P))
+size_t features_scratch_bytes(int P);
+hipError_t launch_blend_features_forward(const ViewParams& vp, const char* geom, const uint32_t* ids, const uint2* ranges,
+                                         const float* final_T, const uint32_t* n_contrib, const float* features, int C,
+                                         float* out, hipStream_t s);
+hipError_t launch_blend_features_backward(const ViewParams& vp, int P, const char* geom, const uint32_t* ids, const uint2* ranges,
+                                          const float* final_T, const uint32_t* n_contrib, const float* features, int C,
+                                          const float* dL_dF, grad_acc_t* grad_rec, double* acc, float* dL_dfeatures,
+                                          hipStream_t s);
 // heaviest-first launch order of the one-wave-per-tile backward from the forward's per-tile traversal lengths
 hipError_t launch_tile_order(const ViewParams& vp, const uint32_t* tile_last, uint32_t* tile_order, hipStream_t s);
 hipError_t launch_blend_lane_stats(const ViewParams& vp, const char* geom, const uint32_t* ids, const uint2* ranges,

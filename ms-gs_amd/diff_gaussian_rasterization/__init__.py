@@ -330,6 +330,8 @@ def _note_camera(ctx, camera, behind=0):
 #   [bg]                               grad mode on and settings.bg requires grad: the background colour, for its gradient
 #   [_ALPHA]                           return_alpha=True: a marker (not a tensor) — the Function returns alpha as a sixth output
 #   [_AbsgradMarker]                   absgrad=True: a marker holding a weak reference to the caller's means2D
+#   [_FEATURES, features]              features given: a marker and the [P,C] tensor, always LAST — the marker tells the tensor
+#                                      from bg; the Function returns the feature map [C,H,W] as its last output
 # A call that asks for none of the new things passes exactly what it passed before them.
 class _AlphaMarker:
     def __repr__(self):
@@ -352,10 +354,45 @@ class _AbsgradMarker:
         return "absgrad"
 
 
-def _extra_inputs(rs, return_alpha=False, absgrad=False, means2D=None):
+# Feature channels (4.12).  `features` [P,C] is splatted with the blend weights of the colour render into one
+# more output [C,H,W], F[c,p] = sum_i f_ic alpha_ip T_ip over background 0 (msgs_features_forward: a replay of the blend walk
+# behind the forward).  A loss on the map sends gradients to the features and — as C more colour channels — to the geometry: the
+# backward first runs msgs_features_backward, which adds the features' geometry sums to the gradient records, then today's
+# backward with scratch_is_clear = 1 on top of them.  A loss that does not use the map takes today's backward unchanged.
+class _FeaturesMarker:
+    def __repr__(self):
+        return "features"
+
+
+_FEATURES = _FeaturesMarker()
+
+
+def _check_features(features, P, dev):
+    """the [P,C] feature tensor of a call, or None when none was given (None, or an empty tensor of a model with Gaussians);
+    every guard runs here, before any launch"""
+    if features is None or (features.numel() == 0 and not (P == 0 and features.dim() == 2 and features.shape[1] > 0)):
+        return None
+    if _C.lib.msgs_get_deterministic():
+        raise ValueError("features are not offered in the verification mode (set_deterministic): that mode checks the "
+                         "gradients of the reference's outputs")
+    _check_rows("features", features, P, None)
+    if features.dim() != 2:
+        raise ValueError(f"features must have shape [{P}, C], got {tuple(features.shape)}")
+    if features.device.type != "cuda" or features.device != dev:
+        raise RuntimeError("diff_gaussian_rasterization (MI355X build): features must live on the HIP device of the model "
+                           "('cuda'); there is no CPU path")
+    return features
+
+
+def _extra_inputs(rs, return_alpha=False, absgrad=False, means2D=None, features=None, model=None):
+    """model: the call's means3D / xyz (its rows and device check `features`)"""
     if absgrad and _C.lib.msgs_get_deterministic():
         raise ValueError("absgrad=True is not offered in the verification mode (set_deterministic): that mode checks the "
                          "gradients, it does not train")
+    if features is not None:
+        features = _check_features(features, int(model.shape[0]), model.device)
+    if features is not None:
+        return tuple(_extra_inputs(rs, return_alpha, absgrad, means2D)) + (_FEATURES, features)
     extra = _camera_inputs(rs)
     if torch.is_grad_enabled() and torch.is_tensor(rs.bg) and rs.bg.requires_grad:
         extra = tuple(extra) + (rs.bg,)
@@ -367,7 +404,14 @@ def _extra_inputs(rs, return_alpha=False, absgrad=False, means2D=None):
 def _note_extra(ctx, extra):
     """forward: split the trailing inputs; leaves ctx.camera (_note_camera), ctx.bg ((shape, dtype, device) when the
     background wants a gradient, else None), ctx.n_extra_tail (inputs behind the camera's), ctx.absgrad (the marker or None)
-    and returns return_alpha"""
+    ctx.features (the caller's tensor or None), ctx.feat (its contiguous float32 form) and returns return_alpha"""
+    ctx.features = ctx.feat = None
+    n_feat = 0
+    if len(extra) >= 2 and extra[-2] is _FEATURES:
+        ctx.features, n_feat = extra[-1], 2
+        ctx.feat = _f32c(extra[-1].detach())
+        ctx.features_want = bool(ctx.needs_input_grad[-1])
+        extra = extra[:-2]
     ctx.absgrad = extra[-1] if extra and isinstance(extra[-1], _AbsgradMarker) else None
     n_abs = int(ctx.absgrad is not None)
     rest = extra[:-1] if n_abs else extra
@@ -375,10 +419,10 @@ def _note_extra(ctx, extra):
     rest = rest[:-1] if alpha else rest
     bg = rest[-1] if len(rest) in (1, 4) else None
     camera = rest[:3] if len(rest) >= 3 else ()
-    ctx.n_extra_tail = len(extra) - len(camera)
+    ctx.n_extra_tail = len(extra) - len(camera) + n_feat
     ctx.has_bg = bg is not None
     ctx.bg = None
-    if bg is not None and ctx.needs_input_grad[len(ctx.needs_input_grad) - 1 - int(alpha) - n_abs]:
+    if bg is not None and ctx.needs_input_grad[len(ctx.needs_input_grad) - 1 - int(alpha) - n_abs - n_feat]:
         ctx.bg = (bg.shape, bg.dtype, bg.device)
     _note_camera(ctx, camera, ctx.n_extra_tail)
     ctx.return_alpha = alpha
@@ -416,9 +460,63 @@ def _bg_grad(ctx, view_ref, image, dL, W, H, dev, stream):
 
 
 def _extra_grads(ctx, g_cam, g_bg):
-    """gradients of the trailing inputs in their order: camera, bg, the alpha marker, the absgrad marker"""
+    """gradients of the trailing inputs in their order: camera, bg, the alpha marker, the absgrad marker, the features marker and
+    dL/dfeatures (in the tensor's shape and dtype; None when the loss did not use the feature map)"""
+    g_feat = ()
+    if ctx.features is not None:
+        g, ctx.g_features = getattr(ctx, "g_features", None), None
+        g_feat = (None, g.view(ctx.features.shape).to(ctx.features.dtype) if g is not None and ctx.features_want else None)
     return tuple(g_cam) + ((g_bg,) if ctx.has_bg else ()) + ((None,) if ctx.return_alpha else ()) + \
-        ((None,) if ctx.absgrad is not None else ())
+        ((None,) if ctx.absgrad is not None else ()) + g_feat
+
+
+def _split_grad_tail(ctx, tail):
+    """the gradients of the outputs behind the reference's five: (grad_alpha, grad_features)"""
+    return (tail[0] if ctx.return_alpha else None), (tail[-1] if ctx.features is not None else None)
+
+
+_features_probe = None             # tests: a callable (name) run in front of every msgs_features_* call
+
+
+def _features_forward(ctx, call, state):
+    """the feature map [C,H,W] of a call with features: msgs_features_forward on the current stream, behind the forward that
+    left `state`.  A deferred forward is resolved first (the replay needs the instance count): correct, at the price of that
+    view's overlap."""
+    geom, binning, image, D = _resolve(state)
+    dev, P, Cn = call.device, call.P, int(ctx.feat.shape[1])
+    if _features_probe is not None:
+        _features_probe("msgs_features_forward")
+    with _on_device(dev):
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        out = torch.empty(Cn, call.H, call.W, dtype=torch.float32, device=dev)
+        _C.check(_C.lib.msgs_features_forward(call.view_ref, P, _ptr(geom), geom.numel(), D, _ptr(binning),
+                                              binning.numel() if binning is not None else 0, _ptr(image), image.numel(),
+                                              _ptr(ctx.feat), Cn, _ptr(out), stream), "msgs_features_forward")
+    return out
+
+
+def _features_backward(ctx, call, geom, binning, image, D, grad_features, scratch, is_clear, dev, stream):
+    """In front of _run_backward, when the loss used the feature map: dL/dfeatures (left on ctx for _extra_grads) and, when a
+    geometry input wants a gradient, the features' geometry sums ADDED to the gradient records in `scratch` — cleared here
+    unless it is the buffer the forward cleared.  Returns the scratch_is_clear flag to hand on: 1 once the records hold sums
+    that msgs_backward* has to add to."""
+    lib = _C.lib
+    P, Cn = call.P, int(ctx.feat.shape[1])
+    G = _f32c(grad_features)
+    out = torch.empty(P, Cn, dtype=torch.float32, device=dev)
+    geom_share = bool(ctx.features_geom)
+    if geom_share and not is_clear:
+        scratch.zero_()
+    acc = _bytes(lib.msgs_features_scratch_bytes(P, Cn), dev)
+    if _features_probe is not None:
+        _features_probe("msgs_features_backward")
+    _C.check(lib.msgs_features_backward(call.view_ref, P, _ptr(geom), geom.numel(), D, _ptr(binning),
+                                        binning.numel() if binning is not None else 0, _ptr(image), image.numel(),
+                                        _ptr(ctx.feat), Cn, _ptr(G), _ptr(scratch) if geom_share else None,
+                                        scratch.numel() if geom_share else 0, _ptr(acc), acc.numel(), _ptr(out), stream),
+             "msgs_features_backward")
+    ctx.g_features = out
+    return 1 if geom_share else is_clear
 
 
 def _refuse_camera_with(camera):
@@ -857,10 +955,15 @@ def _forward_impl(call, grad_rec=None, backward_follows=False, want_alpha=False)
     return color, acc_ps, depth, radii, pixel_sizes, (geom, binning, image, D)
 
 
-def _forward_tail(ctx, call, state, outs):
-    """the end of every autograd forward: what its backward finds on ctx; returns the five outputs (six with return_alpha)"""
+def _forward_tail(ctx, call, state, outs, geometry=(0, 1, 4, 5, 6)):
+    """the end of every autograd forward: what its backward finds on ctx; returns the five outputs (six with return_alpha, and
+    the feature map behind them when features were given).  geometry: the positions of the inputs whose gradient the per-
+    Gaussian backward forms from the records' geometry slots (the camera's follow from ctx.camera)."""
     color, acc_ps, depth, radii, pixel_sizes = outs[:5]
     ctx.call, ctx.state, ctx.radii = call, state, radii
+    if ctx.features is not None:
+        ctx.features_geom = any(ctx.needs_input_grad[k] for k in geometry) or any(m is not None for m in ctx.camera)
+        outs = tuple(outs) + (_features_forward(ctx, call, state),)
     ctx.mark_non_differentiable(acc_ps, radii, pixel_sizes)     # depth and alpha are differentiable (DESIGN.md 2, M6, M9)
     ctx.set_materialize_grads(False)      # grad_depth / grad_alpha are None unless the loss used that map: then today's path
     return tuple(outs)
@@ -890,6 +993,8 @@ class _RasterizeGaussians(torch.autograd.Function):
             ctx.mark_non_differentiable(outs[1], *outs[3:])     # (depth stays differentiable: zero gradients)
             if want_alpha:                                      # (nothing blended: alpha 0, zero gradients)
                 outs = outs + (torch.zeros(H, W, device=dev),)
+            if ctx.features is not None:                        # (nothing blended: a zero map, zero gradients)
+                outs = outs + (torch.zeros(int(ctx.features.shape[1]), H, W, device=dev),)
             ctx.set_materialize_grads(False)
             return outs
         ctx.empty = False
@@ -899,10 +1004,11 @@ class _RasterizeGaussians(torch.autograd.Function):
         *outs, state = _forward_impl(call, _alloc_grad_records(ctx, call.P, call.device), ctx.backward_follows, want_alpha)
         ctx.shapes = (means2D.shape, opacities.shape)
         _save_inputs(ctx, means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp)
-        return _forward_tail(ctx, call, state, outs)
+        return _forward_tail(ctx, call, state, outs, geometry=(0, 1, 4, 5, 6, 7))
 
     @staticmethod
-    def backward(ctx, grad_color, grad_acc_ps, grad_depth, grad_radii, grad_pixel_sizes, grad_alpha=None):
+    def backward(ctx, grad_color, grad_acc_ps, grad_depth, grad_radii, grad_pixel_sizes, *grad_tail):
+        grad_alpha, grad_features = _split_grad_tail(ctx, grad_tail)
         if ctx.empty:
             cam = tuple(None if m is None else torch.zeros(m[0], dtype=m[1], device=m[2]) for m in ctx.camera)
             g_bg = None
@@ -917,6 +1023,8 @@ class _RasterizeGaussians(torch.autograd.Function):
             m2 = ctx.absgrad.means2D() if ctx.absgrad is not None else None
             if m2 is not None:              # no Gaussian: zeros [0, 3], no launch
                 m2.absgrad = torch.zeros(ctx.in_shapes[1], dtype=torch.float32, device=ctx.dev)
+            if grad_features is not None:
+                ctx.g_features = torch.zeros(ctx.features.shape, dtype=torch.float32, device=ctx.dev)
             return tuple(torch.zeros(s, device=ctx.dev) for s in ctx.in_shapes) + (None,) * 6 + _extra_grads(ctx, cam, g_bg)
         _check_saved(ctx)
         call = ctx.call
@@ -942,6 +1050,9 @@ class _RasterizeGaussians(torch.autograd.Function):
                              _ptr(g_scales), _ptr(g_rot), _ptr(g_cov), None, None, None, is_clear)
             cam = _CameraGrads(ctx, P, dev) if ctx.camera else None
             dLa = _f32c(grad_alpha) if grad_alpha is not None else None
+            if grad_features is not None:
+                grads.scratch_is_clear = _features_backward(ctx, call, geom, binning, image, D, grad_features, scratch, is_clear,
+                                                            dev, stream)
             _run_backward(lib, call, ctx, geom, binning, image, D, dL, dLd, dLa, scratch, grads, stream, cam)
             g_bg = _bg_grad(ctx, call.view_ref, image, dL, call.W, call.H, dev, stream) if ctx.bg is not None else None
             if ctx.absgrad is not None:
@@ -975,6 +1086,7 @@ def _save_inputs(ctx, *tensors):
     """Everything the backward re-reads goes through save_for_backward, so that an in-place edit between forward and
     backward (optimizer step, reset_opacity-style edit) raises autograd's version-counter error instead of yielding
     silently wrong gradients.  (The ctypes structs on ctx.call point at the same storage.)"""
+    tensors = tensors + (getattr(ctx, "features", None),)
     ctx.save_for_backward(*[t for t in tensors if torch.is_tensor(t) and t.numel() > 0])
 
 
@@ -1153,7 +1265,8 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
         return _forward_tail(ctx, call, state, outs)
 
     @staticmethod
-    def backward(ctx, grad_color, grad_acc_ps, grad_depth, grad_radii, grad_pixel_sizes, grad_alpha=None):
+    def backward(ctx, grad_color, grad_acc_ps, grad_depth, grad_radii, grad_pixel_sizes, *grad_tail):
+        grad_alpha, grad_features = _split_grad_tail(ctx, grad_tail)
         _check_saved(ctx)
         call = ctx.call
         if grad_color is None:
@@ -1202,6 +1315,9 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
                              is_clear, acc_flag, ev_wait, ev_rec, C.addressof(adam) if adam is not None else None)
             cam = _CameraGrads(ctx, P, dev) if ctx.camera else None
             dLa = _f32c(grad_alpha) if grad_alpha is not None else None
+            if grad_features is not None:
+                grads.scratch_is_clear = _features_backward(ctx, call, geom, binning, image, D, grad_features, scratch, is_clear,
+                                                            dev, stream)
             _run_backward(lib, call, ctx, geom, binning, image, D, dL, dLd, dLa, scratch, grads, stream, cam)
             if adam is not None:
                 step_opt.commit_step_in_backward(ctx.leaves)
@@ -1238,9 +1354,9 @@ class _RasterizeGaussiansChained(torch.autograd.Function):
         return _forward_tail(ctx, call, state, outs)
 
     @staticmethod
-    def backward(ctx, grad_color, grad_acc_ps, grad_depth, grad_radii, grad_pixel_sizes, grad_alpha=None):
-        g = _RasterizeGaussiansRaw.backward(ctx, grad_color, grad_acc_ps, grad_depth, grad_radii, grad_pixel_sizes, grad_alpha)
-        return g[:7] + (None,) * 10 + g[13:]            # (the trailing inputs' gradients — camera, bg, alpha marker — at the end)
+    def backward(ctx, grad_color, grad_acc_ps, grad_depth, grad_radii, grad_pixel_sizes, *grad_tail):
+        g = _RasterizeGaussiansRaw.backward(ctx, grad_color, grad_acc_ps, grad_depth, grad_radii, grad_pixel_sizes, *grad_tail)
+        return g[:7] + (None,) * 10 + g[13:]            # (the trailing inputs' gradients — camera, bg, markers, features — at the end)
 
 
 # Recognition of the reference's getters (scene/gaussian_model.py:127-153) in the autograd graph of the arguments of
@@ -1328,26 +1444,32 @@ def sh_grad_from_views(means3D, gathered, n_views, sh_degree, scale, out_dc, out
 
 def rasterize_gaussians_raw(xyz, means2D, features_dc, features_rest, opacity_raw, scaling_raw, rotation_raw,
                             max_pixel_sizes, min_pixel_sizes, occ_multiplier, dc_delta, base_mask, raster_settings,
-                            absgrad=False, return_alpha=False):
+                            features=None, absgrad=False, return_alpha=False):
     """return_alpha=True: a sixth output, the alpha map [H,W] (1 - final transmittance), differentiable
-    absgrad=True: every backward also assigns means2D.absgrad.  Pass both flags by keyword."""
+    absgrad=True: every backward also assigns means2D.absgrad.
+    features [P,C]: one more output at the END, the feature map [C,H,W], differentiable.  All three by
+    keyword."""
+    extra = _extra_inputs(raster_settings, return_alpha, absgrad, means2D, features, xyz)
     _note_grad_mode()
     return _RasterizeGaussiansRaw.apply(xyz, means2D, features_dc, features_rest, opacity_raw, scaling_raw,
                                         rotation_raw, max_pixel_sizes, min_pixel_sizes, occ_multiplier, dc_delta,
                                         base_mask, raster_settings,
-                                        *_extra_inputs(raster_settings, return_alpha, absgrad, means2D))
+                                        *extra)
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                         max_pixel_sizes, min_pixel_sizes, occ_multiplier, dc_delta, base_mask, raster_settings,
-                        absgrad=False, return_alpha=False):
+                        features=None, absgrad=False, return_alpha=False):
     """return_alpha=True: a sixth output, the alpha map [H,W] (1 - final transmittance), differentiable
-    absgrad=True: every backward also assigns means2D.absgrad.  Pass both flags by keyword."""
+    absgrad=True: every backward also assigns means2D.absgrad.
+    features [P,C]: one more output at the END, the feature map [C,H,W], differentiable.  All three by
+    keyword."""
+    extra = _extra_inputs(raster_settings, return_alpha, absgrad, means2D, features, means3D)
     _note_grad_mode()
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
                                      cov3Ds_precomp, max_pixel_sizes, min_pixel_sizes, occ_multiplier, dc_delta,
                                      base_mask, raster_settings,
-                                     *_extra_inputs(raster_settings, return_alpha, absgrad, means2D))
+                                     *extra)
 
 
 # Contribution scores (DESIGN.md 2, M11; 4.11): what every Gaussian did to the images of one or many views, the criterion of
@@ -1442,6 +1564,22 @@ class GaussianRasterizer(nn.Module):
         self.raster_settings = raster_settings
         self.return_alpha = bool(return_alpha)
         self.absgrad = bool(absgrad)
+        self.features = None
+
+    def with_features(self, features):
+        """A rasterizer like this one whose forward / forward_raw also splat `features` [P,C] (float32 device tensor, C >= 1;
+        None or an empty tensor: none): per-Gaussian vectors — embeddings, logits, normals — blended with the weights of this
+        render.  The feature map [C,H,W] float32, F[c,p] = sum_i f_ic alpha_ip T_ip, becomes one more output at the END of
+        the tuple (behind alpha when both are asked for).  No background term: a pixel nothing was blended into is 0; compose
+        a background outside with the alpha map.  Differentiable: a loss on the map sends gradients to `features` and, the
+        features acting as C more colour channels, to means, opacity, scales / rotations / cov3D and the camera; SH and colours
+        receive nothing from it.  Rows of Gaussians in no tile list are never read.  Inside
+        deferred_forward a call with features resolves its own view before the replay: correct, but that view's overlap is
+        lost.  Not offered in the verification mode (set_deterministic): ValueError before any launch.
+        (forward() keeps the reference's 13 parameters, so the tensor travels on the module.)"""
+        r = GaussianRasterizer(self.raster_settings, self.return_alpha, self.absgrad)
+        r.features = features
+        return r
 
     def markVisible(self, positions):
         """Boolean mask of points in front of the near plane (upstream markVisible; unused by the
@@ -1531,19 +1669,23 @@ class GaussianRasterizer(nn.Module):
             return None if into is not None else acc.scores()
 
     def forward_raw(self, xyz, means2D, features_dc, features_rest, opacity_raw, scaling_raw, rotation_raw,
-                    max_pixel_sizes=None, min_pixel_sizes=None, occ_multiplier=None, dc_delta=None, base_mask=None):
-        """Opt-in fused path on raw GaussianModel parameters (not part of the reference API)."""
+                    max_pixel_sizes=None, min_pixel_sizes=None, occ_multiplier=None, dc_delta=None, base_mask=None, features=None):
+        """Opt-in fused path on raw GaussianModel parameters (not part of the reference API).  features [P,C]: as in
+        with_features(); None: the module's own (with_features), if any."""
+        features = features if features is not None else self.features
         empty = torch.Tensor([])
         o = lambda t: t if t is not None else empty
         return rasterize_gaussians_raw(xyz, means2D, features_dc, features_rest, opacity_raw, scaling_raw,
                                        rotation_raw, o(max_pixel_sizes), o(min_pixel_sizes), o(occ_multiplier),
                                        o(dc_delta), o(base_mask), self.raster_settings, absgrad=self.absgrad,
-                                       return_alpha=self.return_alpha)
+                                       return_alpha=self.return_alpha, features=features)
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
                 cov3D_precomp=None, max_pixel_sizes=None, min_pixel_sizes=None, occ_multiplier=None,
                 dc_delta=None, base_mask=None):
+        """The reference's 13 parameters.  Feature channels travel on the module: with_features(features)(...)."""
         rs = self.raster_settings
+        features = self.features
         if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
             raise Exception('Please provide excatly one of either SHs or precomputed colors!')
         if ((scales is None or rotations is None) and cov3D_precomp is None) or \
@@ -1569,7 +1711,7 @@ class GaussianRasterizer(nn.Module):
                     means3D, means2D, *leaves, shs.detach() if _chain_reads_cat else empty, opacities.detach(), scales.detach(),
                     rotations.detach(),
                     o(max_pixel_sizes), o(min_pixel_sizes), o(occ_multiplier), o(dc_delta), o(base_mask), rs,
-                    *_extra_inputs(rs, self.return_alpha, self.absgrad, means2D))
+                    *_extra_inputs(rs, self.return_alpha, self.absgrad, means2D, features, means3D))
         return rasterize_gaussians(
             means3D, means2D,
             shs if shs is not None else empty,
@@ -1583,4 +1725,4 @@ class GaussianRasterizer(nn.Module):
             occ_multiplier if occ_multiplier is not None else empty,
             dc_delta if dc_delta is not None else empty,
             base_mask if base_mask is not None else empty,
-            rs, absgrad=self.absgrad, return_alpha=self.return_alpha)
+            rs, absgrad=self.absgrad, return_alpha=self.return_alpha, features=features)

@@ -203,6 +203,13 @@ def _load():
     lib.msgs_contrib_accumulate.argtypes = [C.POINTER(View), C.c_int32, vp, sz, C.c_int64, vp, sz, vp, sz, vp, vp, sz, C.c_int32, vp]
     lib.msgs_contrib_finish.restype = C.c_int
     lib.msgs_contrib_finish.argtypes = [C.c_int32, vp, sz, vp, vp, vp, vp]
+    lib.msgs_features_scratch_bytes.restype = sz
+    lib.msgs_features_scratch_bytes.argtypes = [C.c_int32, C.c_int32]
+    lib.msgs_features_forward.restype = C.c_int
+    lib.msgs_features_forward.argtypes = [C.POINTER(View), C.c_int32, vp, sz, C.c_int64, vp, sz, vp, sz, vp, C.c_int32, vp, vp]
+    lib.msgs_features_backward.restype = C.c_int
+    lib.msgs_features_backward.argtypes = [C.POINTER(View), C.c_int32, vp, sz, C.c_int64, vp, sz, vp, sz, vp, C.c_int32, vp,
+                                           vp, sz, vp, sz, vp, vp]
     lib.msgs_backward_per_gaussian.restype = C.c_int
     lib.msgs_backward_per_gaussian.argtypes = [C.POINTER(View), C.POINTER(Gaussians), vp, vp, sz, vp, C.POINTER(Grads), vp]
     lib.msgs_sh_grad_from_views.restype = C.c_int
@@ -276,7 +283,8 @@ EXPORTS = ("msgs_abi_version", "msgs_error_string", "msgs_geom_bytes", "msgs_sta
            "msgs_densify_scratch_bytes", "msgs_densify_select", "msgs_densify_apply",
            "msgs_alpha_map", "msgs_backward_with_alpha", "msgs_bg_grad_scratch_bytes", "msgs_bg_grad",
            "msgs_absgrad_scratch_bytes", "msgs_absgrad",
-           "msgs_contrib_scratch_bytes", "msgs_contrib_accumulate", "msgs_contrib_finish")
+           "msgs_contrib_scratch_bytes", "msgs_contrib_accumulate", "msgs_contrib_finish",
+           "msgs_features_scratch_bytes", "msgs_features_forward", "msgs_features_backward")
 
 
 def check(rc, where):

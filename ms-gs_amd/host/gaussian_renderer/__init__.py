@@ -200,3 +200,48 @@ def render_with_absgrad(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scal
     if alpha:
         out["alpha"] = outs[5]
     return out
+
+
+def render_with_features(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, features, scaling_modifier=1.0,
+                         override_color=None, filter_small=False, filter_large=False, fade_size=1.0, fused=False):
+    """render() — or, with fused=True, render_fused() (then without override_color) — plus per-Gaussian feature channels
+    splatted with the same blend weights: the seven keys of RESULT_KEYS and "features" [C,H,W] float32 for `features` [P,C]
+    (embeddings, segmentation logits, normals, distilled 2-D features ...), F[c,p] = sum_i f_ic alpha_ip T_ip.  The map has
+    NO background term — compose one outside with the alpha map — and is differentiable: a loss on it reaches `features` and,
+    as C more colour channels, the geometry and the camera, not SH / colours.  One forward and one
+    backward whatever C is, where override_color needs ceil(C / 3) of each.  Image, maps and their gradients are those of
+    the call without features, bit for bit."""
+    settings = _settings(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, filter_small, filter_large, fade_size)
+    rasterizer = GaussianRasterizer(raster_settings=settings).with_features(features)
+    if fused:
+        if override_color is not None:
+            raise ValueError("render_with_features: fused=True cannot be combined with override_color")
+        xyz = pc._xyz
+        viewspace = torch.empty_like(xyz, requires_grad=True)
+        outs = rasterizer.forward_raw(
+            xyz, viewspace, pc._features_dc, pc._features_rest, pc._opacity, pc._scaling, pc._rotation,
+            max_pixel_sizes=pc.get_max_pixel_sizes, min_pixel_sizes=pc.get_min_pixel_sizes,
+            occ_multiplier=pc.get_occ_multiplier, dc_delta=pc.get_dc_delta, base_mask=pc.get_base_mask)
+    else:
+        xyz = pc.get_xyz
+        viewspace = torch.zeros_like(xyz, requires_grad=True) + 0
+        try:
+            viewspace.retain_grad()
+        except Exception:
+            pass
+        outs = rasterizer(
+            means3D=xyz,
+            means2D=viewspace,
+            opacities=pc.get_opacity,
+            max_pixel_sizes=pc.get_max_pixel_sizes,
+            min_pixel_sizes=pc.get_min_pixel_sizes,
+            occ_multiplier=pc.get_occ_multiplier,
+            dc_delta=pc.get_dc_delta,
+            base_mask=pc.get_base_mask,
+            **_colour_inputs(viewpoint_camera, pc, pipe, override_color),
+            **_shape_inputs(pc, pipe, scaling_modifier))
+    image, acc_pixel_size, depth, radii, pixel_sizes = outs[:5]
+    values = (image, acc_pixel_size, depth, viewspace, radii > 0, radii, pixel_sizes)
+    out = dict(zip(RESULT_KEYS, values))
+    out["features"] = outs[5] if len(outs) > 5 else None
+    return out
