@@ -444,6 +444,38 @@ int msgs_features_backward(const msgs_view_t* view, int32_t P,
                            void* scratch, size_t scratch_bytes,
                            float* dL_dfeatures, void* stream);
 
+/* ---- depth distortion: the spread of a ray's blended mass along the view axis (DESIGN.md SPEC M13, 4.13) ------ */
+/* With w_ip = alpha_ip T_ip and z_i the view depth the depth map blends, over exactly the pairs msgs_backward* counts, in
+ * tile-list order i = 1..n (front to back):
+ *     msgs_distortion_forward:   out_distortion [H,W] float32,  Dist_p = 2 sum_{j<i} w_ip w_jp (z_i - z_j)
+ * the signed list-order form of the Mip-NeRF 360 distortion sum_i sum_j w_i w_j |z_i - z_j| (equal to it on a depth-sorted
+ * list, and without a kink at ties).  No background term; exactly 0.0f for a pixel with fewer than two counted pairs.
+ * out_moment [H,W] float32: sum_i w_ip (z_i - z_ref) with z_ref the view depth of the tile's first list entry — meaningful
+ * to msgs_distortion_backward of the same view only, which takes it as `moment`.
+ *     msgs_distortion_backward:  dL_ddistortion [H,W] float32 = G.  G dDist/dw_i acts as the only colour channel of pair i over
+ * background 0: the six sums of its q (sum q dx, q dy, q dx^2, q dx dy, q dy^2, q) are ADDED to record slots 0..5 of
+ * grad_records (>= msgs_backward_scratch_bytes(P), the buffer handed to msgs_backward* as `scratch`) and sum_p G dDist/dz_i to
+ * slot 9.  The records must already be zero (cleared by the forward of this view, or by the caller) or hold sums that are to
+ * be included; msgs_backward* is then called with msgs_grads_t.scratch_is_clear = 1 and a non-NULL dL_ddepth (a zero map when
+ * the loss has no depth term), so that the depth variant of its per-Gaussian stage consumes slot 9: means, opacity, scales /
+ * rotations / cov3D and the camera receive the distortion's share, SH and colours nothing.
+ * Both read what the forward of this view left in geom / binning / image_state (single pass, speculative stage 2 or its redo,
+ * depth slabs, occlusion cut-off alike).  P == 0 or num_instances == 0: the forward zero-fills both maps, the backward launches
+ * nothing.  Not offered in the verification mode (MSGS_ERR_INVALID_ARG). */
+int msgs_distortion_forward(const msgs_view_t* view, int32_t P,
+                            const void* geom, size_t geom_bytes,
+                            int64_t num_instances,
+                            const void* binning, size_t binning_bytes,
+                            const void* image_state, size_t image_bytes,
+                            float* out_distortion, float* out_moment, void* stream);
+int msgs_distortion_backward(const msgs_view_t* view, int32_t P,
+                             const void* geom, size_t geom_bytes,
+                             int64_t num_instances,
+                             const void* binning, size_t binning_bytes,
+                             const void* image_state, size_t image_bytes,
+                             const float* moment, const float* dL_ddistortion,
+                             void* grad_records, size_t grad_records_bytes, void* stream);
+
 /* msgs_backward_per_gaussian: the per-Gaussian half of msgs_backward ALONE (2-D covariance backward, projection, SH,
  * scale / quaternion chain — upstream's computeCov2DCUDA + preprocessCUDA backward, SURVEY 2.2 K8 + K9) on per-Gaussian
  * 2-D gradients supplied by the caller instead of the blend backward's sums: sums2d [P,9] DOUBLES (device) =

@@ -926,6 +926,59 @@ int msgs_features_backward(const msgs_view_t* view, int32_t P, const void* geom_
                                            (grad_acc_t*)grad_records, (double*)scratch, dL_dfeatures, s));
     return debug_sync(view, s);
 }
+
+int msgs_distortion_forward(const msgs_view_t* view, int32_t P, const void* geom_v, size_t geom_bytes, int64_t D,
+                            const void* binning_v, size_t binning_bytes, const void* image_v, size_t image_bytes,
+                            float* out_distortion, float* out_moment, void* stream) {
+    if (!view || P < 0 || D < 0 || view->image_width < 1 || view->image_height < 1 || !out_distortion || !out_moment)
+        return MSGS_ERR_INVALID_ARG;
+    if (g_deterministic.load() != 0) return MSGS_ERR_INVALID_ARG;            // not offered in the verification mode
+    const int W = view->image_width, H = view->image_height;
+    hipStream_t s = (hipStream_t)stream;
+    if (P == 0 || D == 0) {                                                  // no instance: no pair, every pixel is 0
+        HIP_TRY(launch_zero(out_distortion, sizeof(float) * (size_t)W * H, s));
+        HIP_TRY(launch_zero(out_moment, sizeof(float) * (size_t)W * H, s));
+        return debug_sync(view, s);
+    }
+    if (!geom_v || !binning_v || !image_v) return MSGS_ERR_INVALID_ARG;
+    if (geom_bytes < msgs_geom_bytes(P) || binning_bytes < msgs_binning_bytes(D, W, H) || image_bytes < msgs_image_bytes(W, H))
+        return MSGS_ERR_CAPACITY;
+    const ViewParams vp = make_view_params(view);
+    const BinningLayout BL(D, vp.gx * vp.gy);
+    const ImageLayout IL(W, H);
+    const char* binning = (const char*)binning_v;
+    const char* image = (const char*)image_v;
+    HIP_TRY(launch_blend_distortion_forward(vp, (const char*)geom_v, (const uint32_t*)(binning + BL.ids),
+                                            (const uint2*)(binning + BL.ranges), (const float*)(image + IL.final_T),
+                                            (const uint32_t*)(image + IL.n_contrib), out_distortion, out_moment, s));
+    return debug_sync(view, s);
+}
+
+int msgs_distortion_backward(const msgs_view_t* view, int32_t P, const void* geom_v, size_t geom_bytes, int64_t D,
+                             const void* binning_v, size_t binning_bytes, const void* image_v, size_t image_bytes,
+                             const float* moment, const float* dL_ddistortion, void* grad_records, size_t grad_records_bytes,
+                             void* stream) {
+    if (!view || P < 0 || D < 0 || view->image_width < 1 || view->image_height < 1) return MSGS_ERR_INVALID_ARG;
+    if (g_deterministic.load() != 0) return MSGS_ERR_INVALID_ARG;            // its scratch holds another layout
+    if (P == 0 || D == 0) return MSGS_OK;                                    // no pair: nothing for the records
+    if (!geom_v || !binning_v || !image_v || !moment || !dL_ddistortion || !grad_records || ((uintptr_t)grad_records & 7))
+        return MSGS_ERR_INVALID_ARG;
+    const int W = view->image_width, H = view->image_height;
+    if (geom_bytes < msgs_geom_bytes(P) || binning_bytes < msgs_binning_bytes(D, W, H) || image_bytes < msgs_image_bytes(W, H) ||
+        grad_records_bytes < msgs_backward_scratch_bytes(P))
+        return MSGS_ERR_CAPACITY;
+    hipStream_t s = (hipStream_t)stream;
+    const ViewParams vp = make_view_params(view);
+    const BinningLayout BL(D, vp.gx * vp.gy);
+    const ImageLayout IL(W, H);
+    const char* binning = (const char*)binning_v;
+    const char* image = (const char*)image_v;
+    HIP_TRY(launch_blend_distortion_backward(vp, (const char*)geom_v, (const uint32_t*)(binning + BL.ids),
+                                             (const uint2*)(binning + BL.ranges), (const float*)(image + IL.final_T),
+                                             (const uint32_t*)(image + IL.n_contrib), moment, dL_ddistortion,
+                                             (grad_acc_t*)grad_records, s));
+    return debug_sync(view, s);
+}
 }  // extern "C"
 
 namespace {

@@ -1608,6 +1608,208 @@ __global__ __launch_bounds__(256) void features_finish_kernel(int P, int C, int 
 }
 
 // ---------------------------------------------------------------------------------------------
+// Depth distortion (DESIGN.md SPEC M13, 4.13; msgs_distortion_forward / msgs_distortion_backward): the Mip-NeRF 360 distortion
+// of a ray's blended mass, in the signed list-order form, over exactly the pairs the backward counts (i = 1..n front to back,
+// w_i = alpha_i T_i, z_i the view depth the depth map blends):
+//     Dist = 2 sum_{j<i} w_i w_j (z_i - z_j) = 2 sum_i w_i (R_i - z_i (T_{i+1} - T_f)),     R_i = sum_{k>i} w_k z_k
+// Quadratic in the weights, so it exists only inside the walk: two more replays of blend_backward_kernel's back-to-front walk
+// (staging and quadrant lists of blend_features_*, plus s_z).  Back to front the suffix moment R_i and the suffix weight
+// T_{i+1} - T_f are what the walk has in hand; the backward needs the prefix too and takes it from M = sum_i w_i z_i, which the
+// forward stores:  sum_{j<i} w_j z_j = M - R_i - w_i z_i,  sum_{j<i} w_j = 1 - T_i.  With B_i = 1 + T_f - T_i - T_{i+1}
+//     dDist/dw_i = 2 (z_i B_i - (M - R_i - w_i z_i) + R_i)          dDist/dz_i = 2 w_i B_i
+// G dDist/dw_i enters the S recurrence as the pair's only colour (S starts at 0: no background term), exactly as e does in
+// features_backward_walk; the six sums of q go to record slots 0..5 and sum G dDist/dz_i to slot 9 through reduce_and_add<true>.
+// Every z is taken relative to z_ref, the view depth of the tile's first list entry: Dist and both derivatives depend on depth
+// differences only, and in float32 the moments of a scene far from the camera would otherwise cancel.
+// R accumulates by the same fmaf of the same operands in both kernels, so M - R_i - w_i z_i closes on zero at the front entry.
+// Opt-in: nothing of the default path calls or shares a kernel with them.
+// ---------------------------------------------------------------------------------------------
+// The T recurrence of pair_grad alone (the same operations: w has the bits of PairGrad::dch); a masked lane gets w = 0, T unchanged.
+struct DistStep { float a_m, alpha_m, Tn, w; };
+__device__ __forceinline__ DistStep dist_step(float& T, const PairAlpha& a, uint64_t validm) {
+    const bool valid = __builtin_amdgcn_inverse_ballot_w64(validm);
+    DistStep d;
+    d.a_m = valid ? a.a_raw : 0.0f;
+    d.alpha_m = fminf(0.99f, d.a_m);
+    const float inv = __builtin_amdgcn_rcpf(1.0f - d.alpha_m);
+    d.Tn = T * inv;
+    T = d.Tn;
+    d.w = d.alpha_m * d.Tn;
+    return d;
+}
+// R += w z~: ONE expression for both kernels (explicit fmaf: no contraction choice left to the compiler)
+__device__ __forceinline__ float dist_moment_add(float R, float w, float zt) { return fmaf(w, zt, R); }
+
+// Staging and quadrant lists shared by the two kernels.  s_r1: {C', p0', sign_test_bound, quadrant mask bits} as in the feature
+// kernels.  Returns the number of entries in this wave's list.
+template <bool IDS>
+__device__ __forceinline__ int dist_stage_and_list(const GaussRec* __restrict__ rec, const uint32_t* __restrict__ ids, uint32_t first,
+                                                   int base, int n, int tid, int w, int lane, uint32_t wave_last, uint64_t lt_mask,
+                                                   float tx0, float ty0, float4* s_r0, float4* s_r1, float* s_z, uint32_t* s_id,
+                                                   uint16_t* s_listw) {
+    if (tid < n) {
+        const uint32_t id = ids[first + base + tid];
+        const float4 r0 = rec[id].r0, r1 = rec[id].r1;
+        const float4 r2 = rec[id].r2;
+        s_r0[tid] = doubled_w(r0);
+        s_r1[tid] = make_float4(r1.x, r1.y, sign_test_bound(r1.y), __uint_as_float(quadrant_mask(r0, r1.x, r2.w, tx0, ty0)));
+        s_z[tid] = r2.y;
+        if constexpr (IDS) s_id[tid] = id;
+    }
+    __syncthreads();
+    int cnt = 0;
+#pragma unroll
+    for (int c = 0; c < BATCH / 64; ++c) {
+        const int e = c * 64 + lane;
+        const bool hit = e < n && (uint32_t)(base + e) < wave_last && ((__float_as_uint(s_r1[e].w) >> w) & 1u);
+        const uint64_t bal = __ballot(hit);
+        if (hit) s_listw[cnt + __popcll(bal & lt_mask)] = (uint16_t)e;
+        cnt += __popcll(bal);
+    }
+    return cnt;
+}
+
+// out_distortion [H,W] = Dist, out_moment [H,W] = M = sum_i w_i (z_i - z_ref): plain stores for the inside pixels; a pixel with
+// fewer than two counted pairs stores Dist = 0.  One 256-thread workgroup per tile, one 8x8 quadrant per wave.
+__global__ __launch_bounds__(256) void blend_distortion_forward_kernel(ViewParams vp, const GaussRec* __restrict__ rec,
+                                                                       const uint32_t* __restrict__ ids,
+                                                                       const uint2* __restrict__ ranges,
+                                                                       const float* __restrict__ final_T,
+                                                                       const uint32_t* __restrict__ n_contrib,
+                                                                       float* __restrict__ out_distortion,
+                                                                       float* __restrict__ out_moment) {
+    __shared__ float4 s_r0[BATCH], s_r1[BATCH];
+    __shared__ float s_z[BATCH];
+    __shared__ uint16_t s_list[4][BATCH];
+    __shared__ uint32_t s_wmax[4];
+
+    const int num_tiles = vp.gx * vp.gy;
+    const int tile = swizzled_tile(blockIdx.x, num_tiles);
+    const int tx = tile % vp.gx, ty = tile / vp.gx;
+    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
+    const int px = tx * TILE + (w & 1) * 8 + (lane & 7);
+    const int py = ty * TILE + (w >> 1) * 8 + (lane >> 3);
+    const bool inside = px < vp.W && py < vp.H;
+    const float pxf = (float)px, pyf = (float)py;
+    const float tx0 = (float)(tx * TILE), ty0 = (float)(ty * TILE);
+    const uint2 range = ranges[tile];
+    const uint64_t lt_mask = (1ull << lane) - 1ull;
+    const size_t pix = (size_t)py * vp.W + px;
+
+    const float Tf = inside ? final_T[pix] : 1.0f;
+    const uint32_t last = inside ? n_contrib[pix] : 0u;
+    float T = Tf, R = 0.f, acc = 0.f;
+
+    const uint32_t wave_last = wave_max_u32(last);
+    if (lane == 0) s_wmax[w] = wave_last;
+    __syncthreads();
+    const uint32_t tile_last = max(max(s_wmax[0], s_wmax[1]), max(s_wmax[2], s_wmax[3]));
+    const float zref = tile_last > 0u ? rec[ids[range.x]].r2.y : 0.f;      // (a tile that blended has a first entry)
+
+    const int nb = ((int)tile_last + BATCH - 1) / BATCH;
+    for (int b = nb - 1; b >= 0; --b) {
+        __syncthreads();                              // previous batch fully consumed
+        const int base = b * BATCH;
+        const int n = min(BATCH, (int)tile_last - base);
+        const int cnt = dist_stage_and_list<false>(rec, ids, range.x, base, n, tid, w, lane, wave_last, lt_mask, tx0, ty0, s_r0,
+                                                   s_r1, s_z, nullptr, s_list[w]);
+        const uint16_t* lp = s_list[w];
+        for (int j = cnt - 1; j >= 0; --j) {
+            const int e = lp[j];
+            const float4 r0 = s_r0[e], r1 = s_r1[e];
+            const float dx = r0.x - pxf, dy = r0.y - pyf;
+            const PairAlpha a = pair_alpha(r0, r1, dx, dy);
+            const uint64_t validm = pair_valid(a, (uint32_t)(base + e), last, r1.z);
+            if (validm == 0) continue;
+            const float Tp = T;                                           // T_{i+1}
+            const DistStep d = dist_step(T, a, validm);
+            const float zt = s_z[e] - zref;
+            acc = fmaf(d.w, fmaf(-zt, Tp - Tf, R), acc);                  // w_i (R_i - z_i (T_{i+1} - T_f)); w = 0 on the masked lanes
+            R = dist_moment_add(R, d.w, zt);
+        }
+    }
+    if (inside) { out_distortion[pix] = 2.0f * acc; out_moment[pix] = R; }
+}
+
+// dL_ddist [H,W] = G, moment [H,W] = the forward's out_moment.  ADDS the six sums of q to record slots 0..5 and
+// sum_p G dDist/dz_i to slot 9 (zeros to 6..8): one atomic instruction per (quadrant, entry), every lane at its own slot.
+__global__ __launch_bounds__(256) void blend_distortion_backward_kernel(ViewParams vp, const GaussRec* __restrict__ rec,
+                                                                        const uint32_t* __restrict__ ids,
+                                                                        const uint2* __restrict__ ranges,
+                                                                        const float* __restrict__ final_T,
+                                                                        const uint32_t* __restrict__ n_contrib,
+                                                                        const float* __restrict__ moment,
+                                                                        const float* __restrict__ dL_ddist,
+                                                                        grad_acc_t* __restrict__ grad_rec) {
+    __shared__ float4 s_r0[BATCH], s_r1[BATCH];
+    __shared__ float s_z[BATCH];
+    __shared__ uint32_t s_id[BATCH];
+    __shared__ uint16_t s_list[4][BATCH];
+    __shared__ uint32_t s_wmax[4];
+
+    const int num_tiles = vp.gx * vp.gy;
+    const int tile = swizzled_tile(blockIdx.x, num_tiles);
+    const int tx = tile % vp.gx, ty = tile / vp.gx;
+    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
+    const int px = tx * TILE + (w & 1) * 8 + (lane & 7);
+    const int py = ty * TILE + (w >> 1) * 8 + (lane >> 3);
+    const bool inside = px < vp.W && py < vp.H;
+    const float pxf = (float)px, pyf = (float)py;
+    const float tx0 = (float)(tx * TILE), ty0 = (float)(ty * TILE);
+    const uint2 range = ranges[tile];
+    const uint64_t lt_mask = (1ull << lane) - 1ull;
+    const size_t pix = (size_t)py * vp.W + px;
+
+    const float Tf = inside ? final_T[pix] : 1.0f;
+    const uint32_t last = inside ? n_contrib[pix] : 0u;
+    const float G2 = inside ? 2.0f * dL_ddist[pix] : 0.f;
+    const float M = inside ? moment[pix] : 0.f;
+    const float oneTf = 1.0f + Tf;
+    float T = Tf, R = 0.f, S = 0.f;
+
+    const uint32_t wave_last = wave_max_u32(last);
+    if (lane == 0) s_wmax[w] = wave_last;
+    __syncthreads();
+    const uint32_t tile_last = max(max(s_wmax[0], s_wmax[1]), max(s_wmax[2], s_wmax[3]));
+    const float zref = tile_last > 0u ? rec[ids[range.x]].r2.y : 0.f;      // the forward's
+
+    const bool alane = IS_ATOMIC_LANE(true, lane);
+    const uint32_t aoff = row_reduce_component<true>(lane);
+
+    const int nb = ((int)tile_last + BATCH - 1) / BATCH;
+    for (int b = nb - 1; b >= 0; --b) {
+        __syncthreads();                              // previous batch fully consumed
+        const int base = b * BATCH;
+        const int n = min(BATCH, (int)tile_last - base);
+        const int cnt = dist_stage_and_list<true>(rec, ids, range.x, base, n, tid, w, lane, wave_last, lt_mask, tx0, ty0, s_r0,
+                                                  s_r1, s_z, s_id, s_list[w]);
+        const uint16_t* lp = s_list[w];
+        for (int j = cnt - 1; j >= 0; --j) {
+            const int e = lp[j];
+            const float4 r0 = s_r0[e], r1 = s_r1[e];
+            const float dx = r0.x - pxf, dy = r0.y - pyf;
+            const PairAlpha a = pair_alpha(r0, r1, dx, dy);
+            const uint64_t validm = pair_valid(a, (uint32_t)(base + e), last, r1.z);
+            if (validm == 0) continue;
+            const float Tp = T;                                           // T_{i+1}
+            const DistStep d = dist_step(T, a, validm);                   // T = T_i
+            const float zt = s_z[e] - zref;
+            const float B = (oneTf - d.Tn) - Tp;
+            const float front = (M - R) - d.w * zt;                       // sum_{j<i} w_j z_j: closes on 0 at the front entry
+            const float ei = G2 * (fmaf(zt, B, R) - front);               // G dDist/dw_i
+            const float dz = G2 * (d.w * B);                              // G dDist/dz_i  (0 on the masked lanes)
+            const float sm = ei - S;
+            const float q = d.a_m * (sm * d.Tn);                          // as pair_grad: the gradient passes the 0.99 clamp
+            S = fmaf(d.alpha_m, sm, S);
+            R = dist_moment_add(R, d.w, zt);
+            const BwdSums v = {q * dx, q * dy, q * a.ev.dxx, q * a.ev.dxy, q * a.ev.dyy, q, 0.f, 0.f, 0.f};
+            reduce_and_add<true>(v, dz, [](float x) { return cross_row_allreduce(x); }, [=] { return s_id[e]; }, grad_rec, alane,
+                                 aoff);
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // statistics for the algorithmic-bytes formula: D_trav = sum_tiles max_pixels n_contrib, V = #radii>0
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void tile_stats_kernel(ViewParams vp, const uint32_t* __restrict__ n_contrib,
@@ -1930,6 +2132,26 @@ hipError_t launch_blend_features_backward(const ViewParams& vp, int P, const cha
     return hipGetLastError();
 }
 size_t features_scratch_bytes(int P) { return sizeof(double) * FEAT_CB * (size_t)(P > 0 ? P : 1); }
+
+// msgs_distortion_forward / _backward (SPEC M13): one launch each, the four-waves-per-tile shape whatever the tile count
+hipError_t launch_blend_distortion_forward(const ViewParams& vp, const char* geom, const uint32_t* ids, const uint2* ranges,
+                                           const float* final_T, const uint32_t* n_contrib, float* out_distortion,
+                                           float* out_moment, hipStream_t s) {
+    const int tiles = vp.gx * vp.gy;
+    if (tiles <= 0) return hipSuccess;
+    hipLaunchKernelGGL(blend_distortion_forward_kernel, dim3(tiles), dim3(256), 0, s, vp, reinterpret_cast<const GaussRec*>(geom),
+                       ids, ranges, final_T, n_contrib, out_distortion, out_moment);
+    return hipGetLastError();
+}
+hipError_t launch_blend_distortion_backward(const ViewParams& vp, const char* geom, const uint32_t* ids, const uint2* ranges,
+                                            const float* final_T, const uint32_t* n_contrib, const float* moment,
+                                            const float* dL_ddist, grad_acc_t* grad_rec, hipStream_t s) {
+    const int tiles = vp.gx * vp.gy;
+    if (tiles <= 0) return hipSuccess;
+    hipLaunchKernelGGL(blend_distortion_backward_kernel, dim3(tiles), dim3(256), 0, s, vp, reinterpret_cast<const GaussRec*>(geom),
+                       ids, ranges, final_T, n_contrib, moment, dL_ddist, grad_rec);
+    return hipGetLastError();
+}
 
 // ---------------------------------------------------------------------------------------------
 // Deterministic backward (msgs_set_deterministic): no float atomics.  K7 stores the nine sums of every tile entry;

@@ -798,6 +798,14 @@ hipError_t launch_blend_features_backward(const ViewParams& vp, int P, const cha
                                           const float* final_T, const uint32_t* n_contrib, const float* features, int C,
                                           const float* dL_dF, grad_acc_t* grad_rec, double* acc, float* dL_dfeatures,
                                           hipStream_t s);
+// msgs_distortion_* (SPEC M13): the depth-distortion map [H,W] and its moment map; the backward adds the six geometry sums of q
+// and the dL/dz sum (slot 9) into grad_rec
+hipError_t launch_blend_distortion_forward(const ViewParams& vp, const char* geom, const uint32_t* ids, const uint2* ranges,
+                                           const float* final_T, const uint32_t* n_contrib, float* out_distortion,
+                                           float* out_moment, hipStream_t s);
+hipError_t launch_blend_distortion_backward(const ViewParams& vp, const char* geom, const uint32_t* ids, const uint2* ranges,
+                                            const float* final_T, const uint32_t* n_contrib, const float* moment,
+                                            const float* dL_ddist, grad_acc_t* grad_rec, hipStream_t s);
 // heaviest-first launch order of the one-wave-per-tile backward from the forward's per-tile traversal lengths
 hipError_t launch_tile_order(const ViewParams& vp, const uint32_t* tile_last, uint32_t* tile_order, hipStream_t s);
 hipError_t launch_blend_lane_stats(const ViewParams& vp, const char* geom, const uint32_t* ids, const uint2* ranges,

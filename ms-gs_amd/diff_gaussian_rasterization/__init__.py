@@ -330,6 +330,8 @@ def _note_camera(ctx, camera, behind=0):
 #   [bg]                               grad mode on and settings.bg requires grad: the background colour, for its gradient
 #   [_ALPHA]                           return_alpha=True: a marker (not a tensor) — the Function returns alpha as a sixth output
 #   [_AbsgradMarker]                   absgrad=True: a marker holding a weak reference to the caller's means2D
+#   [_DISTORTION]                      return_distortion=True: a marker — the Function returns the distortion map [H,W] behind
+#                                      alpha and in front of the feature map
 #   [_FEATURES, features]              features given: a marker and the [P,C] tensor, always LAST — the marker tells the tensor
 #                                      from bg; the Function returns the feature map [C,H,W] as its last output
 # A call that asks for none of the new things passes exactly what it passed before them.
@@ -384,27 +386,49 @@ def _check_features(features, P, dev):
     return features
 
 
-def _extra_inputs(rs, return_alpha=False, absgrad=False, means2D=None, features=None, model=None):
+# Depth distortion (4.13).  return_distortion=True adds one output [H,W] behind alpha:
+# Dist_p = 2 sum_{j<i} w_ip w_jp (z_i - z_j), the signed list-order form of the Mip-NeRF 360 distortion loss over the pairs the
+# backward counts (msgs_distortion_forward: a replay of the blend walk behind the forward).  A loss on the map makes the
+# backward first run msgs_distortion_backward, which adds the map's geometry sums and its dL/dz sum to the gradient records,
+# then today's depth-variant backward with scratch_is_clear = 1 on top of them.  A loss that does not use the map takes today's
+# backward unchanged.
+class _DistortionMarker:
+    def __repr__(self):
+        return "return_distortion"
+
+
+_DISTORTION = _DistortionMarker()
+
+
+def _extra_inputs(rs, return_alpha=False, absgrad=False, means2D=None, features=None, model=None, return_distortion=False):
     """model: the call's means3D / xyz (its rows and device check `features`)"""
     if absgrad and _C.lib.msgs_get_deterministic():
         raise ValueError("absgrad=True is not offered in the verification mode (set_deterministic): that mode checks the "
                          "gradients, it does not train")
+    if return_distortion and _C.lib.msgs_get_deterministic():
+        raise ValueError("return_distortion=True is not offered in the verification mode (set_deterministic): that mode "
+                         "checks the gradients of the reference's outputs")
     if features is not None:
         features = _check_features(features, int(model.shape[0]), model.device)
-    if features is not None:
-        return tuple(_extra_inputs(rs, return_alpha, absgrad, means2D)) + (_FEATURES, features)
     extra = _camera_inputs(rs)
     if torch.is_grad_enabled() and torch.is_tensor(rs.bg) and rs.bg.requires_grad:
         extra = tuple(extra) + (rs.bg,)
     if return_alpha:
         extra = tuple(extra) + (_ALPHA,)
-    return tuple(extra) + (_AbsgradMarker(means2D),) if absgrad else extra
+    if absgrad:
+        extra = tuple(extra) + (_AbsgradMarker(means2D),)
+    if return_distortion:
+        extra = tuple(extra) + (_DISTORTION,)
+    if features is not None:
+        extra = tuple(extra) + (_FEATURES, features)
+    return extra
 
 
 def _note_extra(ctx, extra):
     """forward: split the trailing inputs; leaves ctx.camera (_note_camera), ctx.bg ((shape, dtype, device) when the
     background wants a gradient, else None), ctx.n_extra_tail (inputs behind the camera's), ctx.absgrad (the marker or None)
-    ctx.features (the caller's tensor or None), ctx.feat (its contiguous float32 form) and returns return_alpha"""
+    ctx.features (the caller's tensor or None), ctx.feat (its contiguous float32 form), ctx.distortion (return_distortion) and
+    returns return_alpha"""
     ctx.features = ctx.feat = None
     n_feat = 0
     if len(extra) >= 2 and extra[-2] is _FEATURES:
@@ -412,6 +436,9 @@ def _note_extra(ctx, extra):
         ctx.feat = _f32c(extra[-1].detach())
         ctx.features_want = bool(ctx.needs_input_grad[-1])
         extra = extra[:-2]
+    ctx.distortion = bool(extra) and extra[-1] is _DISTORTION
+    n_feat += int(ctx.distortion)                              # (from here on: the inputs behind the absgrad marker)
+    extra = extra[:-1] if ctx.distortion else extra
     ctx.absgrad = extra[-1] if extra and isinstance(extra[-1], _AbsgradMarker) else None
     n_abs = int(ctx.absgrad is not None)
     rest = extra[:-1] if n_abs else extra
@@ -460,19 +487,20 @@ def _bg_grad(ctx, view_ref, image, dL, W, H, dev, stream):
 
 
 def _extra_grads(ctx, g_cam, g_bg):
-    """gradients of the trailing inputs in their order: camera, bg, the alpha marker, the absgrad marker, the features marker and
-    dL/dfeatures (in the tensor's shape and dtype; None when the loss did not use the feature map)"""
+    """gradients of the trailing inputs in their order: camera, bg, the alpha marker, the absgrad marker, the distortion marker,
+    the features marker and dL/dfeatures (in the tensor's shape and dtype; None when the loss did not use the feature map)"""
     g_feat = ()
     if ctx.features is not None:
         g, ctx.g_features = getattr(ctx, "g_features", None), None
         g_feat = (None, g.view(ctx.features.shape).to(ctx.features.dtype) if g is not None and ctx.features_want else None)
     return tuple(g_cam) + ((g_bg,) if ctx.has_bg else ()) + ((None,) if ctx.return_alpha else ()) + \
-        ((None,) if ctx.absgrad is not None else ()) + g_feat
+        ((None,) if ctx.absgrad is not None else ()) + ((None,) if ctx.distortion else ()) + g_feat
 
 
 def _split_grad_tail(ctx, tail):
-    """the gradients of the outputs behind the reference's five: (grad_alpha, grad_features)"""
-    return (tail[0] if ctx.return_alpha else None), (tail[-1] if ctx.features is not None else None)
+    """the gradients of the outputs behind the reference's five: (grad_alpha, grad_distortion, grad_features)"""
+    return (tail[0] if ctx.return_alpha else None), (tail[int(ctx.return_alpha)] if ctx.distortion else None), \
+        (tail[-1] if ctx.features is not None else None)
 
 
 _features_probe = None             # tests: a callable (name) run in front of every msgs_features_* call
@@ -517,6 +545,45 @@ def _features_backward(ctx, call, geom, binning, image, D, grad_features, scratc
              "msgs_features_backward")
     ctx.g_features = out
     return 1 if geom_share else is_clear
+
+
+_distortion_probe = None           # tests: a callable (name) run in front of every msgs_distortion_* call
+
+
+def _distortion_forward(ctx, call, state):
+    """the distortion map [H,W] of a return_distortion=True call: msgs_distortion_forward on the current stream, behind the
+    forward that left `state`; the moment map the backward needs stays on ctx.  A deferred forward is resolved first (the replay
+    needs the instance count): correct, at the price of that view's overlap."""
+    geom, binning, image, D = _resolve(state)
+    dev, P = call.device, call.P
+    if _distortion_probe is not None:
+        _distortion_probe("msgs_distortion_forward")
+    with _on_device(dev):
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        out = torch.empty(call.H, call.W, dtype=torch.float32, device=dev)
+        ctx.dist_moment = torch.empty(call.H, call.W, dtype=torch.float32, device=dev)
+        _C.check(_C.lib.msgs_distortion_forward(call.view_ref, P, _ptr(geom), geom.numel(), D, _ptr(binning),
+                                                binning.numel() if binning is not None else 0, _ptr(image), image.numel(),
+                                                _ptr(out), _ptr(ctx.dist_moment), stream), "msgs_distortion_forward")
+    return out
+
+
+def _distortion_backward(ctx, call, geom, binning, image, D, grad_distortion, dLd, scratch, is_clear, dev, stream):
+    """In front of _run_backward, when the loss used the distortion map: the map's geometry sums (record slots 0..5) and its
+    dL/dz sum (slot 9) ADDED to the gradient records in `scratch` — cleared here unless it is the buffer the forward cleared.
+    Returns (dL/ddepth to hand on, scratch_is_clear to hand on): the depth variant of the backward consumes slot 9, so a loss
+    without a depth term passes a zero map (fmaf(z, 0, g) is exact: the colour sums keep their bits)."""
+    if not is_clear:
+        scratch.zero_()
+    if _distortion_probe is not None:
+        _distortion_probe("msgs_distortion_backward")
+    _C.check(_C.lib.msgs_distortion_backward(call.view_ref, call.P, _ptr(geom), geom.numel(), D, _ptr(binning),
+                                             binning.numel() if binning is not None else 0, _ptr(image), image.numel(),
+                                             _ptr(ctx.dist_moment), _ptr(_f32c(grad_distortion)), _ptr(scratch), scratch.numel(),
+                                             stream), "msgs_distortion_backward")
+    if dLd is None:
+        dLd = torch.zeros(call.H, call.W, dtype=torch.float32, device=dev)
+    return dLd, 1
 
 
 def _refuse_camera_with(camera):
@@ -957,10 +1024,12 @@ def _forward_impl(call, grad_rec=None, backward_follows=False, want_alpha=False)
 
 def _forward_tail(ctx, call, state, outs, geometry=(0, 1, 4, 5, 6)):
     """the end of every autograd forward: what its backward finds on ctx; returns the five outputs (six with return_alpha, and
-    the feature map behind them when features were given).  geometry: the positions of the inputs whose gradient the per-
+    the distortion map, then the feature map behind them when asked for).  geometry: the positions of the inputs whose gradient the per-
     Gaussian backward forms from the records' geometry slots (the camera's follow from ctx.camera)."""
     color, acc_ps, depth, radii, pixel_sizes = outs[:5]
     ctx.call, ctx.state, ctx.radii = call, state, radii
+    if ctx.distortion:
+        outs = tuple(outs) + (_distortion_forward(ctx, call, state),)
     if ctx.features is not None:
         ctx.features_geom = any(ctx.needs_input_grad[k] for k in geometry) or any(m is not None for m in ctx.camera)
         outs = tuple(outs) + (_features_forward(ctx, call, state),)
@@ -993,6 +1062,8 @@ class _RasterizeGaussians(torch.autograd.Function):
             ctx.mark_non_differentiable(outs[1], *outs[3:])     # (depth stays differentiable: zero gradients)
             if want_alpha:                                      # (nothing blended: alpha 0, zero gradients)
                 outs = outs + (torch.zeros(H, W, device=dev),)
+            if ctx.distortion:                                  # (nothing blended: no pair, zero gradients)
+                outs = outs + (torch.zeros(H, W, device=dev),)
             if ctx.features is not None:                        # (nothing blended: a zero map, zero gradients)
                 outs = outs + (torch.zeros(int(ctx.features.shape[1]), H, W, device=dev),)
             ctx.set_materialize_grads(False)
@@ -1008,7 +1079,7 @@ class _RasterizeGaussians(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_color, grad_acc_ps, grad_depth, grad_radii, grad_pixel_sizes, *grad_tail):
-        grad_alpha, grad_features = _split_grad_tail(ctx, grad_tail)
+        grad_alpha, grad_distortion, grad_features = _split_grad_tail(ctx, grad_tail)
         if ctx.empty:
             cam = tuple(None if m is None else torch.zeros(m[0], dtype=m[1], device=m[2]) for m in ctx.camera)
             g_bg = None
@@ -1045,7 +1116,8 @@ class _RasterizeGaussians(torch.autograd.Function):
             g_rot = torch.empty(P, 4, dtype=torch.float32, device=dev) if call.rot is not None else None
             g_cov = torch.empty(P, 6, dtype=torch.float32, device=dev) if call.cov is not None else None
             dLd = _f32c(grad_depth) if grad_depth is not None else None
-            scratch, is_clear = _take_backward_scratch(ctx, P, D, dev, dLd is not None)
+            scratch, is_clear = _take_backward_scratch(ctx, P, D, dev, dLd is not None or grad_distortion is not None)
+            dLd_loss = dLd                                      # (what the loss itself sent to the depth map: absgrad's input)
             grads = _C.Grads(_ptr(g_means3D), _ptr(g_means2D), _ptr(g_sh), _ptr(g_col), _ptr(g_opac),
                              _ptr(g_scales), _ptr(g_rot), _ptr(g_cov), None, None, None, is_clear)
             cam = _CameraGrads(ctx, P, dev) if ctx.camera else None
@@ -1053,10 +1125,13 @@ class _RasterizeGaussians(torch.autograd.Function):
             if grad_features is not None:
                 grads.scratch_is_clear = _features_backward(ctx, call, geom, binning, image, D, grad_features, scratch, is_clear,
                                                             dev, stream)
+            if grad_distortion is not None:
+                dLd, grads.scratch_is_clear = _distortion_backward(ctx, call, geom, binning, image, D, grad_distortion, dLd, scratch,
+                                                                   grads.scratch_is_clear, dev, stream)
             _run_backward(lib, call, ctx, geom, binning, image, D, dL, dLd, dLa, scratch, grads, stream, cam)
             g_bg = _bg_grad(ctx, call.view_ref, image, dL, call.W, call.H, dev, stream) if ctx.bg is not None else None
             if ctx.absgrad is not None:
-                _absgrad(ctx, call, geom, binning, image, D, dL, dLd, dLa, dev, stream)
+                _absgrad(ctx, call, geom, binning, image, D, dL, dLd_loss, dLa, dev, stream)
         m2_shape, op_shape = ctx.shapes
         # occ_multiplier / dc_delta / pixel-size inputs / masks receive no gradient (DESIGN.md SPEC M5)
         return (g_means3D, g_means2D.view(m2_shape) if g_means2D.shape == m2_shape else g_means2D,
@@ -1266,7 +1341,7 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_color, grad_acc_ps, grad_depth, grad_radii, grad_pixel_sizes, *grad_tail):
-        grad_alpha, grad_features = _split_grad_tail(ctx, grad_tail)
+        grad_alpha, grad_distortion, grad_features = _split_grad_tail(ctx, grad_tail)
         _check_saved(ctx)
         call = ctx.call
         if grad_color is None:
@@ -1308,7 +1383,8 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
                     g_dc, g_rest = _grad_out(kdc, dc_shape, dev), _grad_out(krest, rest_shape, dev)
                 g_opac, g_scal, g_rot = _grad_out(kop, op_shape, dev), _grad_out(ksc, (P, 3), dev), _grad_out(krot, (P, 4), dev)
             dLd = _f32c(grad_depth) if grad_depth is not None else None
-            scratch, is_clear = _take_backward_scratch(ctx, P, D, dev, dLd is not None)
+            scratch, is_clear = _take_backward_scratch(ctx, P, D, dev, dLd is not None or grad_distortion is not None)
+            dLd_loss = dLd                                      # (what the loss itself sent to the depth map: absgrad's input)
             grads = _C.Grads(_ptr(g_xyz), _ptr(g_m2), None, _ptr(factor), _ptr(g_opac), _ptr(g_scal), _ptr(g_rot), None,
                              _ptr(g_dc), _ptr(g_rest),
                              C.c_void_p(ready.cuda_event) if (factor is not None and ready is not None) else None,
@@ -1318,12 +1394,15 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
             if grad_features is not None:
                 grads.scratch_is_clear = _features_backward(ctx, call, geom, binning, image, D, grad_features, scratch, is_clear,
                                                             dev, stream)
+            if grad_distortion is not None:
+                dLd, grads.scratch_is_clear = _distortion_backward(ctx, call, geom, binning, image, D, grad_distortion, dLd, scratch,
+                                                                   grads.scratch_is_clear, dev, stream)
             _run_backward(lib, call, ctx, geom, binning, image, D, dL, dLd, dLa, scratch, grads, stream, cam)
             if adam is not None:
                 step_opt.commit_step_in_backward(ctx.leaves)
             g_bg = _bg_grad(ctx, call.view_ref, image, dL, call.W, call.H, dev, stream) if ctx.bg is not None else None
             if ctx.absgrad is not None:
-                _absgrad(ctx, call, geom, binning, image, D, dL, dLd, dLa, dev, stream)
+                _absgrad(ctx, call, geom, binning, image, D, dL, dLd_loss, dLa, dev, stream)
         g_cam = _extra_grads(ctx, cam.grads(ctx) if cam is not None else (), g_bg)
         if accum is not None or adam is not None:   # the leaf gradients live in the accumulator / were consumed by the step
             return (None, g_m2.view(m2_shape), None, None, None, None, None, None, None, None, None, None, None) + g_cam
@@ -1444,12 +1523,13 @@ def sh_grad_from_views(means3D, gathered, n_views, sh_degree, scale, out_dc, out
 
 def rasterize_gaussians_raw(xyz, means2D, features_dc, features_rest, opacity_raw, scaling_raw, rotation_raw,
                             max_pixel_sizes, min_pixel_sizes, occ_multiplier, dc_delta, base_mask, raster_settings,
-                            features=None, absgrad=False, return_alpha=False):
+                            features=None, return_distortion=False, absgrad=False, return_alpha=False):
     """return_alpha=True: a sixth output, the alpha map [H,W] (1 - final transmittance), differentiable
     absgrad=True: every backward also assigns means2D.absgrad.
-    features [P,C]: one more output at the END, the feature map [C,H,W], differentiable.  All three by
-    keyword."""
-    extra = _extra_inputs(raster_settings, return_alpha, absgrad, means2D, features, xyz)
+    features [P,C]: one more output at the END, the feature map [C,H,W], differentiable.
+    return_distortion=True: one more output behind alpha and in front of the feature map, the depth-distortion map [H,W],
+    differentiable.  All four by keyword."""
+    extra = _extra_inputs(raster_settings, return_alpha, absgrad, means2D, features, xyz, return_distortion)
     _note_grad_mode()
     return _RasterizeGaussiansRaw.apply(xyz, means2D, features_dc, features_rest, opacity_raw, scaling_raw,
                                         rotation_raw, max_pixel_sizes, min_pixel_sizes, occ_multiplier, dc_delta,
@@ -1459,12 +1539,13 @@ def rasterize_gaussians_raw(xyz, means2D, features_dc, features_rest, opacity_ra
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                         max_pixel_sizes, min_pixel_sizes, occ_multiplier, dc_delta, base_mask, raster_settings,
-                        features=None, absgrad=False, return_alpha=False):
+                        features=None, return_distortion=False, absgrad=False, return_alpha=False):
     """return_alpha=True: a sixth output, the alpha map [H,W] (1 - final transmittance), differentiable
     absgrad=True: every backward also assigns means2D.absgrad.
-    features [P,C]: one more output at the END, the feature map [C,H,W], differentiable.  All three by
-    keyword."""
-    extra = _extra_inputs(raster_settings, return_alpha, absgrad, means2D, features, means3D)
+    features [P,C]: one more output at the END, the feature map [C,H,W], differentiable.
+    return_distortion=True: one more output behind alpha and in front of the feature map, the depth-distortion map [H,W],
+    differentiable.  All four by keyword."""
+    extra = _extra_inputs(raster_settings, return_alpha, absgrad, means2D, features, means3D, return_distortion)
     _note_grad_mode()
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
                                      cov3Ds_precomp, max_pixel_sizes, min_pixel_sizes, occ_multiplier, dc_delta,
@@ -1565,6 +1646,25 @@ class GaussianRasterizer(nn.Module):
         self.return_alpha = bool(return_alpha)
         self.absgrad = bool(absgrad)
         self.features = None
+        self.return_distortion = False
+
+    def with_distortion(self, return_distortion=True):
+        """A rasterizer like this one whose forward / forward_raw also return the depth-distortion map [H,W] float32,
+            Dist_p = 2 sum_{j<i} w_ip w_jp (z_i - z_j),   w_ip = alpha_ip T_ip,   z_i the view depth the depth map blends,
+        over exactly the pairs the backward counts, in tile-list order (front to back): the signed list-order form of the
+        Mip-NeRF 360 distortion loss sum_i sum_j w_i w_j |z_i - z_j| (2DGS, gsplat's distloss), equal to it on a depth-sorted
+        list and without a kink at ties.  No background term; exactly 0 for a pixel with fewer than two blended Gaussians.  The
+        map is one more output behind alpha and in front of the feature map.  Differentiable: a loss on it sends gradients to
+        means, opacity, scales / rotations / cov3D and the camera; SH and colours receive nothing from it.  A loss that ignores
+        the map runs today's backward unchanged.  With absgrad=True the statistic means2D.absgrad does NOT include the
+        distortion's share: it is that of the colour, depth and alpha terms, as without the map.  Inside deferred_forward such
+        a call resolves its own view before the replay: correct, but that view's overlap is lost.  Not offered in the
+        verification mode (set_deterministic): ValueError before any launch.
+        (__init__ keeps its pinned parameters, so the flag travels on the module, as with_features() does.)"""
+        r = GaussianRasterizer(self.raster_settings, self.return_alpha, self.absgrad)
+        r.features = self.features
+        r.return_distortion = bool(return_distortion)
+        return r
 
     def with_features(self, features):
         """A rasterizer like this one whose forward / forward_raw also splat `features` [P,C] (float32 device tensor, C >= 1;
@@ -1579,6 +1679,7 @@ class GaussianRasterizer(nn.Module):
         (forward() keeps the reference's 13 parameters, so the tensor travels on the module.)"""
         r = GaussianRasterizer(self.raster_settings, self.return_alpha, self.absgrad)
         r.features = features
+        r.return_distortion = self.return_distortion
         return r
 
     def markVisible(self, positions):
@@ -1669,21 +1770,26 @@ class GaussianRasterizer(nn.Module):
             return None if into is not None else acc.scores()
 
     def forward_raw(self, xyz, means2D, features_dc, features_rest, opacity_raw, scaling_raw, rotation_raw,
-                    max_pixel_sizes=None, min_pixel_sizes=None, occ_multiplier=None, dc_delta=None, base_mask=None, features=None):
+                    max_pixel_sizes=None, min_pixel_sizes=None, occ_multiplier=None, dc_delta=None, base_mask=None, features=None,
+                    return_distortion=None):
         """Opt-in fused path on raw GaussianModel parameters (not part of the reference API).  features [P,C]: as in
-        with_features(); None: the module's own (with_features), if any."""
+        with_features(); None: the module's own (with_features), if any.  return_distortion: as in with_distortion(); None:
+        the module's own."""
         features = features if features is not None else self.features
+        return_distortion = self.return_distortion if return_distortion is None else bool(return_distortion)
         empty = torch.Tensor([])
         o = lambda t: t if t is not None else empty
         return rasterize_gaussians_raw(xyz, means2D, features_dc, features_rest, opacity_raw, scaling_raw,
                                        rotation_raw, o(max_pixel_sizes), o(min_pixel_sizes), o(occ_multiplier),
                                        o(dc_delta), o(base_mask), self.raster_settings, absgrad=self.absgrad,
-                                       return_alpha=self.return_alpha, features=features)
+                                       return_alpha=self.return_alpha, features=features,
+                                       return_distortion=return_distortion)
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
                 cov3D_precomp=None, max_pixel_sizes=None, min_pixel_sizes=None, occ_multiplier=None,
                 dc_delta=None, base_mask=None):
-        """The reference's 13 parameters.  Feature channels travel on the module: with_features(features)(...)."""
+        """The reference's 13 parameters.  Feature channels and the distortion map travel on the module:
+        with_features(features)(...), with_distortion()(...)."""
         rs = self.raster_settings
         features = self.features
         if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
@@ -1711,7 +1817,7 @@ class GaussianRasterizer(nn.Module):
                     means3D, means2D, *leaves, shs.detach() if _chain_reads_cat else empty, opacities.detach(), scales.detach(),
                     rotations.detach(),
                     o(max_pixel_sizes), o(min_pixel_sizes), o(occ_multiplier), o(dc_delta), o(base_mask), rs,
-                    *_extra_inputs(rs, self.return_alpha, self.absgrad, means2D, features, means3D))
+                    *_extra_inputs(rs, self.return_alpha, self.absgrad, means2D, features, means3D, self.return_distortion))
         return rasterize_gaussians(
             means3D, means2D,
             shs if shs is not None else empty,
@@ -1725,4 +1831,5 @@ class GaussianRasterizer(nn.Module):
             occ_multiplier if occ_multiplier is not None else empty,
             dc_delta if dc_delta is not None else empty,
             base_mask if base_mask is not None else empty,
-            rs, absgrad=self.absgrad, return_alpha=self.return_alpha, features=features)
+            rs, absgrad=self.absgrad, return_alpha=self.return_alpha, features=features,
+            return_distortion=self.return_distortion)

@@ -210,6 +210,10 @@ def _load():
     lib.msgs_features_backward.restype = C.c_int
     lib.msgs_features_backward.argtypes = [C.POINTER(View), C.c_int32, vp, sz, C.c_int64, vp, sz, vp, sz, vp, C.c_int32, vp,
                                            vp, sz, vp, sz, vp, vp]
+    lib.msgs_distortion_forward.restype = C.c_int
+    lib.msgs_distortion_forward.argtypes = [C.POINTER(View), C.c_int32, vp, sz, C.c_int64, vp, sz, vp, sz, vp, vp, vp]
+    lib.msgs_distortion_backward.restype = C.c_int
+    lib.msgs_distortion_backward.argtypes = [C.POINTER(View), C.c_int32, vp, sz, C.c_int64, vp, sz, vp, sz, vp, vp, vp, sz, vp]
     lib.msgs_backward_per_gaussian.restype = C.c_int
     lib.msgs_backward_per_gaussian.argtypes = [C.POINTER(View), C.POINTER(Gaussians), vp, vp, sz, vp, C.POINTER(Grads), vp]
     lib.msgs_sh_grad_from_views.restype = C.c_int
@@ -284,7 +288,8 @@ EXPORTS = ("msgs_abi_version", "msgs_error_string", "msgs_geom_bytes", "msgs_sta
            "msgs_alpha_map", "msgs_backward_with_alpha", "msgs_bg_grad_scratch_bytes", "msgs_bg_grad",
            "msgs_absgrad_scratch_bytes", "msgs_absgrad",
            "msgs_contrib_scratch_bytes", "msgs_contrib_accumulate", "msgs_contrib_finish",
-           "msgs_features_scratch_bytes", "msgs_features_forward", "msgs_features_backward")
+           "msgs_features_scratch_bytes", "msgs_features_forward", "msgs_features_backward",
+           "msgs_distortion_forward", "msgs_distortion_backward")
 
 
 def check(rc, where):

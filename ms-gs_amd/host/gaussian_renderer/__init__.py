@@ -245,3 +245,51 @@ def render_with_features(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, fea
     out = dict(zip(RESULT_KEYS, values))
     out["features"] = outs[5] if len(outs) > 5 else None
     return out
+
+
+def render_with_distortion(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, override_color=None,
+                           filter_small=False, filter_large=False, fade_size=1.0, fused=False, alpha=False):
+    """render() — or, with fused=True, render_fused() (then without override_color) — plus the depth distortion of every ray:
+    the seven keys of RESULT_KEYS, "alpha" (render_with_alpha) with alpha=True, and "distortion" [H,W] float32,
+    Dist_p = 2 sum_{j<i} w_ip w_jp (z_i - z_j) with w = alpha T the blend weights of this render and z the view depth, over the
+    pairs the backward counts in front-to-back order: the distortion loss of Mip-NeRF 360 / 2DGS / gsplat's distloss in its
+    signed list-order form.  No background term; 0 where fewer than two Gaussians were blended.  Differentiable: its mean times
+    a small weight is the usual regulariser that keeps the coarse and fine Gaussians of one surface from separating in depth;
+    the gradient reaches the geometry and the camera, not SH / colours.  Image, maps and their gradients
+    are those of the call without it, bit for bit."""
+    settings = _settings(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, filter_small, filter_large, fade_size)
+    rasterizer = GaussianRasterizer(raster_settings=settings, return_alpha=alpha).with_distortion()
+    if fused:
+        if override_color is not None:
+            raise ValueError("render_with_distortion: fused=True cannot be combined with override_color")
+        xyz = pc._xyz
+        viewspace = torch.empty_like(xyz, requires_grad=True)
+        outs = rasterizer.forward_raw(
+            xyz, viewspace, pc._features_dc, pc._features_rest, pc._opacity, pc._scaling, pc._rotation,
+            max_pixel_sizes=pc.get_max_pixel_sizes, min_pixel_sizes=pc.get_min_pixel_sizes,
+            occ_multiplier=pc.get_occ_multiplier, dc_delta=pc.get_dc_delta, base_mask=pc.get_base_mask)
+    else:
+        xyz = pc.get_xyz
+        viewspace = torch.zeros_like(xyz, requires_grad=True) + 0
+        try:
+            viewspace.retain_grad()
+        except Exception:
+            pass
+        outs = rasterizer(
+            means3D=xyz,
+            means2D=viewspace,
+            opacities=pc.get_opacity,
+            max_pixel_sizes=pc.get_max_pixel_sizes,
+            min_pixel_sizes=pc.get_min_pixel_sizes,
+            occ_multiplier=pc.get_occ_multiplier,
+            dc_delta=pc.get_dc_delta,
+            base_mask=pc.get_base_mask,
+            **_colour_inputs(viewpoint_camera, pc, pipe, override_color),
+            **_shape_inputs(pc, pipe, scaling_modifier))
+    image, acc_pixel_size, depth, radii, pixel_sizes = outs[:5]
+    values = (image, acc_pixel_size, depth, viewspace, radii > 0, radii, pixel_sizes)
+    out = dict(zip(RESULT_KEYS, values))
+    if alpha:
+        out["alpha"] = outs[5]
+    out["distortion"] = outs[5 + int(bool(alpha))]
+    return out
