@@ -476,6 +476,33 @@ int msgs_distortion_backward(const msgs_view_t* view, int32_t P,
                              const float* moment, const float* dL_ddistortion,
                              void* grad_records, size_t grad_records_bytes, void* stream);
 
+/* ---- antialiasing: the opacity compensation of the 2-D screen filter as a pre-pass (DESIGN.md SPEC M14, 4.14) ------ */
+/* The +0.3 dilation of the projected covariance (Q3) brightens every Gaussian smaller than a pixel.  Mip-Splatting's
+ * compensation — upstream 3DGS's antialiasing=True, gsplat's rasterize_mode="antialiased" — scales the opacity by
+ *     rho_i = sqrt(max(0.000025, det0 / det1)),   det0 = a0 c0 - b^2,   det1 = (a0 + 0.3)(c0 + 0.3) - b^2
+ * with (a0, b, c0) the entries of T Sigma3D T^T before the dilation, the same float32 values msgs_forward* forms for this view
+ * (tanfov, image size, scale_modifier and viewmatrix of `view`; scales + rotations or cov3D_precomp of `g`).  An antialiased
+ * render IS the plain render — any msgs_forward* / msgs_backward* entry, any opt-in output — of the same model with
+ *     msgs_screen_compensation_forward:   o_eff [P] float32,  o_eff_i = o_i rho_i
+ * in the place of the opacities; pixel sizes and the multi-scale filters then see o_eff.  rho_i = 1 exactly (o_eff_i = o_i bit
+ * for bit, no geometry gradient) where the view depth is <= 0.2 (Q1), where det1 == 0, or where an input of the row or the
+ * result is not finite: rows the renderer skips anyway.
+ *     msgs_screen_compensation_backward:  from dL_do_eff [P]:  dL_dopacity [P] = rho dL_do_eff;  dL_dmeans3D [P,3];
+ *     dL_dscales [P,3] + dL_drotations [P,4], or dL_dcov3D [P,6] (off-diagonals doubled, as msgs_backward writes them) — every row
+ *     is written, zeros where rho is 1 or sits on its floor; each pointer may be NULL (not wanted), one for a tensor `g` does
+ *     not carry is MSGS_ERR_INVALID_ARG.  dL_dV [16] (may be NULL): dL/dviewmatrix in the flat layout of
+ *     msgs_backward_with_camera, through the view-space point and the rotation block, summed over the Gaussians in double in
+ *     a fixed order (the same bits on every run); it needs scratch >= msgs_screen_compensation_scratch_bytes(P), 8-byte
+ *     aligned.  projmatrix, campos and bg do not enter rho.  The projection is recomputed: nothing is kept from the forward.
+ * Reference-API inputs only (raw_params = 0, MSGS_ERR_INVALID_ARG otherwise); exactly one of (scales, rotations) /
+ * cov3D_precomp; shs, colours and the pixel-size inputs of `g`, and bg / projmatrix / campos of `view`, are not read.
+ * P == 0: nothing is launched (dL_dV, when given, is zero-filled). */
+size_t msgs_screen_compensation_scratch_bytes(int32_t P);
+int msgs_screen_compensation_forward(const msgs_view_t* view, const msgs_gaussians_t* g, float* o_eff, void* stream);
+int msgs_screen_compensation_backward(const msgs_view_t* view, const msgs_gaussians_t* g, const float* dL_do_eff,
+                                      float* dL_dopacity, float* dL_dmeans3D, float* dL_dscales, float* dL_drotations,
+                                      float* dL_dcov3D, float* dL_dV, void* scratch, size_t scratch_bytes, void* stream);
+
 /* msgs_backward_per_gaussian: the per-Gaussian half of msgs_backward ALONE (2-D covariance backward, projection, SH,
  * scale / quaternion chain — upstream's computeCov2DCUDA + preprocessCUDA backward, SURVEY 2.2 K8 + K9) on per-Gaussian
  * 2-D gradients supplied by the caller instead of the blend backward's sums: sums2d [P,9] DOUBLES (device) =

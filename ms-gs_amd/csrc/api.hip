@@ -979,6 +979,56 @@ int msgs_distortion_backward(const msgs_view_t* view, int32_t P, const void* geo
                                              (grad_acc_t*)grad_records, s));
     return debug_sync(view, s);
 }
+
+// ---- antialiasing: the opacity compensation of the 2-D screen filter, in front of K1 (SPEC M14) ----
+}  // extern "C"
+namespace {
+// the view's geometry and the activated inputs of the reference API: nothing else enters rho
+inline int check_compensation_inputs(const msgs_view_t* v, const msgs_gaussians_t* g) {
+    if (!v || !g || g->P < 0 || v->image_width <= 0 || v->image_height <= 0 || !v->viewmatrix) return MSGS_ERR_INVALID_ARG;
+    if (g->raw_params != 0) return MSGS_ERR_INVALID_ARG;
+    if (g->P == 0) return MSGS_OK;
+    if (!g->means3D || !g->opacities) return MSGS_ERR_INVALID_ARG;
+    const bool sr = g->scales != nullptr && g->rotations != nullptr;
+    if ((g->scales != nullptr) != (g->rotations != nullptr) || sr == (g->cov3D_precomp != nullptr)) return MSGS_ERR_INVALID_ARG;
+    return MSGS_OK;
+}
+}  // namespace
+extern "C" {
+
+size_t msgs_screen_compensation_scratch_bytes(int32_t P) { return screen_compensation_rows_bytes(P); }
+
+int msgs_screen_compensation_forward(const msgs_view_t* view, const msgs_gaussians_t* g, float* o_eff, void* stream) {
+    const int rc = check_compensation_inputs(view, g);
+    if (rc != MSGS_OK) return rc;
+    if (g->P == 0) return MSGS_OK;
+    if (!o_eff) return MSGS_ERR_INVALID_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(launch_screen_compensation_forward(make_view_params(view), *g, o_eff, s));
+    return debug_sync(view, s);
+}
+
+int msgs_screen_compensation_backward(const msgs_view_t* view, const msgs_gaussians_t* g, const float* dL_do_eff,
+                                      float* dL_dopacity, float* dL_dmeans3D, float* dL_dscales, float* dL_drotations,
+                                      float* dL_dcov3D, float* dL_dV, void* scratch, size_t scratch_bytes, void* stream) {
+    const int rc = check_compensation_inputs(view, g);
+    if (rc != MSGS_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    if (g->P == 0) {                                                         // no Gaussian: the camera sums are zero
+        if (dL_dV) HIP_TRY(launch_zero(dL_dV, sizeof(float) * 16, s));
+        return debug_sync(view, s);
+    }
+    if (!dL_do_eff) return MSGS_ERR_INVALID_ARG;
+    // a gradient the inputs have no tensor for would be written from zeros: refuse the pointer instead
+    if ((g->cov3D_precomp && (dL_dscales || dL_drotations)) || (!g->cov3D_precomp && dL_dcov3D)) return MSGS_ERR_INVALID_ARG;
+    if (dL_dV) {
+        if (!scratch || ((uintptr_t)scratch & 7)) return MSGS_ERR_INVALID_ARG;
+        if (scratch_bytes < msgs_screen_compensation_scratch_bytes(g->P)) return MSGS_ERR_CAPACITY;
+    }
+    HIP_TRY(launch_screen_compensation_backward(make_view_params(view), *g, dL_do_eff, dL_dopacity, dL_dmeans3D, dL_dscales,
+                                                dL_drotations, dL_dcov3D, dL_dV, (double*)scratch, s));
+    return debug_sync(view, s);
+}
 }  // extern "C"
 
 namespace {

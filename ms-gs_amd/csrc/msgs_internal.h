@@ -806,6 +806,13 @@ hipError_t launch_blend_distortion_forward(const ViewParams& vp, const char* geo
 hipError_t launch_blend_distortion_backward(const ViewParams& vp, const char* geom, const uint32_t* ids, const uint2* ranges,
                                             const float* final_T, const uint32_t* n_contrib, const float* moment,
                                             const float* dL_ddist, grad_acc_t* grad_rec, hipStream_t s);
+// antialias.hip — msgs_screen_compensation_* (SPEC M14): o_eff = o rho in front of K1, and its backward.  dL_dV NULL: no camera
+// sums and `rows` is not touched; otherwise rows >= screen_compensation_rows_bytes(P), 8-byte aligned
+size_t screen_compensation_rows_bytes(int P);
+hipError_t launch_screen_compensation_forward(const ViewParams& vp, const msgs_gaussians_t& g, float* o_eff, hipStream_t s);
+hipError_t launch_screen_compensation_backward(const ViewParams& vp, const msgs_gaussians_t& g, const float* dL_do_eff,
+                                               float* dL_dopacity, float* dL_dmeans3D, float* dL_dscales, float* dL_drotations,
+                                               float* dL_dcov3D, float* dL_dV, double* rows, hipStream_t s);
 // heaviest-first launch order of the one-wave-per-tile backward from the forward's per-tile traversal lengths
 hipError_t launch_tile_order(const ViewParams& vp, const uint32_t* tile_last, uint32_t* tile_order, hipStream_t s);
 hipError_t launch_blend_lane_stats(const ViewParams& vp, const char* geom, const uint32_t* ids, const uint2* ranges,

@@ -28,7 +28,8 @@ import torch.nn as nn
 from . import _backend as _C
 
 __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "rasterize_gaussians_raw",
-           "deferred_forward", "GradAccumulator", "set_grad_accumulator", "ContributionScores", "ContributionAccumulator"]
+           "deferred_forward", "GradAccumulator", "set_grad_accumulator", "ContributionScores", "ContributionAccumulator",
+           "screen_compensation"]
 
 
 class GaussianRasterizationSettings(NamedTuple):
@@ -1553,6 +1554,95 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
                                      *extra)
 
 
+# Antialiasing (4.14): the opacity compensation of Mip-Splatting's 2-D screen filter as a pre-pass.  An
+# antialiased render is the plain render of the same model with o_eff = o rho in the place of the opacity; the rasterizer, its
+# backward and every opt-in output only ever see an opacity tensor.
+_compensation_probe = None         # tests: a callable (name) run in front of every msgs_screen_compensation_* call
+
+
+class _ScreenCompensation(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, means3D, opacities, scales, rotations, cov3D_precomp, viewmatrix, raster_settings):
+        P, dev = int(means3D.shape[0]), means3D.device
+        ctx.shapes = tuple(None if t is None else t.shape for t in (means3D, opacities, scales, rotations, cov3D_precomp))
+        ctx.vm = None if viewmatrix is None or not ctx.needs_input_grad[5] else (viewmatrix.shape, viewmatrix.dtype,
+                                                                                 viewmatrix.device)
+        ctx.dev = dev
+        ctx.empty = P == 0
+        if P == 0:
+            if dev.type != "cuda":
+                raise RuntimeError("diff_gaussian_rasterization (MI355X build): tensors must live on a HIP device")
+            return torch.zeros(opacities.shape, dtype=torch.float32, device=dev)
+        call = _Call(raster_settings, means3D, None, None, opacities, scales, rotations, cov3D_precomp, None, None, None, None,
+                     None)
+        o_eff = torch.empty(P, dtype=torch.float32, device=dev)
+        if _compensation_probe is not None:
+            _compensation_probe("msgs_screen_compensation_forward")
+        with _on_device(dev):
+            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            _C.check(_C.lib.msgs_screen_compensation_forward(call.view_ref, call.g_ref, _ptr(o_eff), stream),
+                     "msgs_screen_compensation_forward")
+        ctx.call = call
+        ctx.features = None
+        _save_inputs(ctx, means3D, opacities, scales, rotations, cov3D_precomp, viewmatrix)
+        return o_eff.view(opacities.shape)
+
+    @staticmethod
+    def backward(ctx, grad_o_eff):
+        dev = ctx.dev
+        zeros = lambda s: None if s is None else torch.zeros(s, dtype=torch.float32, device=dev)
+        g_vm = None
+        if ctx.empty or grad_o_eff is None:
+            if ctx.vm is not None:
+                g_vm = torch.zeros(ctx.vm[0], dtype=ctx.vm[1], device=ctx.vm[2])
+            return tuple(zeros(s) for s in ctx.shapes) + (g_vm, None)
+        _check_saved(ctx)
+        call = ctx.call
+        P = call.P
+        new = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
+        g_opac, g_means = new(P), new(P, 3)
+        g_scales = new(P, 3) if call.scales is not None else None
+        g_rot = new(P, 4) if call.rot is not None else None
+        g_cov = new(P, 6) if call.cov is not None else None
+        dV = new(16) if ctx.vm is not None else None
+        if _compensation_probe is not None:
+            _compensation_probe("msgs_screen_compensation_backward")
+        with _on_device(dev):
+            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            scratch = _bytes(_C.lib.msgs_screen_compensation_scratch_bytes(P), dev) if dV is not None else None
+            g = _f32c(grad_o_eff).reshape(-1)
+            _C.check(_C.lib.msgs_screen_compensation_backward(
+                call.view_ref, call.g_ref, _ptr(g), _ptr(g_opac), _ptr(g_means), _ptr(g_scales), _ptr(g_rot), _ptr(g_cov),
+                _ptr(dV), _ptr(scratch), scratch.numel() if scratch is not None else 0, stream),
+                "msgs_screen_compensation_backward")
+        if dV is not None:
+            g_vm = dV.view(ctx.vm[0]).to(device=ctx.vm[2], dtype=ctx.vm[1])
+        sh = ctx.shapes
+        return (g_means.view(sh[0]), g_opac.view(sh[1]), None if g_scales is None else g_scales.view(sh[2]),
+                None if g_rot is None else g_rot.view(sh[3]), None if g_cov is None else g_cov.view(sh[4]), g_vm, None)
+
+
+def screen_compensation(means3D, opacities, raster_settings, scales=None, rotations=None, cov3D_precomp=None):
+    """o_eff = opacities * rho, in opacities' shape (float32): the opacity compensation of the antialiasing filter of
+    Mip-Splatting (upstream 3DGS's antialiasing=True, gsplat's rasterize_mode="antialiased") for the view of `raster_settings`:
+        rho = sqrt(max(0.000025, det0 / det1)),   det0 = a0 c0 - b^2,   det1 = (a0 + 0.3)(c0 + 0.3) - b^2
+    with (a0, b, c0) the projected 2-D covariance before the rasterizer's +0.3 dilation, the float32 values the rasterizer forms
+    itself.  Rendering the same model with o_eff in the place of its opacities IS the antialiased render
+    (GaussianRasterizer.with_antialiasing() does just that); a Gaussian smaller than a pixel is dimmed by the factor the dilation
+    spreads it out.  rho is 1 exactly for a Gaussian behind the near plane (view depth <= 0.2) or with non-finite inputs.
+    Differentiable in opacities, means3D, scales + rotations or cov3D_precomp (exactly one of the two, the rasterizer's rule)
+    and, when it requires grad, raster_settings.viewmatrix; projmatrix, campos and bg do not enter.  Two HIP kernels beside
+    the rasterizer's own; activated inputs only."""
+    if means3D.shape[0] > 0:        # (no Gaussian: every tensor is empty, which upstream's convention reads as "not provided")
+        scales, rotations, cov3D_precomp = _opt(scales), _opt(rotations), _opt(cov3D_precomp)
+    if ((scales is None or rotations is None) and cov3D_precomp is None) or \
+            ((scales is not None or rotations is not None) and cov3D_precomp is not None):
+        raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
+    vm = raster_settings.viewmatrix
+    vm = vm if torch.is_grad_enabled() and torch.is_tensor(vm) and vm.requires_grad else None
+    return _ScreenCompensation.apply(means3D, opacities, scales, rotations, cov3D_precomp, vm, raster_settings)
+
+
 # Contribution scores (DESIGN.md 2, M11; 4.11): what every Gaussian did to the images of one or many views, the criterion of
 # contribution-based pruning (LightGaussian's global significance, RadSplat's max contribution, Mini-Splatting's importance).
 # With w_ip = alpha_ip T_ip, the blend weight of Gaussian i in pixel p, and an optional per-pixel weight map m_p >= 0:
@@ -1647,6 +1737,31 @@ class GaussianRasterizer(nn.Module):
         self.absgrad = bool(absgrad)
         self.features = None
         self.return_distortion = False
+        self.antialiasing = False
+
+    def with_antialiasing(self, on=True):
+        """A rasterizer like this one whose forward / contributions / preprocess_only render ANTIALIASED: the opacity of every
+        Gaussian is first multiplied by rho = sqrt(max(0.000025, det0 / det1)), the compensation of Mip-Splatting's 2-D screen
+        filter (upstream 3DGS's antialiasing=True, gsplat's rasterize_mode="antialiased"; screen_compensation()), so that the
+        +0.3 dilation of the projected covariance no longer brightens Gaussians smaller than a pixel.  By definition the result
+        is the plain render of the same model with o_eff = o rho in the place of the opacity, bit for bit: return_alpha,
+        absgrad, with_features, with_distortion, depth and camera gradients and the verification mode work as without it, and
+        pixel_sizes and the multi-scale filters see o_eff.  Gradients reach opacities, means3D, scales / rotations / cov3D and
+        a viewmatrix that requires grad through rho as well.  forward() of such a module takes the plain route: the chained
+        backward of the reference's getters does not apply to o rho, their backward runs in autograd.  forward_raw() raises
+        ValueError: the raw entry applies the sigmoid inside its kernels.
+        (__init__ keeps its pinned parameters, so the flag travels on the module, as with_distortion() does.)"""
+        r = GaussianRasterizer(self.raster_settings, self.return_alpha, self.absgrad)
+        r.features = self.features
+        r.return_distortion = self.return_distortion
+        r.antialiasing = bool(on)
+        return r
+
+    def _opacities(self, means3D, opacities, scales, rotations, cov3D_precomp):
+        """the opacities the rasterizer is fed: o rho under with_antialiasing(), else the caller's"""
+        if not self.antialiasing:
+            return opacities
+        return screen_compensation(means3D, opacities, self.raster_settings, scales, rotations, cov3D_precomp)
 
     def with_distortion(self, return_distortion=True):
         """A rasterizer like this one whose forward / forward_raw also return the depth-distortion map [H,W] float32,
@@ -1664,6 +1779,7 @@ class GaussianRasterizer(nn.Module):
         r = GaussianRasterizer(self.raster_settings, self.return_alpha, self.absgrad)
         r.features = self.features
         r.return_distortion = bool(return_distortion)
+        r.antialiasing = self.antialiasing
         return r
 
     def with_features(self, features):
@@ -1680,6 +1796,7 @@ class GaussianRasterizer(nn.Module):
         r = GaussianRasterizer(self.raster_settings, self.return_alpha, self.absgrad)
         r.features = features
         r.return_distortion = self.return_distortion
+        r.antialiasing = self.antialiasing
         return r
 
     def markVisible(self, positions):
@@ -1711,6 +1828,7 @@ class GaussianRasterizer(nn.Module):
         with torch.no_grad():
             P = int(means3D.shape[0])
             dev = means3D.device
+            opacities = self._opacities(means3D, opacities, scales, rotations, cov3D_precomp)
             call = _Call(rs, means3D, None, torch.zeros(P, 3, device=dev), opacities, scales, rotations,
                          cov3D_precomp, max_pixel_sizes, min_pixel_sizes, None, None, base_mask)
             radii = torch.zeros(P, dtype=torch.int32, device=dev)
@@ -1755,6 +1873,7 @@ class GaussianRasterizer(nn.Module):
             if P > 0:
                 if shs is None and colors_precomp is None:
                     colors_precomp = torch.zeros(P, 3, dtype=torch.float32, device=dev)
+                opacities = self._opacities(means3D, opacities, scales, rotations, cov3D_precomp)
                 call = _Call(rs, means3D, _opt(shs), _opt(colors_precomp), opacities, _opt(scales), _opt(rotations),
                              _opt(cov3D_precomp), _opt(max_pixel_sizes), _opt(min_pixel_sizes), None, None, _opt(base_mask))
                 pending, _deferred.pending = getattr(_deferred, "pending", None), None      # not deferred: the replay reads D
@@ -1774,7 +1893,10 @@ class GaussianRasterizer(nn.Module):
                     return_distortion=None):
         """Opt-in fused path on raw GaussianModel parameters (not part of the reference API).  features [P,C]: as in
         with_features(); None: the module's own (with_features), if any.  return_distortion: as in with_distortion(); None:
-        the module's own."""
+        the module's own.  Not offered under with_antialiasing(): ValueError before any launch."""
+        if self.antialiasing:
+            raise ValueError("with_antialiasing() is not offered on the raw-parameter entry (forward_raw / render_fused): the "
+                             "sigmoid is applied inside its kernels; render through forward() instead")
         features = features if features is not None else self.features
         return_distortion = self.return_distortion if return_distortion is None else bool(return_distortion)
         empty = torch.Tensor([])
@@ -1798,7 +1920,10 @@ class GaussianRasterizer(nn.Module):
                 ((scales is not None or rotations is not None) and cov3D_precomp is not None):
             raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
         empty = torch.Tensor([])
-        if chain_reference_getters and torch.is_grad_enabled() and shs is not None and cov3D_precomp is None \
+        if self.antialiasing:
+            # o rho is not the sigmoid getter: straight to the plain route (no chained mode, none of its warning)
+            opacities = self._opacities(means3D, opacities, scales, rotations, cov3D_precomp)
+        elif chain_reference_getters and torch.is_grad_enabled() and shs is not None and cov3D_precomp is None \
                 and means3D.shape[0] > 0 and means3D.device.type == "cuda":
             leaves = _match_reference_getters(means3D, shs, opacities, scales, rotations)
             if leaves is None and not _warned_chain[0] and all(

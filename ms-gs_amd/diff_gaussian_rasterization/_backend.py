@@ -214,6 +214,12 @@ def _load():
     lib.msgs_distortion_forward.argtypes = [C.POINTER(View), C.c_int32, vp, sz, C.c_int64, vp, sz, vp, sz, vp, vp, vp]
     lib.msgs_distortion_backward.restype = C.c_int
     lib.msgs_distortion_backward.argtypes = [C.POINTER(View), C.c_int32, vp, sz, C.c_int64, vp, sz, vp, sz, vp, vp, vp, sz, vp]
+    lib.msgs_screen_compensation_scratch_bytes.restype = sz
+    lib.msgs_screen_compensation_scratch_bytes.argtypes = [C.c_int32]
+    lib.msgs_screen_compensation_forward.restype = C.c_int
+    lib.msgs_screen_compensation_forward.argtypes = [C.POINTER(View), C.POINTER(Gaussians), vp, vp]
+    lib.msgs_screen_compensation_backward.restype = C.c_int
+    lib.msgs_screen_compensation_backward.argtypes = [C.POINTER(View), C.POINTER(Gaussians), vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
     lib.msgs_backward_per_gaussian.restype = C.c_int
     lib.msgs_backward_per_gaussian.argtypes = [C.POINTER(View), C.POINTER(Gaussians), vp, vp, sz, vp, C.POINTER(Grads), vp]
     lib.msgs_sh_grad_from_views.restype = C.c_int
@@ -289,7 +295,8 @@ EXPORTS = ("msgs_abi_version", "msgs_error_string", "msgs_geom_bytes", "msgs_sta
            "msgs_absgrad_scratch_bytes", "msgs_absgrad",
            "msgs_contrib_scratch_bytes", "msgs_contrib_accumulate", "msgs_contrib_finish",
            "msgs_features_scratch_bytes", "msgs_features_forward", "msgs_features_backward",
-           "msgs_distortion_forward", "msgs_distortion_backward")
+           "msgs_distortion_forward", "msgs_distortion_backward",
+           "msgs_screen_compensation_forward", "msgs_screen_compensation_backward", "msgs_screen_compensation_scratch_bytes")
 
 
 def check(rc, where):

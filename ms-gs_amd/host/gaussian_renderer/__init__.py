@@ -293,3 +293,35 @@ def render_with_distortion(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, s
         out["alpha"] = outs[5]
     out["distortion"] = outs[5 + int(bool(alpha))]
     return out
+
+
+def render_with_antialiasing(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, override_color=None,
+                             filter_small=False, filter_large=False, fade_size=1.0):
+    """render() ANTIALIASED: the opacity of every Gaussian is multiplied by rho = sqrt(max(0.000025, det0 / det1)), the
+    compensation of Mip-Splatting's 2-D screen filter (upstream 3DGS's antialiasing=True, gsplat's
+    rasterize_mode="antialiased"), so that the +0.3 dilation of the projected covariance no longer brightens Gaussians smaller
+    than a pixel.  The same seven keys.  By definition the plain render of the same model with o rho in the place of the
+    opacity (diff_gaussian_rasterization.screen_compensation): "pixel_sizes" and the multi-scale filters see the compensated
+    opacity, and the gradients reach opacity, means, scales and rotations (or the covariance) through rho as well
+    (DESIGN.md 2, M14).  The getters' backward runs in autograd here: the chained mode does not apply to o rho."""
+    xyz = pc.get_xyz
+    viewspace = torch.zeros_like(xyz, requires_grad=True) + 0
+    try:
+        viewspace.retain_grad()
+    except Exception:
+        pass
+    rasterizer = GaussianRasterizer(raster_settings=_settings(
+        viewpoint_camera, pc, pipe, bg_color, scaling_modifier, filter_small, filter_large, fade_size)).with_antialiasing()
+    image, acc_pixel_size, depth, radii, pixel_sizes = rasterizer(
+        means3D=xyz,
+        means2D=viewspace,
+        opacities=pc.get_opacity,
+        max_pixel_sizes=pc.get_max_pixel_sizes,
+        min_pixel_sizes=pc.get_min_pixel_sizes,
+        occ_multiplier=pc.get_occ_multiplier,
+        dc_delta=pc.get_dc_delta,
+        base_mask=pc.get_base_mask,
+        **_colour_inputs(viewpoint_camera, pc, pipe, override_color),
+        **_shape_inputs(pc, pipe, scaling_modifier))
+    values = (image, acc_pixel_size, depth, viewspace, radii > 0, radii, pixel_sizes)
+    return dict(zip(RESULT_KEYS, values))
