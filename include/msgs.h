@@ -476,6 +476,37 @@ int msgs_distortion_backward(const msgs_view_t* view, int32_t P,
                              const float* moment, const float* dL_ddistortion,
                              void* grad_records, size_t grad_records_bytes, void* stream);
 
+/* ---- median depth and Gaussian id: the Gaussian at which a ray's transmittance falls through 1/2 (DESIGN.md SPEC M15, 4.15) -- */
+/* The blended entries i = 1..n of a pixel p are exactly the pairs the forward blended and msgs_backward* counts, in tile-list
+ * order (front to back, depth ties in index order): list position below n_contrib[p], exponent passing the sign test,
+ * alpha >= 1/255.  Transmittance is the forward's own float32 recurrence, T_1 = 1, T_{i+1} = fmaf(-T_i, alpha_i, T_i) with
+ * alpha_i = min(0.99, ...) — not a T rebuilt from final_T by division — so the maps are a deterministic function of what the
+ * render blended.  The median entry m(p) is the LAST blended entry with T_i > 0.5 (strict; the 2DGS / gsplat rule): the entry
+ * whose blending takes T to <= 1/2, or the last blended entry of a ray that never gets there.
+ *     msgs_median_depth_forward:   out_median_depth [H,W] float32 = z_m(p), the float32 view depth the depth map blends;
+ *                                  0.0f where nothing was blended.
+ *                                  out_median_id [H,W] int32 = the row of that Gaussian in the model; -1 where nothing was
+ *                                  blended.  Never differentiable.
+ * Reads what the forward of this view left in geom / binning / image_state (single pass, speculative stage 2 or its redo,
+ * depth slabs, occlusion cut-off alike).  P == 0 or num_instances == 0: the depth map is zero-filled, the id map filled with -1.
+ *     msgs_median_depth_backward:  d median_depth_p / dz_i = [i = m(p)], nothing through the selection.  With
+ * dL_dmedian_depth [H,W] float32 = G, sum_{p: median_id[p] = i} G_p is ADDED to slot 9 (dL/dz) of record i of grad_records
+ * (>= msgs_backward_scratch_bytes(P), the buffer handed to msgs_backward* as `scratch`); an id outside [0, P) adds nothing.
+ * The records must already be zero (cleared by the forward of this view, or by the caller) or hold sums that are to be
+ * included; msgs_backward* is then called with msgs_grads_t.scratch_is_clear = 1 and a non-NULL dL_ddepth (a zero map when the
+ * loss has no depth term), so that the depth variant of its per-Gaussian stage consumes slot 9: the means and, when asked, the
+ * camera receive the map's share; opacity, scales, rotations, means2D, SH and colours exactly nothing.  P == 0: launches
+ * nothing.  Neither is offered in the verification mode (MSGS_ERR_INVALID_ARG). */
+int msgs_median_depth_forward(const msgs_view_t* view, int32_t P,
+                              const void* geom, size_t geom_bytes,
+                              int64_t num_instances,
+                              const void* binning, size_t binning_bytes,
+                              const void* image_state, size_t image_bytes,
+                              float* out_median_depth, int32_t* out_median_id, void* stream);
+int msgs_median_depth_backward(const msgs_view_t* view, int32_t P,
+                               const int32_t* median_id, const float* dL_dmedian_depth,
+                               void* grad_records, size_t grad_records_bytes, void* stream);
+
 /* ---- antialiasing: the opacity compensation of the 2-D screen filter as a pre-pass (DESIGN.md SPEC M14, 4.14) ------ */
 /* The +0.3 dilation of the projected covariance (Q3) brightens every Gaussian smaller than a pixel.  Mip-Splatting's
  * compensation — upstream 3DGS's antialiasing=True, gsplat's rasterize_mode="antialiased" — scales the opacity by

@@ -980,6 +980,46 @@ int msgs_distortion_backward(const msgs_view_t* view, int32_t P, const void* geo
     return debug_sync(view, s);
 }
 
+int msgs_median_depth_forward(const msgs_view_t* view, int32_t P, const void* geom_v, size_t geom_bytes, int64_t D,
+                              const void* binning_v, size_t binning_bytes, const void* image_v, size_t image_bytes,
+                              float* out_median_depth, int32_t* out_median_id, void* stream) {
+    if (!view || P < 0 || D < 0 || view->image_width < 1 || view->image_height < 1 || !out_median_depth || !out_median_id)
+        return MSGS_ERR_INVALID_ARG;
+    if (g_deterministic.load() != 0) return MSGS_ERR_INVALID_ARG;            // not offered in the verification mode
+    const int W = view->image_width, H = view->image_height;
+    hipStream_t s = (hipStream_t)stream;
+    if (P == 0 || D == 0) {                                                  // no instance: nothing blended anywhere
+        HIP_TRY(launch_zero(out_median_depth, sizeof(float) * (size_t)W * H, s));
+        HIP_TRY(hipMemsetAsync(out_median_id, 0xFF, sizeof(int32_t) * (size_t)W * H, s));      // every id -1
+        return debug_sync(view, s);
+    }
+    if (!geom_v || !binning_v || !image_v) return MSGS_ERR_INVALID_ARG;
+    if (geom_bytes < msgs_geom_bytes(P) || binning_bytes < msgs_binning_bytes(D, W, H) || image_bytes < msgs_image_bytes(W, H))
+        return MSGS_ERR_CAPACITY;
+    const ViewParams vp = make_view_params(view);
+    const BinningLayout BL(D, vp.gx * vp.gy);
+    const ImageLayout IL(W, H);
+    const char* binning = (const char*)binning_v;
+    const char* image = (const char*)image_v;
+    HIP_TRY(launch_blend_median_depth_forward(vp, (const char*)geom_v, (const uint32_t*)(binning + BL.ids),
+                                              (const uint2*)(binning + BL.ranges), (const uint32_t*)(image + IL.n_contrib),
+                                              out_median_depth, out_median_id, s));
+    return debug_sync(view, s);
+}
+
+int msgs_median_depth_backward(const msgs_view_t* view, int32_t P, const int32_t* median_id, const float* dL_dmedian_depth,
+                               void* grad_records, size_t grad_records_bytes, void* stream) {
+    if (!view || P < 0 || view->image_width < 1 || view->image_height < 1) return MSGS_ERR_INVALID_ARG;
+    if (g_deterministic.load() != 0) return MSGS_ERR_INVALID_ARG;            // its scratch holds another layout
+    if (P == 0) return MSGS_OK;                                              // every id is -1: nothing for the records
+    if (!median_id || !dL_dmedian_depth || !grad_records || ((uintptr_t)grad_records & 7)) return MSGS_ERR_INVALID_ARG;
+    if (grad_records_bytes < msgs_backward_scratch_bytes(P)) return MSGS_ERR_CAPACITY;
+    hipStream_t s = (hipStream_t)stream;
+    const ViewParams vp = make_view_params(view);
+    HIP_TRY(launch_median_depth_backward(vp, P, median_id, dL_dmedian_depth, (grad_acc_t*)grad_records, s));
+    return debug_sync(view, s);
+}
+
 // ---- antialiasing: the opacity compensation of the 2-D screen filter, in front of K1 (SPEC M14) ----
 }  // extern "C"
 namespace {

@@ -1810,6 +1810,123 @@ __global__ __launch_bounds__(256) void blend_distortion_backward_kernel(ViewPara
 }
 
 // ---------------------------------------------------------------------------------------------
+// Median depth and Gaussian id (DESIGN.md SPEC M15, 4.15; msgs_median_depth_forward / msgs_median_depth_backward).  Over the
+// blended entries i = 1..n of a pixel (the pairs the backward counts, in tile-list order) with the FORWARD's transmittance
+// recurrence T_1 = 1, T_{i+1} = fmaf(-T_i, alpha_i, T_i), the median entry m is the last one with T_i > 0.5 (the 2DGS / gsplat
+// rule): the entry whose blending takes T to <= 0.5, or the last blended entry of a ray that never gets there.
+//     median_depth = z_m (GaussRec.r2.y, the depth the depth map blends; 0.0f where nothing was blended)
+//     median_id    = its row in the model (-1 where nothing was blended)
+// T_i exists only inside the walk, hence one more replay of the tile lists (staging and quadrant lists of the distortion
+// kernels) — but FRONT TO BACK, unlike the other replays: the selection compares T_i itself with 0.5, and only the forward's own
+// recurrence from T_1 = 1 reproduces the bits the render blended with (T_f divided back up differs in the last places, which
+// flips the entry on a ray that crosses near 0.5).  Front to back also ends early: a lane is finished once T <= 0.5 after a blend
+// or at n_contrib, a wave leaves its list and the workgroup its batch loop when all their lanes are.  While T_i > 0.5 and
+// alpha <= 0.99, T_{i+1} >= 0.005: the forward's T < 1e-4 stop rule cannot fire on an entry this walk looks at, so pair_valid
+// (position below n_contrib, sign test, alpha >= 1/255) is exactly "blended" here.
+// Gradient: d median_depth / dz_i = [i = m], nothing through the selection.  median_depth_backward_kernel adds G_p to slot 9
+// (dL/dz) of record median_id[p]; the depth variant of the per-Gaussian backward carries it to the means and the camera.
+// Opt-in: nothing of the default path calls or shares a kernel with them.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void blend_median_depth_forward_kernel(ViewParams vp, const GaussRec* __restrict__ rec,
+                                                                         const uint32_t* __restrict__ ids,
+                                                                         const uint2* __restrict__ ranges,
+                                                                         const uint32_t* __restrict__ n_contrib,
+                                                                         float* __restrict__ out_depth,
+                                                                         int32_t* __restrict__ out_id) {
+    __shared__ float4 s_r0[BATCH], s_r1[BATCH];
+    __shared__ float s_z[BATCH];
+    __shared__ uint32_t s_id[BATCH];
+    __shared__ uint16_t s_list[4][BATCH];
+    __shared__ uint32_t s_wmax[4];
+
+    const int num_tiles = vp.gx * vp.gy;
+    const int tile = swizzled_tile(blockIdx.x, num_tiles);
+    const int tx = tile % vp.gx, ty = tile / vp.gx;
+    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
+    const int px = tx * TILE + (w & 1) * 8 + (lane & 7);
+    const int py = ty * TILE + (w >> 1) * 8 + (lane >> 3);
+    const bool inside = px < vp.W && py < vp.H;
+    const float pxf = (float)px, pyf = (float)py;
+    const float tx0 = (float)(tx * TILE), ty0 = (float)(ty * TILE);
+    const uint2 range = ranges[tile];
+    const uint64_t lt_mask = (1ull << lane) - 1ull;
+    const size_t pix = (size_t)py * vp.W + px;
+
+    const uint32_t last = inside ? n_contrib[pix] : 0u;
+    float T = 1.0f, zm = 0.0f;
+    int32_t idm = -1;
+
+    const uint32_t wave_last = wave_max_u32(last);
+    if (lane == 0) s_wmax[w] = wave_last;
+    __syncthreads();
+    const uint32_t tile_last = max(max(s_wmax[0], s_wmax[1]), max(s_wmax[2], s_wmax[3]));
+
+    uint64_t open = __builtin_amdgcn_ballot_w64(last > 0u);          // lanes that have not reached their median entry yet
+
+    for (int base = 0; base < (int)tile_last; base += BATCH) {
+        if (__syncthreads_and(open == 0)) break;      // every lane of the tile is finished; the barrier also protects the batch
+        const int n = min(BATCH, (int)tile_last - base);
+        // (a finished wave stages its share of the batch and compacts nothing)
+        const uint32_t list_last = open ? wave_last : 0u;
+        const int cnt = dist_stage_and_list<true>(rec, ids, range.x, base, n, tid, w, lane, list_last, lt_mask, tx0, ty0, s_r0,
+                                                  s_r1, s_z, s_id, s_list[w]);
+        const uint16_t* lp = s_list[w];
+        for (int j = 0; j < cnt; ++j) {
+            if (open == 0) break;
+            const int e = lp[j];
+            const float4 r0 = s_r0[e], r1 = s_r1[e];
+            const float dx = r0.x - pxf, dy = r0.y - pyf;
+            const PairAlpha a = pair_alpha(r0, r1, dx, dy);
+            const uint32_t pos = (uint32_t)(base + e);
+            const uint64_t validm = pair_valid(a, pos, last, r1.z) & open;
+            const uint64_t at_end = __builtin_amdgcn_ballot_w64(pos + 1u >= last);      // nothing of this lane's behind this entry
+            if (validm != 0) {
+                const bool valid = __builtin_amdgcn_inverse_ballot_w64(validm);
+                const float alpha = fminf(0.99f, a.a_raw);
+                const float Tn = __fmaf_rn(-T, alpha, T);                               // forward_walk's test_T
+                const uint64_t crossed = __builtin_amdgcn_ballot_w64(Tn <= 0.5f);
+                zm = valid ? s_z[e] : zm;                                               // T_i > 0.5 on every open lane
+                idm = valid ? (int32_t)s_id[e] : idm;
+                T = valid ? Tn : T;
+                open &= ~(validm & crossed);
+            }
+            open &= ~at_end;
+        }
+    }
+    if (inside) { out_depth[pix] = zm; out_id[pix] = idm; }
+}
+
+// median_id [H,W], dL_dmedian [H,W] = G: ADDS sum_{p: median_id[p] = i} G_p to slot 9 of record i.  The pixel mapping of the
+// blend kernels, so that a wave holds one 8x8 block: neighbouring pixels mostly share their median Gaussian, and one lane per
+// 80-byte record is the worst shape for an atomic wave-instruction.  The lanes of a wave that hold the same id are combined first
+// (leader's id broadcast, ballot of the equal lanes, wave total of their G) and the leader issues ONE add per distinct id.
+__global__ __launch_bounds__(256) void median_depth_backward_kernel(ViewParams vp, int P, const int32_t* __restrict__ median_id,
+                                                                    const float* __restrict__ dL_dmedian,
+                                                                    grad_acc_t* __restrict__ grad_rec) {
+    const int num_tiles = vp.gx * vp.gy;
+    const int tile = swizzled_tile(blockIdx.x, num_tiles);
+    const int tx = tile % vp.gx, ty = tile / vp.gx;
+    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
+    const int px = tx * TILE + (w & 1) * 8 + (lane & 7);
+    const int py = ty * TILE + (w >> 1) * 8 + (lane >> 3);
+    const bool inside = px < vp.W && py < vp.H;
+    const size_t pix = (size_t)py * vp.W + px;
+
+    const int32_t id = inside ? median_id[pix] : -1;
+    const float g = inside ? dL_dmedian[pix] : 0.f;
+    uint64_t rem = __builtin_amdgcn_ballot_w64(id >= 0 && id < P);   // (an id outside the model adds nothing)
+    while (rem != 0) {
+        const int leader = __builtin_ctzll(rem);
+        const int32_t cur = lane_bcast(id, leader);
+        const bool mine = id == cur;
+        const uint64_t same = __builtin_amdgcn_ballot_w64(mine);
+        const float tot = wave_allreduce_sum(mine ? g : 0.f);
+        if (lane == leader) unsafeAtomicAdd(grad_rec + (size_t)cur * GRAD_REC_FLOATS + 9, (grad_acc_t)tot);
+        rem &= ~same;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // statistics for the algorithmic-bytes formula: D_trav = sum_tiles max_pixels n_contrib, V = #radii>0
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void tile_stats_kernel(ViewParams vp, const uint32_t* __restrict__ n_contrib,
@@ -2150,6 +2267,23 @@ hipError_t launch_blend_distortion_backward(const ViewParams& vp, const char* ge
     if (tiles <= 0) return hipSuccess;
     hipLaunchKernelGGL(blend_distortion_backward_kernel, dim3(tiles), dim3(256), 0, s, vp, reinterpret_cast<const GaussRec*>(geom),
                        ids, ranges, final_T, n_contrib, moment, dL_ddist, grad_rec);
+    return hipGetLastError();
+}
+
+// msgs_median_depth_forward / _backward (SPEC M15): one launch each, one workgroup per tile
+hipError_t launch_blend_median_depth_forward(const ViewParams& vp, const char* geom, const uint32_t* ids, const uint2* ranges,
+                                             const uint32_t* n_contrib, float* out_depth, int32_t* out_id, hipStream_t s) {
+    const int tiles = vp.gx * vp.gy;
+    if (tiles <= 0) return hipSuccess;
+    hipLaunchKernelGGL(blend_median_depth_forward_kernel, dim3(tiles), dim3(256), 0, s, vp, reinterpret_cast<const GaussRec*>(geom),
+                       ids, ranges, n_contrib, out_depth, out_id);
+    return hipGetLastError();
+}
+hipError_t launch_median_depth_backward(const ViewParams& vp, int P, const int32_t* median_id, const float* dL_dmedian,
+                                        grad_acc_t* grad_rec, hipStream_t s) {
+    const int tiles = vp.gx * vp.gy;
+    if (tiles <= 0 || P <= 0) return hipSuccess;
+    hipLaunchKernelGGL(median_depth_backward_kernel, dim3(tiles), dim3(256), 0, s, vp, P, median_id, dL_dmedian, grad_rec);
     return hipGetLastError();
 }
 

@@ -813,6 +813,12 @@ hipError_t launch_screen_compensation_forward(const ViewParams& vp, const msgs_g
 hipError_t launch_screen_compensation_backward(const ViewParams& vp, const msgs_gaussians_t& g, const float* dL_do_eff,
                                                float* dL_dopacity, float* dL_dmeans3D, float* dL_dscales, float* dL_drotations,
                                                float* dL_dcov3D, float* dL_dV, double* rows, hipStream_t s);
+// msgs_median_depth_* (SPEC M15): the median-depth map [H,W] and the id map of its Gaussians (front-to-back replay with early
+// exit); the backward adds dL/dmedian_depth of every pixel to slot 9 (dL/dz) of its Gaussian's record
+hipError_t launch_blend_median_depth_forward(const ViewParams& vp, const char* geom, const uint32_t* ids, const uint2* ranges,
+                                             const uint32_t* n_contrib, float* out_depth, int32_t* out_id, hipStream_t s);
+hipError_t launch_median_depth_backward(const ViewParams& vp, int P, const int32_t* median_id, const float* dL_dmedian,
+                                        grad_acc_t* grad_rec, hipStream_t s);
 // heaviest-first launch order of the one-wave-per-tile backward from the forward's per-tile traversal lengths
 hipError_t launch_tile_order(const ViewParams& vp, const uint32_t* tile_last, uint32_t* tile_order, hipStream_t s);
 hipError_t launch_blend_lane_stats(const ViewParams& vp, const char* geom, const uint32_t* ids, const uint2* ranges,

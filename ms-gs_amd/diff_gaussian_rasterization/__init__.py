@@ -333,6 +333,8 @@ def _note_camera(ctx, camera, behind=0):
 #   [_AbsgradMarker]                   absgrad=True: a marker holding a weak reference to the caller's means2D
 #   [_DISTORTION]                      return_distortion=True: a marker — the Function returns the distortion map [H,W] behind
 #                                      alpha and in front of the feature map
+#   [_MEDIAN]                          return_median_depth=True: a marker — the Function returns median_depth [H,W] float32 and
+#                                      median_id [H,W] int32 behind the distortion map and in front of the feature map (M15)
 #   [_FEATURES, features]              features given: a marker and the [P,C] tensor, always LAST — the marker tells the tensor
 #                                      from bg; the Function returns the feature map [C,H,W] as its last output
 # A call that asks for none of the new things passes exactly what it passed before them.
@@ -401,13 +403,32 @@ class _DistortionMarker:
 _DISTORTION = _DistortionMarker()
 
 
-def _extra_inputs(rs, return_alpha=False, absgrad=False, means2D=None, features=None, model=None, return_distortion=False):
+# Median depth and Gaussian id (4.15).  return_median_depth=True adds two outputs behind the distortion map:
+# median_depth [H,W] float32, the view depth of the Gaussian at which the ray's transmittance falls through 1/2 (the last blended
+# entry with T_i > 0.5, T by the forward's own recurrence), and median_id [H,W] int32, that Gaussian's row (-1 / 0.0 where nothing
+# was blended; never differentiable).  msgs_median_depth_forward: a front-to-back replay of the tile lists behind the forward.
+# A loss on median_depth makes the backward first run msgs_median_depth_backward, which adds every pixel's gradient to slot 9
+# (dL/dz) of its Gaussian's record, then today's depth-variant backward with scratch_is_clear = 1 on top of them.  A loss that
+# does not use the map takes today's backward unchanged.
+class _MedianMarker:
+    def __repr__(self):
+        return "return_median_depth"
+
+
+_MEDIAN = _MedianMarker()
+
+
+def _extra_inputs(rs, return_alpha=False, absgrad=False, means2D=None, features=None, model=None, return_distortion=False,
+                  return_median_depth=False):
     """model: the call's means3D / xyz (its rows and device check `features`)"""
     if absgrad and _C.lib.msgs_get_deterministic():
         raise ValueError("absgrad=True is not offered in the verification mode (set_deterministic): that mode checks the "
                          "gradients, it does not train")
     if return_distortion and _C.lib.msgs_get_deterministic():
         raise ValueError("return_distortion=True is not offered in the verification mode (set_deterministic): that mode "
+                         "checks the gradients of the reference's outputs")
+    if return_median_depth and _C.lib.msgs_get_deterministic():
+        raise ValueError("return_median_depth=True is not offered in the verification mode (set_deterministic): that mode "
                          "checks the gradients of the reference's outputs")
     if features is not None:
         features = _check_features(features, int(model.shape[0]), model.device)
@@ -420,6 +441,8 @@ def _extra_inputs(rs, return_alpha=False, absgrad=False, means2D=None, features=
         extra = tuple(extra) + (_AbsgradMarker(means2D),)
     if return_distortion:
         extra = tuple(extra) + (_DISTORTION,)
+    if return_median_depth:
+        extra = tuple(extra) + (_MEDIAN,)
     if features is not None:
         extra = tuple(extra) + (_FEATURES, features)
     return extra
@@ -428,8 +451,8 @@ def _extra_inputs(rs, return_alpha=False, absgrad=False, means2D=None, features=
 def _note_extra(ctx, extra):
     """forward: split the trailing inputs; leaves ctx.camera (_note_camera), ctx.bg ((shape, dtype, device) when the
     background wants a gradient, else None), ctx.n_extra_tail (inputs behind the camera's), ctx.absgrad (the marker or None)
-    ctx.features (the caller's tensor or None), ctx.feat (its contiguous float32 form), ctx.distortion (return_distortion) and
-    returns return_alpha"""
+    ctx.features (the caller's tensor or None), ctx.feat (its contiguous float32 form), ctx.distortion (return_distortion),
+    ctx.median (return_median_depth) and returns return_alpha"""
     ctx.features = ctx.feat = None
     n_feat = 0
     if len(extra) >= 2 and extra[-2] is _FEATURES:
@@ -437,6 +460,9 @@ def _note_extra(ctx, extra):
         ctx.feat = _f32c(extra[-1].detach())
         ctx.features_want = bool(ctx.needs_input_grad[-1])
         extra = extra[:-2]
+    ctx.median = bool(extra) and extra[-1] is _MEDIAN
+    n_feat += int(ctx.median)
+    extra = extra[:-1] if ctx.median else extra
     ctx.distortion = bool(extra) and extra[-1] is _DISTORTION
     n_feat += int(ctx.distortion)                              # (from here on: the inputs behind the absgrad marker)
     extra = extra[:-1] if ctx.distortion else extra
@@ -489,19 +515,22 @@ def _bg_grad(ctx, view_ref, image, dL, W, H, dev, stream):
 
 def _extra_grads(ctx, g_cam, g_bg):
     """gradients of the trailing inputs in their order: camera, bg, the alpha marker, the absgrad marker, the distortion marker,
-    the features marker and dL/dfeatures (in the tensor's shape and dtype; None when the loss did not use the feature map)"""
+    the median marker, the features marker and dL/dfeatures (in the tensor's shape and dtype; None when the loss did not use the feature map)"""
     g_feat = ()
     if ctx.features is not None:
         g, ctx.g_features = getattr(ctx, "g_features", None), None
         g_feat = (None, g.view(ctx.features.shape).to(ctx.features.dtype) if g is not None and ctx.features_want else None)
     return tuple(g_cam) + ((g_bg,) if ctx.has_bg else ()) + ((None,) if ctx.return_alpha else ()) + \
-        ((None,) if ctx.absgrad is not None else ()) + ((None,) if ctx.distortion else ()) + g_feat
+        ((None,) if ctx.absgrad is not None else ()) + ((None,) if ctx.distortion else ()) + \
+        ((None,) if ctx.median else ()) + g_feat
 
 
 def _split_grad_tail(ctx, tail):
-    """the gradients of the outputs behind the reference's five: (grad_alpha, grad_distortion, grad_features)"""
+    """the gradients of the outputs behind the reference's five: (grad_alpha, grad_distortion, grad_median, grad_features);
+    grad_median is that of median_depth — median_id, the output behind it, is not differentiable"""
+    k_med = int(ctx.return_alpha) + int(ctx.distortion)
     return (tail[0] if ctx.return_alpha else None), (tail[int(ctx.return_alpha)] if ctx.distortion else None), \
-        (tail[-1] if ctx.features is not None else None)
+        (tail[k_med] if ctx.median else None), (tail[-1] if ctx.features is not None else None)
 
 
 _features_probe = None             # tests: a callable (name) run in front of every msgs_features_* call
@@ -582,6 +611,46 @@ def _distortion_backward(ctx, call, geom, binning, image, D, grad_distortion, dL
                                              binning.numel() if binning is not None else 0, _ptr(image), image.numel(),
                                              _ptr(ctx.dist_moment), _ptr(_f32c(grad_distortion)), _ptr(scratch), scratch.numel(),
                                              stream), "msgs_distortion_backward")
+    if dLd is None:
+        dLd = torch.zeros(call.H, call.W, dtype=torch.float32, device=dev)
+    return dLd, 1
+
+
+_median_probe = None               # tests: a callable (name) run in front of every msgs_median_depth_* call
+
+
+def _median_depth_forward(ctx, call, state):
+    """(median_depth [H,W] float32, median_id [H,W] int32) of a return_median_depth=True call: msgs_median_depth_forward on the
+    current stream, behind the forward that left `state`; the id map stays on ctx for the backward.  A deferred forward is
+    resolved first (the replay needs the instance count): correct, at the price of that view's overlap."""
+    geom, binning, image, D = _resolve(state)
+    dev, P = call.device, call.P
+    if _median_probe is not None:
+        _median_probe("msgs_median_depth_forward")
+    with _on_device(dev):
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        out = torch.empty(call.H, call.W, dtype=torch.float32, device=dev)
+        ids = torch.empty(call.H, call.W, dtype=torch.int32, device=dev)
+        _C.check(_C.lib.msgs_median_depth_forward(call.view_ref, P, _ptr(geom), geom.numel(), D, _ptr(binning),
+                                                  binning.numel() if binning is not None else 0, _ptr(image), image.numel(),
+                                                  _ptr(out), _ptr(ids), stream), "msgs_median_depth_forward")
+    ctx.median_id = ids
+    return out, ids
+
+
+def _median_depth_backward(ctx, call, D, grad_median, dLd, scratch, is_clear, dev, stream):
+    """In front of _run_backward, when the loss used median_depth: every pixel's gradient ADDED to slot 9 (dL/dz) of the record
+    of its median Gaussian in `scratch` — cleared here unless it is the buffer the forward cleared or already holds the sums of
+    the feature / distortion maps.  Returns (dL/ddepth to hand on, scratch_is_clear to hand on): the depth variant of the
+    backward consumes slot 9, so a loss without a depth term passes a zero map (fmaf(z, 0, g) is exact: the colour sums keep
+    their bits)."""
+    if not is_clear:
+        scratch.zero_()
+    if D > 0:                                                   # (no instance: every id is -1, nothing to add)
+        if _median_probe is not None:
+            _median_probe("msgs_median_depth_backward")
+        _C.check(_C.lib.msgs_median_depth_backward(call.view_ref, call.P, _ptr(ctx.median_id), _ptr(_f32c(grad_median)),
+                                                   _ptr(scratch), scratch.numel(), stream), "msgs_median_depth_backward")
     if dLd is None:
         dLd = torch.zeros(call.H, call.W, dtype=torch.float32, device=dev)
     return dLd, 1
@@ -1025,16 +1094,21 @@ def _forward_impl(call, grad_rec=None, backward_follows=False, want_alpha=False)
 
 def _forward_tail(ctx, call, state, outs, geometry=(0, 1, 4, 5, 6)):
     """the end of every autograd forward: what its backward finds on ctx; returns the five outputs (six with return_alpha, and
-    the distortion map, then the feature map behind them when asked for).  geometry: the positions of the inputs whose gradient the per-
+    the distortion map, then median_depth and median_id, then the feature map behind them when asked for).  geometry: the positions of the inputs whose gradient the per-
     Gaussian backward forms from the records' geometry slots (the camera's follow from ctx.camera)."""
     color, acc_ps, depth, radii, pixel_sizes = outs[:5]
     ctx.call, ctx.state, ctx.radii = call, state, radii
     if ctx.distortion:
         outs = tuple(outs) + (_distortion_forward(ctx, call, state),)
+    non_diff = (acc_ps, radii, pixel_sizes)
+    if ctx.median:
+        median_depth, median_id = _median_depth_forward(ctx, call, state)
+        outs = tuple(outs) + (median_depth, median_id)
+        non_diff += (median_id,)
     if ctx.features is not None:
         ctx.features_geom = any(ctx.needs_input_grad[k] for k in geometry) or any(m is not None for m in ctx.camera)
         outs = tuple(outs) + (_features_forward(ctx, call, state),)
-    ctx.mark_non_differentiable(acc_ps, radii, pixel_sizes)     # depth and alpha are differentiable (DESIGN.md 2, M6, M9)
+    ctx.mark_non_differentiable(*non_diff)                      # depth and alpha are differentiable (DESIGN.md 2, M6, M9)
     ctx.set_materialize_grads(False)      # grad_depth / grad_alpha are None unless the loss used that map: then today's path
     return tuple(outs)
 
@@ -1060,11 +1134,15 @@ class _RasterizeGaussians(torch.autograd.Function):
             ctx.HW = (H, W, int(bool(rs.debug)))
             outs = (color, torch.zeros(H, W, device=dev), torch.zeros(H, W, device=dev),
                     torch.zeros(0, dtype=torch.int32, device=dev), torch.zeros(0, device=dev))
-            ctx.mark_non_differentiable(outs[1], *outs[3:])     # (depth stays differentiable: zero gradients)
+            non_diff = (outs[1],) + outs[3:]                    # (depth stays differentiable: zero gradients)
             if want_alpha:                                      # (nothing blended: alpha 0, zero gradients)
                 outs = outs + (torch.zeros(H, W, device=dev),)
             if ctx.distortion:                                  # (nothing blended: no pair, zero gradients)
                 outs = outs + (torch.zeros(H, W, device=dev),)
+            if ctx.median:                                      # (nothing blended: depth 0, id -1, zero gradients)
+                outs = outs + (torch.zeros(H, W, device=dev), torch.full((H, W), -1, dtype=torch.int32, device=dev))
+                non_diff += (outs[-1],)
+            ctx.mark_non_differentiable(*non_diff)
             if ctx.features is not None:                        # (nothing blended: a zero map, zero gradients)
                 outs = outs + (torch.zeros(int(ctx.features.shape[1]), H, W, device=dev),)
             ctx.set_materialize_grads(False)
@@ -1080,7 +1158,7 @@ class _RasterizeGaussians(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_color, grad_acc_ps, grad_depth, grad_radii, grad_pixel_sizes, *grad_tail):
-        grad_alpha, grad_distortion, grad_features = _split_grad_tail(ctx, grad_tail)
+        grad_alpha, grad_distortion, grad_median, grad_features = _split_grad_tail(ctx, grad_tail)
         if ctx.empty:
             cam = tuple(None if m is None else torch.zeros(m[0], dtype=m[1], device=m[2]) for m in ctx.camera)
             g_bg = None
@@ -1117,7 +1195,8 @@ class _RasterizeGaussians(torch.autograd.Function):
             g_rot = torch.empty(P, 4, dtype=torch.float32, device=dev) if call.rot is not None else None
             g_cov = torch.empty(P, 6, dtype=torch.float32, device=dev) if call.cov is not None else None
             dLd = _f32c(grad_depth) if grad_depth is not None else None
-            scratch, is_clear = _take_backward_scratch(ctx, P, D, dev, dLd is not None or grad_distortion is not None)
+            scratch, is_clear = _take_backward_scratch(ctx, P, D, dev, dLd is not None or grad_distortion is not None or
+                                                       grad_median is not None)
             dLd_loss = dLd                                      # (what the loss itself sent to the depth map: absgrad's input)
             grads = _C.Grads(_ptr(g_means3D), _ptr(g_means2D), _ptr(g_sh), _ptr(g_col), _ptr(g_opac),
                              _ptr(g_scales), _ptr(g_rot), _ptr(g_cov), None, None, None, is_clear)
@@ -1129,6 +1208,9 @@ class _RasterizeGaussians(torch.autograd.Function):
             if grad_distortion is not None:
                 dLd, grads.scratch_is_clear = _distortion_backward(ctx, call, geom, binning, image, D, grad_distortion, dLd, scratch,
                                                                    grads.scratch_is_clear, dev, stream)
+            if grad_median is not None:
+                dLd, grads.scratch_is_clear = _median_depth_backward(ctx, call, D, grad_median, dLd, scratch,
+                                                                     grads.scratch_is_clear, dev, stream)
             _run_backward(lib, call, ctx, geom, binning, image, D, dL, dLd, dLa, scratch, grads, stream, cam)
             g_bg = _bg_grad(ctx, call.view_ref, image, dL, call.W, call.H, dev, stream) if ctx.bg is not None else None
             if ctx.absgrad is not None:
@@ -1342,7 +1424,7 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_color, grad_acc_ps, grad_depth, grad_radii, grad_pixel_sizes, *grad_tail):
-        grad_alpha, grad_distortion, grad_features = _split_grad_tail(ctx, grad_tail)
+        grad_alpha, grad_distortion, grad_median, grad_features = _split_grad_tail(ctx, grad_tail)
         _check_saved(ctx)
         call = ctx.call
         if grad_color is None:
@@ -1384,7 +1466,8 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
                     g_dc, g_rest = _grad_out(kdc, dc_shape, dev), _grad_out(krest, rest_shape, dev)
                 g_opac, g_scal, g_rot = _grad_out(kop, op_shape, dev), _grad_out(ksc, (P, 3), dev), _grad_out(krot, (P, 4), dev)
             dLd = _f32c(grad_depth) if grad_depth is not None else None
-            scratch, is_clear = _take_backward_scratch(ctx, P, D, dev, dLd is not None or grad_distortion is not None)
+            scratch, is_clear = _take_backward_scratch(ctx, P, D, dev, dLd is not None or grad_distortion is not None or
+                                                       grad_median is not None)
             dLd_loss = dLd                                      # (what the loss itself sent to the depth map: absgrad's input)
             grads = _C.Grads(_ptr(g_xyz), _ptr(g_m2), None, _ptr(factor), _ptr(g_opac), _ptr(g_scal), _ptr(g_rot), None,
                              _ptr(g_dc), _ptr(g_rest),
@@ -1398,6 +1481,9 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
             if grad_distortion is not None:
                 dLd, grads.scratch_is_clear = _distortion_backward(ctx, call, geom, binning, image, D, grad_distortion, dLd, scratch,
                                                                    grads.scratch_is_clear, dev, stream)
+            if grad_median is not None:
+                dLd, grads.scratch_is_clear = _median_depth_backward(ctx, call, D, grad_median, dLd, scratch,
+                                                                     grads.scratch_is_clear, dev, stream)
             _run_backward(lib, call, ctx, geom, binning, image, D, dL, dLd, dLa, scratch, grads, stream, cam)
             if adam is not None:
                 step_opt.commit_step_in_backward(ctx.leaves)
@@ -1524,13 +1610,18 @@ def sh_grad_from_views(means3D, gathered, n_views, sh_degree, scale, out_dc, out
 
 def rasterize_gaussians_raw(xyz, means2D, features_dc, features_rest, opacity_raw, scaling_raw, rotation_raw,
                             max_pixel_sizes, min_pixel_sizes, occ_multiplier, dc_delta, base_mask, raster_settings,
-                            features=None, return_distortion=False, absgrad=False, return_alpha=False):
+                            features=None, return_median_depth=False, return_distortion=False, absgrad=False,
+                            return_alpha=False):
     """return_alpha=True: a sixth output, the alpha map [H,W] (1 - final transmittance), differentiable
     absgrad=True: every backward also assigns means2D.absgrad.
     features [P,C]: one more output at the END, the feature map [C,H,W], differentiable.
     return_distortion=True: one more output behind alpha and in front of the feature map, the depth-distortion map [H,W],
-    differentiable.  All four by keyword."""
-    extra = _extra_inputs(raster_settings, return_alpha, absgrad, means2D, features, xyz, return_distortion)
+    differentiable.
+    return_median_depth=True: two more outputs behind the distortion map and in front of the feature map, median_depth [H,W]
+    float32 (differentiable w.r.t. the means and the camera) and median_id [H,W] int32.  All five by
+    keyword."""
+    extra = _extra_inputs(raster_settings, return_alpha, absgrad, means2D, features, xyz, return_distortion,
+                          return_median_depth)
     _note_grad_mode()
     return _RasterizeGaussiansRaw.apply(xyz, means2D, features_dc, features_rest, opacity_raw, scaling_raw,
                                         rotation_raw, max_pixel_sizes, min_pixel_sizes, occ_multiplier, dc_delta,
@@ -1540,13 +1631,18 @@ def rasterize_gaussians_raw(xyz, means2D, features_dc, features_rest, opacity_ra
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                         max_pixel_sizes, min_pixel_sizes, occ_multiplier, dc_delta, base_mask, raster_settings,
-                        features=None, return_distortion=False, absgrad=False, return_alpha=False):
+                        features=None, return_median_depth=False, return_distortion=False, absgrad=False,
+                        return_alpha=False):
     """return_alpha=True: a sixth output, the alpha map [H,W] (1 - final transmittance), differentiable
     absgrad=True: every backward also assigns means2D.absgrad.
     features [P,C]: one more output at the END, the feature map [C,H,W], differentiable.
     return_distortion=True: one more output behind alpha and in front of the feature map, the depth-distortion map [H,W],
-    differentiable.  All four by keyword."""
-    extra = _extra_inputs(raster_settings, return_alpha, absgrad, means2D, features, means3D, return_distortion)
+    differentiable.
+    return_median_depth=True: two more outputs behind the distortion map and in front of the feature map, median_depth [H,W]
+    float32 (differentiable w.r.t. the means and the camera) and median_id [H,W] int32.  All five by
+    keyword."""
+    extra = _extra_inputs(raster_settings, return_alpha, absgrad, means2D, features, means3D, return_distortion,
+                          return_median_depth)
     _note_grad_mode()
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
                                      cov3Ds_precomp, max_pixel_sizes, min_pixel_sizes, occ_multiplier, dc_delta,
@@ -1737,6 +1833,7 @@ class GaussianRasterizer(nn.Module):
         self.absgrad = bool(absgrad)
         self.features = None
         self.return_distortion = False
+        self.return_median_depth = False
         self.antialiasing = False
 
     def with_antialiasing(self, on=True):
@@ -1754,6 +1851,7 @@ class GaussianRasterizer(nn.Module):
         r = GaussianRasterizer(self.raster_settings, self.return_alpha, self.absgrad)
         r.features = self.features
         r.return_distortion = self.return_distortion
+        r.return_median_depth = self.return_median_depth
         r.antialiasing = bool(on)
         return r
 
@@ -1779,6 +1877,33 @@ class GaussianRasterizer(nn.Module):
         r = GaussianRasterizer(self.raster_settings, self.return_alpha, self.absgrad)
         r.features = self.features
         r.return_distortion = bool(return_distortion)
+        r.return_median_depth = self.return_median_depth
+        r.antialiasing = self.antialiasing
+        return r
+
+    def with_median_depth(self, on=True):
+        """A rasterizer like this one whose forward / forward_raw also return two maps, behind alpha and the distortion map and
+        in front of the feature map:
+            median_depth [H,W] float32: the view depth (the z the depth map blends) of the Gaussian at which the ray's
+                                        transmittance falls through 1/2; 0.0 where nothing was blended
+            median_id    [H,W] int32:   the row of that Gaussian in the model; -1 where nothing was blended
+        Over the blended entries i = 1..n of a pixel (the pairs the backward counts, in tile-list order, front to back) with the
+        forward's own recurrence T_1 = 1, T_{i+1} = fmaf(-T_i, alpha_i, T_i), the median entry is the LAST one with T_i > 0.5
+        (the 2DGS / gsplat rule): the entry whose blending takes T to <= 1/2, or the last blended entry of a ray that never
+        gets there.  Unlike the blended depth map it is the depth of one Gaussian — no smear across silhouettes, no drift when
+        coarse and fine Gaussians stack on a surface — and median_id says which: picking, labels[median_id] lookups, per-pixel
+        level ids.  median_depth is differentiable with d median_depth_p / dz_i = [i = median entry of p] and nothing through
+        the selection, as in 2DGS: a loss on it sends gradients to means3D and, when asked, to the camera; opacity, scales,
+        rotations, means2D, SH and colours receive exactly nothing.  median_id is never differentiable.  A loss that ignores
+        the map runs today's backward unchanged.  With absgrad=True the statistic means2D.absgrad does not include this map's
+        share: it has none.  Inside deferred_forward such a call resolves its own view before the replay: correct, but that
+        view's overlap is lost.  Not offered in the verification mode (set_deterministic): ValueError before any launch
+        (DESIGN.md 2, M15).
+        (__init__ keeps its pinned parameters, so the flag travels on the module, as with_distortion() does.)"""
+        r = GaussianRasterizer(self.raster_settings, self.return_alpha, self.absgrad)
+        r.features = self.features
+        r.return_distortion = self.return_distortion
+        r.return_median_depth = bool(on)
         r.antialiasing = self.antialiasing
         return r
 
@@ -1796,6 +1921,7 @@ class GaussianRasterizer(nn.Module):
         r = GaussianRasterizer(self.raster_settings, self.return_alpha, self.absgrad)
         r.features = features
         r.return_distortion = self.return_distortion
+        r.return_median_depth = self.return_median_depth
         r.antialiasing = self.antialiasing
         return r
 
@@ -1890,28 +2016,29 @@ class GaussianRasterizer(nn.Module):
 
     def forward_raw(self, xyz, means2D, features_dc, features_rest, opacity_raw, scaling_raw, rotation_raw,
                     max_pixel_sizes=None, min_pixel_sizes=None, occ_multiplier=None, dc_delta=None, base_mask=None, features=None,
-                    return_distortion=None):
+                    return_distortion=None, return_median_depth=None):
         """Opt-in fused path on raw GaussianModel parameters (not part of the reference API).  features [P,C]: as in
         with_features(); None: the module's own (with_features), if any.  return_distortion: as in with_distortion(); None:
-        the module's own.  Not offered under with_antialiasing(): ValueError before any launch."""
+        the module's own.  return_median_depth: as in with_median_depth(); None: the module's own.  Not offered under with_antialiasing(): ValueError before any launch."""
         if self.antialiasing:
             raise ValueError("with_antialiasing() is not offered on the raw-parameter entry (forward_raw / render_fused): the "
                              "sigmoid is applied inside its kernels; render through forward() instead")
         features = features if features is not None else self.features
         return_distortion = self.return_distortion if return_distortion is None else bool(return_distortion)
+        return_median_depth = self.return_median_depth if return_median_depth is None else bool(return_median_depth)
         empty = torch.Tensor([])
         o = lambda t: t if t is not None else empty
         return rasterize_gaussians_raw(xyz, means2D, features_dc, features_rest, opacity_raw, scaling_raw,
                                        rotation_raw, o(max_pixel_sizes), o(min_pixel_sizes), o(occ_multiplier),
                                        o(dc_delta), o(base_mask), self.raster_settings, absgrad=self.absgrad,
                                        return_alpha=self.return_alpha, features=features,
-                                       return_distortion=return_distortion)
+                                       return_distortion=return_distortion, return_median_depth=return_median_depth)
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
                 cov3D_precomp=None, max_pixel_sizes=None, min_pixel_sizes=None, occ_multiplier=None,
                 dc_delta=None, base_mask=None):
-        """The reference's 13 parameters.  Feature channels and the distortion map travel on the module:
-        with_features(features)(...), with_distortion()(...)."""
+        """The reference's 13 parameters.  Feature channels, the distortion map and the median-depth maps travel on the module:
+        with_features(features)(...), with_distortion()(...), with_median_depth()(...)."""
         rs = self.raster_settings
         features = self.features
         if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
@@ -1942,7 +2069,8 @@ class GaussianRasterizer(nn.Module):
                     means3D, means2D, *leaves, shs.detach() if _chain_reads_cat else empty, opacities.detach(), scales.detach(),
                     rotations.detach(),
                     o(max_pixel_sizes), o(min_pixel_sizes), o(occ_multiplier), o(dc_delta), o(base_mask), rs,
-                    *_extra_inputs(rs, self.return_alpha, self.absgrad, means2D, features, means3D, self.return_distortion))
+                    *_extra_inputs(rs, self.return_alpha, self.absgrad, means2D, features, means3D, self.return_distortion,
+                                   self.return_median_depth))
         return rasterize_gaussians(
             means3D, means2D,
             shs if shs is not None else empty,
@@ -1957,4 +2085,4 @@ class GaussianRasterizer(nn.Module):
             dc_delta if dc_delta is not None else empty,
             base_mask if base_mask is not None else empty,
             rs, absgrad=self.absgrad, return_alpha=self.return_alpha, features=features,
-            return_distortion=self.return_distortion)
+            return_distortion=self.return_distortion, return_median_depth=self.return_median_depth)

@@ -214,6 +214,10 @@ def _load():
     lib.msgs_distortion_forward.argtypes = [C.POINTER(View), C.c_int32, vp, sz, C.c_int64, vp, sz, vp, sz, vp, vp, vp]
     lib.msgs_distortion_backward.restype = C.c_int
     lib.msgs_distortion_backward.argtypes = [C.POINTER(View), C.c_int32, vp, sz, C.c_int64, vp, sz, vp, sz, vp, vp, vp, sz, vp]
+    lib.msgs_median_depth_forward.restype = C.c_int
+    lib.msgs_median_depth_forward.argtypes = [C.POINTER(View), C.c_int32, vp, sz, C.c_int64, vp, sz, vp, sz, vp, vp, vp]
+    lib.msgs_median_depth_backward.restype = C.c_int
+    lib.msgs_median_depth_backward.argtypes = [C.POINTER(View), C.c_int32, vp, vp, vp, sz, vp]
     lib.msgs_screen_compensation_scratch_bytes.restype = sz
     lib.msgs_screen_compensation_scratch_bytes.argtypes = [C.c_int32]
     lib.msgs_screen_compensation_forward.restype = C.c_int
@@ -296,6 +300,7 @@ EXPORTS = ("msgs_abi_version", "msgs_error_string", "msgs_geom_bytes", "msgs_sta
            "msgs_contrib_scratch_bytes", "msgs_contrib_accumulate", "msgs_contrib_finish",
            "msgs_features_scratch_bytes", "msgs_features_forward", "msgs_features_backward",
            "msgs_distortion_forward", "msgs_distortion_backward",
+           "msgs_median_depth_forward", "msgs_median_depth_backward",
            "msgs_screen_compensation_forward", "msgs_screen_compensation_backward", "msgs_screen_compensation_scratch_bytes")
 
 

@@ -325,3 +325,55 @@ def render_with_antialiasing(viewpoint_camera, pc, pipe, bg_color: torch.Tensor,
         **_shape_inputs(pc, pipe, scaling_modifier))
     values = (image, acc_pixel_size, depth, viewspace, radii > 0, radii, pixel_sizes)
     return dict(zip(RESULT_KEYS, values))
+
+
+def render_with_median_depth(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, override_color=None,
+                             filter_small=False, filter_large=False, fade_size=1.0, alpha=False, fused=False):
+    """render() — or, with fused=True, render_fused() (then without override_color) — plus the median depth of every ray and
+    the Gaussian it belongs to: the seven keys of RESULT_KEYS, "alpha" (render_with_alpha) with alpha=True, and
+        "median_depth" [H,W] float32: the view depth of the Gaussian at which the ray's transmittance falls through 1/2 (the
+                                      last blended Gaussian with T > 0.5; the last blended one on a ray that never gets there);
+                                      0 where nothing was blended
+        "median_id"    [H,W] int32:   that Gaussian's row in the model, -1 where nothing was blended
+    Unlike "depth" (the blended sum of z alpha T) it is the depth of one Gaussian: the input of TSDF fusion, of depth
+    supervision and of depth-normal consistency (2DGS, RaDe-GS), and it stays on the occluding Gaussian when the level of a
+    multi-scale model changes.  median_depth is differentiable towards the means and the camera only, with nothing through the
+    selection; median_id is an index map (labels[id.clamp_min(0)] masked by id >= 0).  Image, maps and their gradients are
+    those of the call without it, bit for bit."""
+    settings = _settings(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, filter_small, filter_large, fade_size)
+    rasterizer = GaussianRasterizer(raster_settings=settings, return_alpha=alpha).with_median_depth()
+    if fused:
+        if override_color is not None:
+            raise ValueError("render_with_median_depth: fused=True cannot be combined with override_color")
+        xyz = pc._xyz
+        viewspace = torch.empty_like(xyz, requires_grad=True)
+        outs = rasterizer.forward_raw(
+            xyz, viewspace, pc._features_dc, pc._features_rest, pc._opacity, pc._scaling, pc._rotation,
+            max_pixel_sizes=pc.get_max_pixel_sizes, min_pixel_sizes=pc.get_min_pixel_sizes,
+            occ_multiplier=pc.get_occ_multiplier, dc_delta=pc.get_dc_delta, base_mask=pc.get_base_mask)
+    else:
+        xyz = pc.get_xyz
+        viewspace = torch.zeros_like(xyz, requires_grad=True) + 0
+        try:
+            viewspace.retain_grad()
+        except Exception:
+            pass
+        outs = rasterizer(
+            means3D=xyz,
+            means2D=viewspace,
+            opacities=pc.get_opacity,
+            max_pixel_sizes=pc.get_max_pixel_sizes,
+            min_pixel_sizes=pc.get_min_pixel_sizes,
+            occ_multiplier=pc.get_occ_multiplier,
+            dc_delta=pc.get_dc_delta,
+            base_mask=pc.get_base_mask,
+            **_colour_inputs(viewpoint_camera, pc, pipe, override_color),
+            **_shape_inputs(pc, pipe, scaling_modifier))
+    image, acc_pixel_size, depth, radii, pixel_sizes = outs[:5]
+    values = (image, acc_pixel_size, depth, viewspace, radii > 0, radii, pixel_sizes)
+    out = dict(zip(RESULT_KEYS, values))
+    if alpha:
+        out["alpha"] = outs[5]
+    k = 5 + int(bool(alpha))
+    out["median_depth"], out["median_id"] = outs[k], outs[k + 1]
+    return out
