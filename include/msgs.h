@@ -632,6 +632,16 @@ int msgs_set_blend_granularity(int32_t mode);
  * 0xFFFFFFFF = a block stayed open)}.  (The instances removed = the instance count of the same view with the pass switched
  * off minus the one with it on.)  Synchronises `stream`; not re-entrant (a diagnostic). */
 int msgs_set_occlusion(int32_t on);
+/* Which depth sort the forward runs (process-wide switch; both give the same arrays bit for bit, ties in index order):
+ * 0 (default) = by P — up to 1.5 M Gaussians the bucket path (a histogram of the keys over fine depth bins balances 255 buckets,
+ * one compacting pass distributes the keys, one workgroup per bucket finishes it in LDS: five launches), above that the four
+ * 8-bit LSD passes (eight launches); 1 = always the LSD passes; 2 = the bucket path for every P it can run at (up to 2 097 152).
+ * The choice never depends on device data.  Initial value from MSGS_DEPTH_SORT.  Returns the previous value.
+ * msgs_depth_sort_stats reads what the sort did for the forward that last wrote `geom`: out_host[3] = {1 when the bucket path
+ * ran, buckets that outgrew one workgroup's LDS (8192 pairs) and were sorted in chunks through HBM — correct, only slow; it
+ * takes thousands of Gaussians within 1/512 octave of depth —, V = Gaussians that stayed in the sort}.  Synchronises `stream`. */
+int msgs_set_depth_sort(int32_t mode);
+int msgs_depth_sort_stats(const void* geom, size_t geom_bytes, int32_t P, int64_t* out_host, void* stream);
 /* What the last forward that RETURNED ITS INSTANCE COUNT on the calling host thread (msgs_forward, msgs_forward_stage1,
  * msgs_forward_finish) learned besides the count — the words travel with it, no extra device access: out_host[0] = cover
  * candidates of its occlusion pass (0 when the pass did not run), out_host[1] = 1 when the pass closed at least one block.

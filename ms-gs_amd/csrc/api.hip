@@ -119,6 +119,7 @@ int msgs_get_deterministic(void) { return g_deterministic.load(); }
 int msgs_set_backward_generation(int32_t gen) { return set_backward_generation(gen); }
 int msgs_set_blend_granularity(int32_t mode) { return set_blend_granularity(mode); }
 int msgs_set_occlusion(int32_t on) { return set_occlusion(on); }
+int msgs_set_depth_sort(int32_t mode) { return set_depth_sort(mode); }
 
 }  // extern "C"
 
@@ -234,7 +235,10 @@ int forward_stage1_launch(const msgs_view_t* view, const msgs_gaussians_t* g, in
     // K1 also clears the depth sort's group-sum table (saves a fill launch) and the header of the occlusion cut-off
     // (enabled = 0, no candidates: what the emit reads when the pass does not run)
     ZeroJob zj1{nullptr, 0, (uint32_t*)(geom + GL.slab_hdr), (GL.occ_hdr - GL.slab_hdr) / 4 + sizeof(OccHeader) / 4 + 2 * (size_t)OCC_BUCKETS};
-    const bool sort1_prezeroed = radix_sort_zero_region(P, 0, 32, scratch + SL.sort, &zj1.p0, &zj1.n0);
+    // depth sort: the bucket path or the LSD passes, from P and the process-wide switch alone (sort.hip, depth_sort_uses_buckets)
+    const bool sort1_buckets = depth_sort_uses_buckets(P);
+    const bool sort1_prezeroed = sort1_buckets ? depth_sort_zero_region(P, scratch + SL.sort, &zj1.p0, &zj1.n0)
+                                               : radix_sort_zero_region(P, 0, 32, scratch + SL.sort, &zj1.p0, &zj1.n0);
     // exact per-tile occlusion cut-off (occlusion.hip): on unless switched off
     const bool occlusion = get_occlusion() != 0;
     uint32_t* heavy_list = occlusion ? (uint32_t*)(scratch + SL.heavy_list) : nullptr;
@@ -260,9 +264,14 @@ int forward_stage1_launch(const msgs_view_t* view, const msgs_gaussians_t* g, in
     uint32_t* heavy_q_word = spec ? (uint32_t*)((char*)spec->buf.scratch2 + Stage2Scratch(spec->capacity).heavy_q) : nullptr;
 
     tm.begin(MSGS_K_DEPTH_SORT);
-    HIP_TRY(radix_sort_pairs((uint32_t*)(geom + GL.key), nullptr, (uint32_t*)(geom + GL.skey),
-                             (uint32_t*)(geom + GL.order), P, 0, 32, scratch + SL.sort, s, sort1_prezeroed,
-                             (uint32_t*)(geom + GL.nvalid)));
+    if (sort1_buckets)   // (its two info words sit behind the SlabHeader, in the range K1 cleared: zero on the LSD path)
+        HIP_TRY(depth_sort_buckets((const uint32_t*)(geom + GL.key), (uint32_t*)(geom + GL.skey), (uint32_t*)(geom + GL.order), P,
+                                   scratch + SL.sort, s, sort1_prezeroed, (uint32_t*)(geom + GL.nvalid),
+                                   (uint32_t*)(geom + GL.slab_hdr + DEPTH_SORT_INFO_OFFSET)));
+    else
+        HIP_TRY(radix_sort_pairs((uint32_t*)(geom + GL.key), nullptr, (uint32_t*)(geom + GL.skey),
+                                 (uint32_t*)(geom + GL.order), P, 0, 32, scratch + SL.sort, s, sort1_prezeroed,
+                                 (uint32_t*)(geom + GL.nvalid)));
     tm.end(MSGS_K_DEPTH_SORT);
     if ((rc = debug_sync(view, s))) return rc;
     tm.begin(MSGS_K_SCAN);
@@ -1246,6 +1255,22 @@ int msgs_slab_stats(const void* geom_v, size_t geom_bytes, int32_t P, int64_t* o
     out_host[3] = h.n_open;
     out_host[4] = (int64_t)h.total_b;
     out_host[5] = h.pad0;          // 1: slab B outgrew its buffers (never observed)
+    return MSGS_OK;
+}
+
+int msgs_depth_sort_stats(const void* geom_v, size_t geom_bytes, int32_t P, int64_t* out_host, void* stream) {
+    if (!geom_v || !out_host || P <= 0) return MSGS_ERR_INVALID_ARG;
+    if (geom_bytes < msgs_geom_bytes(P)) return MSGS_ERR_CAPACITY;
+    static_assert(sizeof(SlabHeader) <= DEPTH_SORT_INFO_OFFSET && DEPTH_SORT_INFO_OFFSET + 8 <= 256, "inside the slab header's slot");
+    const GeomLayout GL(P);
+    uint32_t info[2], V;
+    hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(hipMemcpyAsync(info, (const char*)geom_v + GL.slab_hdr + DEPTH_SORT_INFO_OFFSET, sizeof(info), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&V, (const char*)geom_v + GL.nvalid, sizeof(V), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    out_host[0] = info[0];
+    out_host[1] = info[1];
+    out_host[2] = V;
     return MSGS_OK;
 }
 

@@ -202,13 +202,68 @@ struct SortScratch {
     }
 };
 
+// Depth sort, bucket path (sort.hip): one balanced most-significant pass into DEPTH_BUCKETS buckets, then every
+// bucket is finished by one workgroup inside LDS.  The buckets are balanced from a histogram of the keys over fine depth bins:
+// a monotone function of the key, 2^(23 - DEPTH_BIN_SHIFT) = 512 bins per octave of depth from 0.1875 (below the near plane at
+// 0.2) to the largest finite float, clamped at both ends (keys below / above — negative floats, NaNs — share the end bins).
+constexpr int DEPTH_BIN_SHIFT = 14;
+constexpr uint32_t DEPTH_BIN_LO = 0x3E400000u >> DEPTH_BIN_SHIFT;      // bin of depth 0.1875
+constexpr int DEPTH_COARSE = 261;                                      // groups of 256 fine bins
+constexpr int DEPTH_BINS = DEPTH_COARSE * 256;                         // 66 816
+static_assert(DEPTH_BIN_LO + DEPTH_BINS - 1 == (0x7F7FFFFFu >> DEPTH_BIN_SHIFT), "the top bin is the one of FLT_MAX");
+constexpr int DEPTH_BUCKETS = 255;                                     // bucket of bin b = floor(exclusive_prefix[b] * 255 / V)
+constexpr int DEPTH_LDS_THREADS = 1024;
+constexpr int DEPTH_LDS_ITEMS = 8;
+constexpr int DEPTH_LDS_CAP = DEPTH_LDS_THREADS * DEPTH_LDS_ITEMS;     // pairs one workgroup sorts in LDS (64 KB + 16 KB of counters)
+// Host rule: the bucket path up to this many Gaussians.  A bucket holds at most V / 255 + (largest bin) pairs; at 1.5 M that is
+// 5883 + the largest bin, which stays below the cap for bins of up to 2300 keys (profiles/depth_bucket_sort_notes.md has the bench
+// scenes' figures).  A larger bucket is still sorted correctly (in chunks through HBM), only slowly.
+constexpr int64_t DEPTH_BUCKET_MAX_P = 1'500'000;
+// the forward's two info words of the bucket path, in GeomLayout::slab_hdr's slot behind the SlabHeader (K1 clears the slot)
+constexpr size_t DEPTH_SORT_INFO_OFFSET = 64;
+
+__host__ __device__ inline uint32_t depth_bin(uint32_t key) {
+    uint32_t b = key >> DEPTH_BIN_SHIFT;
+    b = b < DEPTH_BIN_LO ? DEPTH_BIN_LO : b;
+    b -= DEPTH_BIN_LO;
+    return b < (uint32_t)DEPTH_BINS ? b : (uint32_t)DEPTH_BINS - 1u;
+}
+
+// The fine histogram is built without global atomics on the bins (1 M of them on a few thousand hot addresses cost 164 us,
+// profiles/depth_bucket_sort_notes.md): every workgroup of depth_hist_kernel counts DEPTH_HIST_KEYS keys into a private
+// histogram of ALL bins in LDS — 16-bit counters, 131 KB — and writes it out as its own slice; the splitter adds the slices up.
+constexpr int DEPTH_HIST_KEYS = 32768;                                 // keys per workgroup: below 2^16, so no counter overflows
+constexpr int DEPTH_HIST_MAX_BLOCKS = 64;
+constexpr int64_t DEPTH_BUCKET_HARD_MAX = (int64_t)DEPTH_HIST_KEYS * DEPTH_HIST_MAX_BLOCKS;   // 2 097 152: the largest n the path sorts
+__host__ __device__ inline int depth_hist_blocks(int64_t n) {
+    const int64_t b = (n + DEPTH_HIST_KEYS - 1) / DEPTH_HIST_KEYS;
+    return b < 1 ? 1 : (b > DEPTH_HIST_MAX_BLOCKS ? DEPTH_HIST_MAX_BLOCKS : (int)b);
+}
+
+// scratch of one depth sort over n pairs: the LSD sort's (first, so that either path can run on it) and, directly behind its
+// group sums, the tables of the bucket path — the sums per group of 256 bins (zero at entry, one range with the group sums), the
+// bin -> bucket bytes, the bucket bases and two spare words, the histogram slices (uint16 [blocks][DEPTH_BINS])
+struct DepthSortScratch {
+    size_t sort, coarse, map, bases, slices, total;
+    __host__ __device__ explicit DepthSortScratch(int64_t n) {
+        size_t o = 0;
+        sort = o;   o = align256(o + SortScratch(n).total);
+        coarse = o; o = align256(o + 4 * (size_t)DEPTH_COARSE);
+        map = o;    o = align256(o + (size_t)DEPTH_BINS);
+        bases = o;  o = align256(o + 4 * (size_t)(DEPTH_BUCKETS + 2 + 2));
+        slices = o; o = align256(o + 2 * (size_t)DEPTH_BINS * depth_hist_blocks(n));     // (monotone in n: 64 slices from 2 M on)
+        total = o;
+    }
+    __host__ __device__ size_t zero_end() const { return coarse + 4 * (size_t)DEPTH_COARSE; }
+};
+
 struct Stage1Scratch {
     size_t sort, scan_partials, total_out, heavy_list, heavy_count, heavy_blk, occ_cand, total;
     __host__ __device__ explicit Stage1Scratch(int64_t P) {
         size_t o = 0;
         const size_t Pn = (size_t)(P > 0 ? P : 1);
         const size_t waves = 4 * ((Pn + 255) / 256);          // wave slots of preprocess_kernel's grid
-        sort = o;          o = align256(o + SortScratch(P).total);
+        sort = o;          o = align256(o + DepthSortScratch(P).total);
         scan_partials = o; o = align256(o + 8 * (size_t)(scan_blocks(P > 0 ? P : 1) + 2));
         total_out = o;     o = align256(o + 64);    // {scan total} and the collected status block
         // occlusion cut-off: cover candidates as preprocess_kernel leaves them (per wave: up to 64 Gaussian ids + a count),
@@ -659,6 +714,22 @@ hipError_t radix_sort_pairs(uint32_t* keys_in, uint32_t* vals_in, uint32_t* keys
 bool radix_sort_keys16_ok(int64_t n, int begin_bit, int end_bit);
 bool radix_sort_zero_region(int64_t n, int begin_bit, int end_bit, char* scratch, uint32_t** ptr, size_t* words);
 bool radix_sort_supports_device_count(int64_t n, int begin_bit, int end_bit);
+
+// The forward's depth sort on the bucket path: the contract of radix_sort_pairs(keys_in, nullptr, keys_out, vals_out, n, 0, 32,
+// ..., n_valid_dev) — keys equal to 0xFFFFFFFF are dropped, the V survivors land in keys_out / vals_out by key ascending, ties in
+// index order, *n_valid_dev = V, keys_in is left as it was — in five launches: fine histogram of the keys' depth bins, splitter
+// (bin -> bucket table, bucket bases, V), the compacting bucket pass, one workgroup per bucket that finishes it in LDS.
+// scratch: DepthSortScratch(n).  pre_zeroed: the words of depth_sort_zero_region are zero already.
+// info (optional, two device words): [0] = 1 (this path ran), [1] = buckets above DEPTH_LDS_CAP pairs (sorted in chunks, slowly).
+// Inputs above DEPTH_BUCKET_HARD_MAX pairs are refused: depth_sort_uses_buckets never chooses them.
+hipError_t depth_sort_buckets(const uint32_t* keys_in, uint32_t* keys_out, uint32_t* vals_out, int64_t n,
+                              char* scratch /* DepthSortScratch(n) */, hipStream_t s, bool pre_zeroed, uint32_t* n_valid_dev,
+                              uint32_t* info = nullptr);
+bool depth_sort_zero_region(int64_t n, char* scratch, uint32_t** ptr, size_t* words);
+// the host rule, from n and the process-wide switch alone (include/msgs.h, msgs_set_depth_sort)
+bool depth_sort_uses_buckets(int64_t n);
+int set_depth_sort(int mode);             // 0 = by n (default), 1 = always the LSD sort, 2 = buckets wherever they can run
+int get_depth_sort();
 
 // out[r] = exclusive sum of in[gather ? gather[r] : r]; *total (device, u64) = grand total
 // n_ptr (optional, device word): the number of elements actually scanned, <= n (n sizes the grids)

@@ -19,6 +19,8 @@
 #include "msgs_internal.h"
 
 #include <algorithm>
+#include <atomic>
+#include <cstdlib>
 
 namespace msgs {
 
@@ -190,6 +192,18 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_apply_fused_kernel(const ui
 // ---------------------------------------------------------------------------------------------
 // radix pass
 // ---------------------------------------------------------------------------------------------
+// The digit of a key: bits [shift, shift + 8) for every LSD pass; for the bucket pass of the depth sort (below) the bucket of
+// the key's depth bin, read from the table the splitter kernel wrote.  Same kernels either way.
+struct ShiftDigit {
+    int shift;
+    uint32_t mask;
+    __device__ __forceinline__ uint32_t operator()(uint32_t k) const { return (k >> shift) & mask; }
+};
+struct BucketDigit {
+    const uint8_t* __restrict__ map;
+    __device__ __forceinline__ uint32_t operator()(uint32_t k) const { return map[depth_bin(k)]; }
+};
+
 // Element layout inside a block's chunk: wave w owns [w*64*ITEMS, (w+1)*64*ITEMS); in round r lane l
 // handles element w*64*ITEMS + r*64 + l.  Waves, rounds and lanes are therefore all in key order.
 template <int ITEMS = SORT_ITEMS>
@@ -206,9 +220,9 @@ __device__ __forceinline__ int64_t elem_index(int64_t chunk_base, int w, int r, 
 // (n_ptr) and run over the survivors only: their grids are still sized for the upper bound, surplus blocks leave at once.
 // KeyT: uint32_t, or uint16_t for the tile sort whenever the tile ids (and the sentinel) fit 16 bits — 6 instead of 8 bytes per
 // pair and pass; the keys sit in uint16 arrays in HBM and are widened in registers / LDS.
-template <int ITEMS, bool DROP = false, typename KeyT = uint32_t>
+template <int ITEMS, bool DROP = false, typename KeyT = uint32_t, typename Digit = ShiftDigit>
 __global__ __launch_bounds__(SORT_THREADS) void radix_hist_kernel(const KeyT* __restrict__ keys, int64_t n,
-                                                                  int shift, uint32_t mask, int64_t nblocks,
+                                                                  Digit dg, int64_t nblocks,
                                                                   uint32_t* __restrict__ hist,
                                                                   uint32_t* __restrict__ gsum, int gsize, int ngroups,
                                                                   const uint32_t* __restrict__ n_ptr = nullptr) {
@@ -232,7 +246,7 @@ __global__ __launch_bounds__(SORT_THREADS) void radix_hist_kernel(const KeyT* __
 #pragma unroll
             for (int j = 0; j < KPV; ++j) {
                 const uint32_t k = sizeof(KeyT) == 4 ? w4[j] : ((w4[j >> 1] >> ((j & 1) * 16)) & 0xFFFFu);
-                if (!DROP || k != 0xFFFFFFFFu) atomicAdd(&s_hist[(k >> shift) & mask], 1u);
+                if (!DROP || k != 0xFFFFFFFFu) atomicAdd(&s_hist[dg(k)], 1u);
             }
         }
     } else {
@@ -241,7 +255,7 @@ __global__ __launch_bounds__(SORT_THREADS) void radix_hist_kernel(const KeyT* __
             const int64_t i = elem_index<ITEMS>(chunk_base, w, r, lane);
             if (i < n) {
                 const uint32_t k = (uint32_t)keys[i];
-                if (!DROP || k != 0xFFFFFFFFu) atomicAdd(&s_hist[(k >> shift) & mask], 1u);
+                if (!DROP || k != 0xFFFFFFFFu) atomicAdd(&s_hist[dg(k)], 1u);
             }
         }
     }
@@ -300,12 +314,12 @@ __global__ __launch_bounds__(256) void group_scan_kernel(uint32_t* __restrict__ 
     }
 }
 
-template <int ITEMS, bool DROP = false, typename KeyT = uint32_t>
+template <int ITEMS, bool DROP = false, typename KeyT = uint32_t, typename Digit = ShiftDigit>
 __global__ __launch_bounds__(SORT_THREADS) void radix_scatter_kernel(const KeyT* __restrict__ keys_in,
                                                                      const uint32_t* __restrict__ vals_in,
                                                                      KeyT* __restrict__ keys_out,
                                                                      uint32_t* __restrict__ vals_out, int64_t n,
-                                                                     int shift, uint32_t mask, int64_t nblocks,
+                                                                     Digit dg, int64_t nblocks,
                                                                      const uint32_t* __restrict__ hist_scanned,
                                                                      const uint32_t* __restrict__ gsum, int gsize,
                                                                      int ngroups, bool gsum_is_base = false,
@@ -331,7 +345,7 @@ __global__ __launch_bounds__(SORT_THREADS) void radix_scatter_kernel(const KeyT*
         key[r] = i < n ? (uint32_t)keys_in[i] : 0xFFFFFFFFu;
         const bool valid = i < n && (!DROP || key[r] != 0xFFFFFFFFu);      // DROP: not-rendered Gaussians leave the sort here
         val[r] = valid ? (vals_in ? vals_in[i] : (uint32_t)i) : 0u;
-        const uint32_t d = (key[r] >> shift) & mask;
+        const uint32_t d = dg(key[r]);
         // match-any over the 8 digit bits
         uint64_t peers = __ballot(valid);
 #pragma unroll
@@ -393,7 +407,7 @@ __global__ __launch_bounds__(SORT_THREADS) void radix_scatter_kernel(const KeyT*
     for (int r = 0; r < ITEMS; ++r) {
         const int64_t i = elem_index<ITEMS>(chunk_base, w, r, lane);
         if (i < n && (!DROP || key[r] != 0xFFFFFFFFu)) {
-            const uint32_t lp = s_cnt[w][(key[r] >> shift) & mask] + rank[r];
+            const uint32_t lp = s_cnt[w][dg(key[r])] + rank[r];
             s_key[lp] = key[r];
             s_val[lp] = val[r];
         }
@@ -405,7 +419,7 @@ __global__ __launch_bounds__(SORT_THREADS) void radix_scatter_kernel(const KeyT*
         const int j = r * SORT_THREADS + threadIdx.x;
         if (j < nvalid) {
             const uint32_t k = s_key[j];
-            const uint32_t pos = (uint32_t)j + s_delta[(k >> shift) & mask];
+            const uint32_t pos = (uint32_t)j + s_delta[dg(k)];
             keys_out[pos] = (KeyT)k;
             vals_out[pos] = s_val[j];
         }
@@ -499,19 +513,20 @@ void launch_pass(const KeyT* src_k, const uint32_t* src_v, KeyT* dst_k, uint32_t
                  const GroupGeom& G, uint32_t* hist, uint32_t* gs, bool drop, const uint32_t* n_ptr, uint32_t* n_out,
                  hipStream_t s) {
     const dim3 grid((unsigned)G.nb), block(SORT_THREADS);
+    const ShiftDigit dg{shift, mask};
     if (drop) {
-        hipLaunchKernelGGL((radix_hist_kernel<ITEMS, true, KeyT>), grid, block, 0, s, src_k, n, shift, mask, G.nb, hist, gs, G.gsize,
+        hipLaunchKernelGGL((radix_hist_kernel<ITEMS, true, KeyT>), grid, block, 0, s, src_k, n, dg, G.nb, hist, gs, G.gsize,
                            G.ngroups, (const uint32_t*)nullptr);
-        hipLaunchKernelGGL((radix_scatter_kernel<ITEMS, true, KeyT>), grid, block, 0, s, src_k, src_v, dst_k, dst_v, n, shift,
-                           mask, G.nb, hist, gs, G.gsize, G.ngroups, false, (const uint32_t*)nullptr, n_out);
+        hipLaunchKernelGGL((radix_scatter_kernel<ITEMS, true, KeyT>), grid, block, 0, s, src_k, src_v, dst_k, dst_v, n, dg,
+                           G.nb, hist, gs, G.gsize, G.ngroups, false, (const uint32_t*)nullptr, n_out);
         return;
     }
-    hipLaunchKernelGGL((radix_hist_kernel<ITEMS, false, KeyT>), grid, block, 0, s, src_k, n, shift, mask, G.nb, hist, gs, G.gsize,
+    hipLaunchKernelGGL((radix_hist_kernel<ITEMS, false, KeyT>), grid, block, 0, s, src_k, n, dg, G.nb, hist, gs, G.gsize,
                        G.ngroups, n_ptr);
     if (G.scanned)
         hipLaunchKernelGGL(group_scan_kernel, dim3((unsigned)G.ngroups + 1), dim3(256), 0, s, gs, G.ngroups, hist, G.gsize, G.nb, n_ptr,
                            SORT_THREADS * ITEMS);
-    hipLaunchKernelGGL((radix_scatter_kernel<ITEMS, false, KeyT>), grid, block, 0, s, src_k, src_v, dst_k, dst_v, n, shift, mask,
+    hipLaunchKernelGGL((radix_scatter_kernel<ITEMS, false, KeyT>), grid, block, 0, s, src_k, src_v, dst_k, dst_v, n, dg,
                        G.nb, hist, gs, G.gsize, G.ngroups, G.scanned, n_ptr, (uint32_t*)nullptr);
 }
 
@@ -586,6 +601,374 @@ hipError_t radix_sort_pairs(uint32_t* keys_in, uint32_t* vals_in, uint32_t* keys
     if (n_valid_dev && !compact) hipLaunchKernelGGL(store_u32_kernel, dim3(1), dim3(1), 0, s, n_valid_dev, (uint32_t)n);
     return sort_passes<uint32_t>(keys_in, vals_in, keys_out, vals_out, n, passes, begin_bit, end_bit, G, keys_alt, vals_alt, hist,
                                  gsum_all, compact, n_valid_dev, n_dev, s);
+}
+
+// ---------------------------------------------------------------------------------------------
+// depth sort, bucket path (msgs_internal.h, DepthSortScratch): fine histogram -> splitter -> bucket pass -> one workgroup per bucket
+// ---------------------------------------------------------------------------------------------
+namespace {
+
+constexpr int DEPTH_LDS_WAVES = DEPTH_LDS_THREADS / 64;
+constexpr int DEPTH_HIST_THREADS = 1024;
+constexpr int DEPTH_HIST_WORDS = DEPTH_BINS / 2;     // 16-bit counters, two per LDS word
+static_assert(DEPTH_HIST_KEYS < 65536 && DEPTH_BINS % 2 == 0 && DEPTH_HIST_KEYS % 4 == 0, "16-bit counters in pairs; uint4 loads");
+
+// Counts of the surviving keys per fine depth bin: every workgroup counts its DEPTH_HIST_KEYS keys into a histogram of ALL bins
+// in LDS (16-bit counters) and writes it out whole as slice blockIdx.x — no atomics on the bins, nothing to clear beforehand.
+// The sums per group of 256 bins (coarse[], zero at entry) take one atomic per workgroup and non-empty group.
+__global__ __launch_bounds__(DEPTH_HIST_THREADS) void depth_hist_kernel(const uint32_t* __restrict__ keys, int64_t n,
+                                                                        uint32_t* __restrict__ slices, uint32_t* __restrict__ coarse) {
+    __shared__ __attribute__((aligned(16))) uint32_t s_h[DEPTH_HIST_WORDS];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int64_t first = (int64_t)blockIdx.x * DEPTH_HIST_KEYS;
+    const int64_t end = first + DEPTH_HIST_KEYS < n ? first + DEPTH_HIST_KEYS : n;
+    const bool aligned = (reinterpret_cast<uintptr_t>(keys) & 15) == 0;
+    constexpr int ROUNDS = DEPTH_HIST_KEYS / (4 * DEPTH_HIST_THREADS);
+    static_assert(ROUNDS * 4 * DEPTH_HIST_THREADS == DEPTH_HIST_KEYS, "whole rounds of uint4 loads");
+    uint32_t k4[ROUNDS][4];
+    // every load of the thread is in flight before the first count (a loop of dependent load -> count rounds took 20 us)
+#pragma unroll
+    for (int r = 0; r < ROUNDS; ++r) {
+        const int64_t i0 = first + 4 * ((int64_t)r * DEPTH_HIST_THREADS + tid);
+        if (aligned && i0 + 4 <= end) {
+            const uint4 v = *reinterpret_cast<const uint4*>(keys + i0);
+            k4[r][0] = v.x; k4[r][1] = v.y; k4[r][2] = v.z; k4[r][3] = v.w;
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) k4[r][j] = i0 + j < end ? keys[i0 + j] : 0xFFFFFFFFu;
+        }
+    }
+    for (int q = tid; q < DEPTH_HIST_WORDS / 4; q += DEPTH_HIST_THREADS) reinterpret_cast<uint4*>(s_h)[q] = make_uint4(0u, 0u, 0u, 0u);
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < ROUNDS; ++r) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (k4[r][j] != 0xFFFFFFFFu) {
+                const uint32_t b = depth_bin(k4[r][j]);
+                atomicAdd(&s_h[b >> 1], 1u << ((b & 1u) * 16));
+            }
+        }
+    }
+    __syncthreads();
+    // four words = eight bins per thread and round; 32 lanes cover one group of 256 bins.  The rounds are independent (unrolled):
+    // a loop of load -> six dependent shuffles -> atomic per round, one word per thread, took 13 us of this kernel's 20
+    uint4* out = reinterpret_cast<uint4*>(slices + (size_t)blockIdx.x * DEPTH_HIST_WORDS);
+    constexpr int QUADS = DEPTH_HIST_WORDS / 4;
+    static_assert(QUADS * 4 == DEPTH_HIST_WORDS && QUADS % 32 == 0, "whole uint4s; whole groups per half wave");
+#pragma unroll
+    for (int q0 = 0; q0 < QUADS; q0 += DEPTH_HIST_THREADS) {               // (every wave runs every round: the shuffles below)
+        const int q = q0 + tid;
+        const uint4 v = q < QUADS ? reinterpret_cast<const uint4*>(s_h)[q] : make_uint4(0u, 0u, 0u, 0u);
+        if (q < QUADS) out[q] = v;
+        uint32_t c = (v.x & 0xFFFFu) + (v.x >> 16) + (v.y & 0xFFFFu) + (v.y >> 16) + (v.z & 0xFFFFu) + (v.z >> 16) + (v.w & 0xFFFFu) + (v.w >> 16);
+        for (int off = 16; off > 0; off >>= 1) c += (uint32_t)__shfl_xor((int)c, off);
+        if ((lane & 31) == 0 && c) atomicAdd(&coarse[q >> 5], c);
+    }
+}
+
+// One block per group of 256 fine bins: the bins' counts (the slices added up), the exclusive prefix of every bin (the group sums
+// in front + a block scan), bucket of bin b = floor(prefix[b] * 255 / V) — monotone in b, so a bucket is a run of bins and holds
+// at most V / 255 + (its last bin) keys — the bin -> bucket bytes, and bases[k] = keys in buckets below k for k = 0 .. 256, each
+// written by the one bin at which the bucket number passes k.  Block 0 publishes V and the info words.
+__global__ __launch_bounds__(256) void depth_split_kernel(const uint16_t* __restrict__ slices, int nslices,
+                                                          const uint32_t* __restrict__ coarse, uint8_t* __restrict__ map,
+                                                          uint32_t* __restrict__ bases, uint32_t* __restrict__ n_valid,
+                                                          uint32_t* __restrict__ info) {
+    __shared__ uint32_t s_wave[4], s_last[5];
+    __shared__ uint64_t s_sum[4];
+    const int t = threadIdx.x, j = blockIdx.x;
+    static_assert(DEPTH_COARSE <= 512 && DEPTH_HIST_MAX_BLOCKS <= 64, "two group sums per thread; one slice per lane of wave 0");
+    const int b = j * 256 + t;
+    uint32_t cnt = 0;
+#pragma unroll 16
+    for (int k = 0; k < nslices; ++k) cnt += slices[(size_t)k * DEPTH_BINS + b];
+    // the count of the bin in front of this group: one slice per lane of wave 0
+    uint32_t front = (t < nslices && j > 0) ? slices[(size_t)t * DEPTH_BINS + b - t - 1] : 0u;
+    for (int off = 32; off > 0; off >>= 1) front += (uint32_t)__shfl_xor((int)front, off);
+    if ((t & 63) == 63) s_last[(t >> 6) + 1] = cnt;
+    if (t == 0) s_last[0] = front;
+    const uint32_t c0 = t < DEPTH_COARSE ? coarse[t] : 0u;
+    const uint32_t c1 = t + 256 < DEPTH_COARSE ? coarse[t + 256] : 0u;
+    const uint32_t mine_before = (t < j ? c0 : 0u) + (t + 256 < j ? c1 : 0u);
+    // both sums in one reduction: keys in front of this group (high word) and all keys (low word); each stays below 2^31
+    const uint64_t both = block_sum_u64(((uint64_t)mine_before << 32) + ((uint64_t)c0 + c1), s_sum);
+    const uint32_t before = (uint32_t)(both >> 32), V = (uint32_t)both;
+    uint32_t total;
+    const uint32_t excl = block_exclusive_scan(cnt, s_wave, &total) + before;
+    const int bucket = V ? (int)((uint64_t)excl * DEPTH_BUCKETS / V) : 0;
+    map[b] = (uint8_t)bucket;
+    // the bucket of the bin in front, from its prefix excl - count[b - 1]
+    uint32_t cnt_prev = (uint32_t)__shfl_up((int)cnt, 1);
+    if ((t & 63) == 0) cnt_prev = s_last[t >> 6];                  // wave 0: the bin in front of the group
+    const int prev = b == 0 ? -1 : (V ? (int)((uint64_t)(excl - cnt_prev) * DEPTH_BUCKETS / V) : 0);
+    for (int k = prev + 1; k <= bucket; ++k) bases[k] = excl;
+    if (b == DEPTH_BINS - 1)
+        for (int k = bucket + 1; k <= DEPTH_BUCKETS + 1; ++k) bases[k] = V;
+    if (b == 0) {
+        if (n_valid) *n_valid = V;
+        info[0] = 1u;
+        info[1] = 0u;
+    }
+}
+
+// Ranks the keys a workgroup of DEPTH_LDS_THREADS holds in registers by the digit (key >> shift) & 255, stably.  Element e =
+// w * 64 * R + r * 64 + lane (wave w, round r < R) is valid when e < nloc; waves, rounds and lanes are in element order.  On return
+// s_cnt[w][d] is where the keys of (wave w, digit d) start in the digit-major order of the nloc elements, rank[r] the place of
+// the key among them, and s_dcount[d] the elements of digit d.  The same match-any ranking as radix_scatter_kernel.
+__device__ __forceinline__ void lds_rank(const uint32_t (&key)[DEPTH_LDS_ITEMS], uint32_t (&rank)[DEPTH_LDS_ITEMS], int R, int nloc,
+                                         int shift, uint32_t (*s_cnt)[256], uint32_t* s_wsum, uint32_t* s_dcount) {
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    for (int k = tid; k < DEPTH_LDS_WAVES * 256; k += DEPTH_LDS_THREADS) (&s_cnt[0][0])[k] = 0;
+    __syncthreads();
+    const uint64_t lt_mask = (1ull << lane) - 1ull;
+#pragma unroll
+    for (int r = 0; r < DEPTH_LDS_ITEMS; ++r) {
+        if (r < R) {                                              // (uniform over the workgroup)
+            const bool valid = w * 64 * R + r * 64 + lane < nloc;
+            const uint32_t d = shift < 32 ? (key[r] >> shift) & 255u : 0u;
+            uint64_t peers = __ballot(valid);
+#pragma unroll
+            for (int b = 0; b < 8; ++b) {
+                const uint64_t m = __ballot((d >> b) & 1u);
+                peers &= ((d >> b) & 1u) ? m : ~m;
+            }
+            const uint32_t prev = s_cnt[w][d];
+            const uint32_t before = (uint32_t)__popcll(peers & lt_mask);
+            rank[r] = prev + before;
+            if (valid && before == 0) s_cnt[w][d] = prev + (uint32_t)__popcll(peers);
+        }
+    }
+    __syncthreads();
+    uint32_t c[DEPTH_LDS_WAVES], ltot = 0;
+    if (tid < 256) {
+#pragma unroll
+        for (int k = 0; k < DEPTH_LDS_WAVES; ++k) { c[k] = s_cnt[k][tid]; ltot += c[k]; }
+    }
+    const uint32_t inc = wave_inclusive_scan(ltot, lane);
+    if (tid < 256 && lane == 63) s_wsum[w] = inc;
+    __syncthreads();
+    if (tid < 256) {
+        uint32_t run = inc - ltot;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) run += k < w ? s_wsum[k] : 0u;
+#pragma unroll
+        for (int k = 0; k < DEPTH_LDS_WAVES; ++k) { s_cnt[k][tid] = run; run += c[k]; }
+        s_dcount[tid] = ltot;
+    }
+    __syncthreads();
+}
+
+// One workgroup per bucket: the pairs [bases[k], bases[k + 1]) of the bucket pass's output, in index order, leave sorted by key
+// (stable) at the same positions of the final arrays.  LSD passes of 8 bits over the bits in which the bucket's keys differ.
+// Up to DEPTH_LDS_CAP pairs: in registers and LDS, one read and one write of HBM.  Above: the same passes in chunks of DEPTH_LDS_CAP
+// pairs that ping-pong between the bucket's own ranges of the two global arrays — an odd number of passes, so that the last one
+// lands in the final arrays (a pass over bits that do not differ is the identity) — and info[1] counts the bucket.
+__global__ __launch_bounds__(DEPTH_LDS_THREADS) void depth_lds_sort_kernel(uint32_t* keys_a, uint32_t* vals_a, uint32_t* keys_out,
+                                                                           uint32_t* vals_out, const uint32_t* __restrict__ bases,
+                                                                           int64_t n, uint32_t* __restrict__ info) {
+    __shared__ uint32_t s_key[DEPTH_LDS_CAP], s_val[DEPTH_LDS_CAP];
+    __shared__ uint32_t s_cnt[DEPTH_LDS_WAVES][256];
+    __shared__ uint32_t s_wsum[4], s_dcount[256], s_run[256], s_or;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    uint32_t lo = bases[blockIdx.x], hi = bases[blockIdx.x + 1];
+    if (hi > (uint32_t)n) hi = (uint32_t)n;                      // (never: the bases count keys of this very input)
+    if (lo >= hi) return;
+    const int64_t count = (int64_t)hi - lo;
+
+    uint32_t key[DEPTH_LDS_ITEMS], val[DEPTH_LDS_ITEMS], rank[DEPTH_LDS_ITEMS];
+    const bool fits = count <= DEPTH_LDS_CAP;
+    const int R = fits ? ((int)count + DEPTH_LDS_THREADS - 1) / DEPTH_LDS_THREADS : DEPTH_LDS_ITEMS;
+
+    // the bits in which the keys of the bucket differ (a bucket that fits is loaded into registers on the way)
+    if (tid == 0) s_or = 0;
+    __syncthreads();
+    {
+        const uint32_t k0 = keys_a[lo];
+        uint32_t diff = 0;
+        if (fits) {
+#pragma unroll
+            for (int r = 0; r < DEPTH_LDS_ITEMS; ++r) {
+                const int e = w * 64 * R + r * 64 + lane;
+                const bool valid = r < R && e < (int)count;
+                key[r] = valid ? keys_a[lo + e] : 0xFFFFFFFFu;
+                val[r] = valid ? vals_a[lo + e] : 0u;
+            }
+#pragma unroll
+            for (int r = 0; r < DEPTH_LDS_ITEMS; ++r) {
+                const int e = w * 64 * R + r * 64 + lane;
+                if (r < R && e < (int)count) diff |= key[r] ^ k0;
+            }
+        } else {
+            for (int64_t i = tid; i < count; i += DEPTH_LDS_THREADS) diff |= keys_a[lo + i] ^ k0;
+        }
+        for (int off = 32; off > 0; off >>= 1) diff |= (uint32_t)__shfl_xor((int)diff, off);
+        if (lane == 0 && diff) atomicOr(&s_or, diff);
+    }
+    __syncthreads();
+    const int bits = 32 - __clz((int)s_or);                      // (__clz(0) = 32)
+    int npass = (bits + 7) / 8;
+
+    if (fits) {
+        const int nloc = (int)count;
+        if (npass == 0) {                                        // all keys equal: already in order
+#pragma unroll
+            for (int r = 0; r < DEPTH_LDS_ITEMS; ++r) {
+                const int e = w * 64 * R + r * 64 + lane;
+                if (r < R && e < nloc) { keys_out[lo + e] = key[r]; vals_out[lo + e] = val[r]; }
+            }
+            return;
+        }
+        for (int p = 0; p < npass; ++p) {
+            lds_rank(key, rank, R, nloc, 8 * p, s_cnt, s_wsum, s_dcount);
+#pragma unroll
+            for (int r = 0; r < DEPTH_LDS_ITEMS; ++r) {
+                const int e = w * 64 * R + r * 64 + lane;
+                if (r < R && e < nloc) {
+                    const uint32_t lp = s_cnt[w][(key[r] >> (8 * p)) & 255u] + rank[r];
+                    s_key[lp] = key[r];
+                    s_val[lp] = val[r];
+                }
+            }
+            __syncthreads();
+            if (p + 1 < npass) {
+#pragma unroll
+                for (int r = 0; r < DEPTH_LDS_ITEMS; ++r) {
+                    const int e = w * 64 * R + r * 64 + lane;
+                    if (r < R && e < nloc) { key[r] = s_key[e]; val[r] = s_val[e]; }
+                }
+            }
+        }
+        for (int i = tid; i < nloc; i += DEPTH_LDS_THREADS) {
+            keys_out[lo + i] = s_key[i];
+            vals_out[lo + i] = s_val[i];
+        }
+        return;
+    }
+
+    // a bucket above the cap (one fine bin holds thousands of keys): chunks through HBM, bounded loops
+    if (tid == 0) atomicAdd(&info[1], 1u);
+    if ((npass & 1) == 0) ++npass;
+    for (int p = 0; p < npass; ++p) {
+        const int shift = 8 * p;
+        const uint32_t* src_k = (p & 1) ? keys_out : keys_a;
+        const uint32_t* src_v = (p & 1) ? vals_out : vals_a;
+        uint32_t* dst_k = (p & 1) ? keys_a : keys_out;
+        uint32_t* dst_v = (p & 1) ? vals_a : vals_out;
+        // where each digit's run starts inside the bucket
+        if (tid < 256) s_run[tid] = 0;
+        __syncthreads();
+        for (int64_t i = tid; i < count; i += DEPTH_LDS_THREADS)
+            atomicAdd(&s_run[shift < 32 ? (src_k[lo + i] >> shift) & 255u : 0u], 1u);
+        __syncthreads();
+        if (tid == 0) {
+            uint32_t run = 0;
+            for (int d = 0; d < 256; ++d) { const uint32_t c = s_run[d]; s_run[d] = run; run += c; }
+        }
+        __syncthreads();
+        for (int64_t c0 = 0; c0 < count; c0 += DEPTH_LDS_CAP) {
+            const int nloc = (int)(count - c0 < DEPTH_LDS_CAP ? count - c0 : DEPTH_LDS_CAP);
+            const int R = DEPTH_LDS_ITEMS;
+#pragma unroll
+            for (int r = 0; r < DEPTH_LDS_ITEMS; ++r) {
+                const int e = w * 64 * R + r * 64 + lane;
+                key[r] = e < nloc ? src_k[lo + c0 + e] : 0xFFFFFFFFu;
+                val[r] = e < nloc ? src_v[lo + c0 + e] : 0u;
+            }
+            lds_rank(key, rank, R, nloc, shift, s_cnt, s_wsum, s_dcount);
+#pragma unroll
+            for (int r = 0; r < DEPTH_LDS_ITEMS; ++r) {
+                const int e = w * 64 * R + r * 64 + lane;
+                if (e < nloc) {
+                    const uint32_t d = shift < 32 ? (key[r] >> shift) & 255u : 0u;
+                    const uint32_t pos = s_run[d] + (s_cnt[w][d] + rank[r] - s_cnt[0][d]);
+                    dst_k[lo + pos] = key[r];
+                    dst_v[lo + pos] = val[r];
+                }
+            }
+            __syncthreads();
+            if (tid < 256) s_run[tid] += s_dcount[tid];
+            __syncthreads();
+        }
+        __threadfence();        // the next pass reads what this one wrote (other waves of this workgroup)
+        __syncthreads();
+    }
+}
+
+std::atomic<int> g_depth_sort{[] {
+    const char* e = getenv("MSGS_DEPTH_SORT");
+    return (e && (e[0] == '1' || e[0] == '2') && e[1] == 0) ? e[0] - '0' : 0;
+}()};
+
+template <int ITEMS>
+void launch_bucket_pass(const uint32_t* src_k, uint32_t* dst_k, uint32_t* dst_v, int64_t n, const uint8_t* map, const GroupGeom& G,
+                        uint32_t* hist, uint32_t* gs, hipStream_t s) {
+    const dim3 grid((unsigned)G.nb), block(SORT_THREADS);
+    const BucketDigit dg{map};
+    hipLaunchKernelGGL((radix_hist_kernel<ITEMS, true, uint32_t, BucketDigit>), grid, block, 0, s, src_k, n, dg, G.nb, hist, gs,
+                       G.gsize, G.ngroups, (const uint32_t*)nullptr);
+    hipLaunchKernelGGL((radix_scatter_kernel<ITEMS, true, uint32_t, BucketDigit>), grid, block, 0, s, src_k, (const uint32_t*)nullptr,
+                       dst_k, dst_v, n, dg, G.nb, (const uint32_t*)hist, (const uint32_t*)gs, G.gsize, G.ngroups, false,
+                       (const uint32_t*)nullptr, (uint32_t*)nullptr);
+}
+
+}  // namespace
+
+int set_depth_sort(int mode) { return g_depth_sort.exchange(mode == 1 || mode == 2 ? mode : 0); }
+int get_depth_sort() { return g_depth_sort.load(); }
+
+bool depth_sort_uses_buckets(int64_t n) {
+    const int mode = g_depth_sort.load();
+    if (mode == 1 || n <= 0 || n > DEPTH_BUCKET_HARD_MAX) return false;
+    return mode == 2 || n <= DEPTH_BUCKET_MAX_P;
+}
+
+// the group sums of the bucket pass and, directly behind them, the sums per group of 256 depth bins: one range
+bool depth_sort_zero_region(int64_t n, char* scratch, uint32_t** ptr, size_t* words) {
+    const DepthSortScratch L(n);
+    size_t w = 0;
+    if (!radix_sort_zero_region(n, 0, 32, scratch + L.sort, ptr, &w)) return false;
+    *words = (size_t)((scratch + L.zero_end()) - reinterpret_cast<char*>(*ptr)) / 4;
+    return true;
+}
+
+hipError_t depth_sort_buckets(const uint32_t* keys_in, uint32_t* keys_out, uint32_t* vals_out, int64_t n, char* scratch,
+                              hipStream_t s, bool pre_zeroed, uint32_t* n_valid_dev, uint32_t* info) {
+    if (n <= 0) {
+        if (n_valid_dev) hipLaunchKernelGGL(store_u32_kernel, dim3(1), dim3(1), 0, s, n_valid_dev, 0u);
+        return hipSuccess;
+    }
+    const GroupGeom G(n);
+    if (n > DEPTH_BUCKET_HARD_MAX) return hipErrorInvalidValue;
+    const DepthSortScratch L(n);
+    const SortScratch SS(n);
+    char* sort = scratch + L.sort;
+    uint32_t* keys_a = reinterpret_cast<uint32_t*>(sort + SS.keys_alt);
+    uint32_t* vals_a = reinterpret_cast<uint32_t*>(sort + SS.vals_alt);
+    uint32_t* hist = reinterpret_cast<uint32_t*>(sort + SS.hist);
+    uint32_t* gsum = hist + (size_t)256 * G.nb;
+    uint32_t* slices = reinterpret_cast<uint32_t*>(scratch + L.slices);
+    uint32_t* coarse = reinterpret_cast<uint32_t*>(scratch + L.coarse);
+    uint8_t* map = reinterpret_cast<uint8_t*>(scratch + L.map);
+    uint32_t* bases = reinterpret_cast<uint32_t*>(scratch + L.bases);
+    if (!info) info = bases + DEPTH_BUCKETS + 2;
+    if (!pre_zeroed) {
+        uint32_t* zp = nullptr;
+        size_t zw = 0;
+        if (!depth_sort_zero_region(n, scratch, &zp, &zw)) return hipErrorInvalidValue;
+        const hipError_t e = launch_zero(zp, sizeof(uint32_t) * zw, s);
+        if (e != hipSuccess) return e;
+    }
+    const int hb = depth_hist_blocks(n);
+    hipLaunchKernelGGL(depth_hist_kernel, dim3((unsigned)hb), dim3(DEPTH_HIST_THREADS), 0, s, keys_in, n, slices, coarse);
+    hipLaunchKernelGGL(depth_split_kernel, dim3(DEPTH_COARSE), dim3(256), 0, s, (const uint16_t*)slices, hb, (const uint32_t*)coarse, map,
+                       bases, n_valid_dev, info);
+    if (G.big) launch_bucket_pass<16>(keys_in, keys_a, vals_a, n, map, G, hist, gsum, s);
+    else if (G.mid) launch_bucket_pass<8>(keys_in, keys_a, vals_a, n, map, G, hist, gsum, s);
+    else launch_bucket_pass<SORT_ITEMS>(keys_in, keys_a, vals_a, n, map, G, hist, gsum, s);
+    hipLaunchKernelGGL(depth_lds_sort_kernel, dim3(DEPTH_BUCKETS), dim3(DEPTH_LDS_THREADS), 0, s, keys_a, vals_a, keys_out, vals_out,
+                       (const uint32_t*)bases, n, info);
+    return hipGetLastError();
 }
 
 }  // namespace msgs

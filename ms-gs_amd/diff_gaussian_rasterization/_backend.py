@@ -154,6 +154,10 @@ def _load():
     lib.msgs_set_occlusion.argtypes = [C.c_int32]
     lib.msgs_occlusion_stats.restype = C.c_int
     lib.msgs_occlusion_stats.argtypes = [vp, sz, C.c_int32, C.POINTER(C.c_int64), vp]
+    lib.msgs_set_depth_sort.restype = C.c_int
+    lib.msgs_set_depth_sort.argtypes = [C.c_int32]
+    lib.msgs_depth_sort_stats.restype = C.c_int
+    lib.msgs_depth_sort_stats.argtypes = [vp, sz, C.c_int32, C.POINTER(C.c_int64), vp]
     lib.msgs_slab_stats.restype = C.c_int
     lib.msgs_slab_stats.argtypes = [vp, sz, C.c_int32, C.POINTER(C.c_int64), vp]
     lib.msgs_forward.restype = C.c_int
@@ -301,7 +305,8 @@ EXPORTS = ("msgs_abi_version", "msgs_error_string", "msgs_geom_bytes", "msgs_sta
            "msgs_features_scratch_bytes", "msgs_features_forward", "msgs_features_backward",
            "msgs_distortion_forward", "msgs_distortion_backward",
            "msgs_median_depth_forward", "msgs_median_depth_backward",
-           "msgs_screen_compensation_forward", "msgs_screen_compensation_backward", "msgs_screen_compensation_scratch_bytes")
+           "msgs_screen_compensation_forward", "msgs_screen_compensation_backward", "msgs_screen_compensation_scratch_bytes",
+           "msgs_set_depth_sort", "msgs_depth_sort_stats")
 
 
 def check(rc, where):
