@@ -534,6 +534,42 @@ int msgs_screen_compensation_backward(const msgs_view_t* view, const msgs_gaussi
                                       float* dL_dopacity, float* dL_dmeans3D, float* dL_dscales, float* dL_drotations,
                                       float* dL_dcov3D, float* dL_dV, void* scratch, size_t scratch_bytes, void* stream);
 
+/* ---- 3-D smoothing filter of Mip-Splatting: camera sweep and filtered getters (DESIGN.md SPEC M16, 4.17) ------------------- */
+/* The 3-D filter bounds the size of every Gaussian from below by the highest sampling rate nu (pixels per world unit) at which
+ * any camera of a set sees its centre.  `cameras` is a device table [n_cameras, MSGS_FILTER3D_CAMERA_FLOATS] float32, row n =
+ * { M_n[16] (world_view_transform in the layout of msgs_view_t::viewmatrix), fx_n, fy_n, W_n, H_n }, fx = W / (2 tan(FoVx / 2)).
+ * With t = the view-space centre (float32, the operations of msgs_forward*), zc = max(t.z, 0.001),
+ * x = t.x / zc fx + W / 2, y = t.y / zc fy + H / 2, camera n SEES the centre iff
+ *     t.z > 0.2   and   -0.15 W <= x <= 1.15 W   and   -0.15 H <= y <= 1.15 H       (a NaN / Inf anywhere: not seen)
+ *     rule MSGS_FILTER3D_RULE_PER_CAMERA:     nu = max over the seeing cameras of fx_n / t.z          (the paper)
+ *     rule MSGS_FILTER3D_RULE_MIP_SPLATTING:  nu = (max over ALL cameras of fx_n) / (min over the seeing cameras of t.z)
+ *                                                                                                      (the published code)
+ * msgs_filter3d_sweep writes valid [P] (one byte per Gaussian, 1 = some camera sees it) and filter_3D [P] float32 =
+ * sqrt(variance) / nu; a Gaussian no camera sees takes the smallest nu of those that are seen (the largest filter); when none
+ * is seen filter_3D is 0 everywhere, which the getters below read as "no filter".  Min and max only: the same bits on every run
+ * and for every launch geometry.  scratch >= msgs_filter3d_scratch_bytes(P, n_cameras), 4-byte aligned; everything on `stream`,
+ * no synchronisation.  P == 0: nothing is launched.
+ *
+ * The filtered getters, for f = filter_3D, s the scales [P,3] and o the opacities [P]:
+ *     s_eff_k = sqrt(s_k^2 + f^2),   o_eff = o r_0 r_1 r_2,   r_k = s_k / s_eff_k      (= o sqrt(det S^2 / det(S^2 + f^2 I)))
+ * A filtered render IS the plain render of the same model with (s_eff, o_eff) in the place of (s, o).  A row with f == 0 passes
+ * s and o through bit for bit; s_k == 0 with f > 0 gives s_eff_k = f, o_eff = 0 and finite gradients.  raw != 0: `scales` are
+ * log-scales and `opacities` logits, activated here with the expressions of msgs_gaussians_t::raw_params == 1, and the backward
+ * returns the gradients of those raw values.  msgs_smoothing_filter_backward writes every row of dL_dscales [P,3] and
+ * dL_dopacities [P]; one of dL_dscales_eff / dL_dopacities_eff may be NULL (that output did not enter the loss: zeros). */
+#define MSGS_FILTER3D_CAMERA_FLOATS 20
+#define MSGS_FILTER3D_CAMERA_CHUNK 64          /* camera rows staged per pass of the sweep (tests straddle it) */
+#define MSGS_FILTER3D_RULE_PER_CAMERA 0
+#define MSGS_FILTER3D_RULE_MIP_SPLATTING 1
+size_t msgs_filter3d_scratch_bytes(int32_t P, int32_t n_cameras);
+int msgs_filter3d_sweep(int32_t P, const float* means3D, int32_t n_cameras, const float* cameras, int32_t rule, float variance,
+                        float* filter_3D, uint8_t* valid, void* scratch, size_t scratch_bytes, void* stream);
+int msgs_smoothing_filter_forward(int32_t P, int32_t raw, const float* scales, const float* opacities, const float* filter_3D,
+                                  float* scales_eff, float* opacities_eff, void* stream);
+int msgs_smoothing_filter_backward(int32_t P, int32_t raw, const float* scales, const float* opacities, const float* filter_3D,
+                                   const float* dL_dscales_eff, const float* dL_dopacities_eff, float* dL_dscales,
+                                   float* dL_dopacities, void* stream);
+
 /* msgs_backward_per_gaussian: the per-Gaussian half of msgs_backward ALONE (2-D covariance backward, projection, SH,
  * scale / quaternion chain — upstream's computeCov2DCUDA + preprocessCUDA backward, SURVEY 2.2 K8 + K9) on per-Gaussian
  * 2-D gradients supplied by the caller instead of the blend backward's sums: sums2d [P,9] DOUBLES (device) =

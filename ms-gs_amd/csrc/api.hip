@@ -1080,6 +1080,45 @@ int msgs_screen_compensation_backward(const msgs_view_t* view, const msgs_gaussi
 }
 }  // extern "C"
 
+// ---- 3-D smoothing filter: the camera sweep and the filtered getters (SPEC M16) ----
+extern "C" {
+size_t msgs_filter3d_scratch_bytes(int32_t P, int32_t n_cameras) { (void)P; (void)n_cameras; return 256; }
+
+int msgs_filter3d_sweep(int32_t P, const float* means3D, int32_t n_cameras, const float* cameras, int32_t rule, float variance,
+                        float* filter_3D, uint8_t* valid, void* scratch, size_t scratch_bytes, void* stream) {
+    if (P < 0 || n_cameras < 1 || !(variance > 0.0f)) return MSGS_ERR_INVALID_ARG;
+    if (rule != MSGS_FILTER3D_RULE_PER_CAMERA && rule != MSGS_FILTER3D_RULE_MIP_SPLATTING) return MSGS_ERR_INVALID_ARG;
+    if (P == 0) return MSGS_OK;
+    if (!means3D || !cameras || !filter_3D || !valid || !scratch || ((uintptr_t)scratch & 3)) return MSGS_ERR_INVALID_ARG;
+    if (scratch_bytes < msgs_filter3d_scratch_bytes(P, n_cameras)) return MSGS_ERR_CAPACITY;
+    HIP_TRY(launch_filter3d_sweep(P, means3D, n_cameras, cameras, rule, variance, filter_3D, valid, (uint32_t*)scratch,
+                                  (hipStream_t)stream));
+    return MSGS_OK;
+}
+
+int msgs_smoothing_filter_forward(int32_t P, int32_t raw, const float* scales, const float* opacities, const float* filter_3D,
+                                  float* scales_eff, float* opacities_eff, void* stream) {
+    if (P < 0) return MSGS_ERR_INVALID_ARG;
+    if (P == 0) return MSGS_OK;
+    if (!scales || !opacities || !filter_3D || !scales_eff || !opacities_eff) return MSGS_ERR_INVALID_ARG;
+    HIP_TRY(launch_smoothing_filter_forward(P, raw != 0, scales, opacities, filter_3D, scales_eff, opacities_eff,
+                                            (hipStream_t)stream));
+    return MSGS_OK;
+}
+
+int msgs_smoothing_filter_backward(int32_t P, int32_t raw, const float* scales, const float* opacities, const float* filter_3D,
+                                   const float* dL_dscales_eff, const float* dL_dopacities_eff, float* dL_dscales,
+                                   float* dL_dopacities, void* stream) {
+    if (P < 0) return MSGS_ERR_INVALID_ARG;
+    if (P == 0) return MSGS_OK;
+    if (!scales || !opacities || !filter_3D || !dL_dscales || !dL_dopacities) return MSGS_ERR_INVALID_ARG;
+    if (!dL_dscales_eff && !dL_dopacities_eff) return MSGS_ERR_INVALID_ARG;
+    HIP_TRY(launch_smoothing_filter_backward(P, raw != 0, scales, opacities, filter_3D, dL_dscales_eff, dL_dopacities_eff,
+                                             dL_dscales, dL_dopacities, (hipStream_t)stream));
+    return MSGS_OK;
+}
+}  // extern "C"
+
 namespace {
 int backward_impl(const msgs_view_t* view, const msgs_gaussians_t* g, const int32_t* radii, const void* geom_v,
                   size_t geom_bytes, int64_t D, const void* binning_v, size_t binning_bytes, const void* image_v,

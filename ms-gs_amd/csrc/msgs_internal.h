@@ -884,6 +884,15 @@ hipError_t launch_screen_compensation_forward(const ViewParams& vp, const msgs_g
 hipError_t launch_screen_compensation_backward(const ViewParams& vp, const msgs_gaussians_t& g, const float* dL_do_eff,
                                                float* dL_dopacity, float* dL_dmeans3D, float* dL_dscales, float* dL_drotations,
                                                float* dL_dcov3D, float* dL_dV, double* rows, hipStream_t s);
+// filter3d.hip — msgs_filter3d_sweep and msgs_smoothing_filter_* (SPEC M16): the camera sweep of the 3-D smoothing filter
+// (`fallback`: one device word, set and read inside) and the filtered getters with their backward
+hipError_t launch_filter3d_sweep(int P, const float* means3D, int V, const float* cameras, int rule, float variance,
+                                 float* filter_3D, uint8_t* valid, uint32_t* fallback, hipStream_t s);
+hipError_t launch_smoothing_filter_forward(int P, bool raw, const float* scales, const float* opacities, const float* filter_3D,
+                                           float* scales_eff, float* opacities_eff, hipStream_t s);
+hipError_t launch_smoothing_filter_backward(int P, bool raw, const float* scales, const float* opacities, const float* filter_3D,
+                                            const float* dL_dscales_eff, const float* dL_dopacities_eff, float* dL_dscales,
+                                            float* dL_dopacities, hipStream_t s);
 // msgs_median_depth_* (SPEC M15): the median-depth map [H,W] and the id map of its Gaussians (front-to-back replay with early
 // exit); the backward adds dL/dmedian_depth of every pixel to slot 9 (dL/dz) of its Gaussian's record
 hipError_t launch_blend_median_depth_forward(const ViewParams& vp, const char* geom, const uint32_t* ids, const uint2* ranges,

@@ -29,7 +29,7 @@ from . import _backend as _C
 
 __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "rasterize_gaussians_raw",
            "deferred_forward", "GradAccumulator", "set_grad_accumulator", "ContributionScores", "ContributionAccumulator",
-           "screen_compensation"]
+           "screen_compensation", "compute_3d_filter", "smoothing_filter", "FILTER3D_CAMERA_CHUNK"]
 
 
 class GaussianRasterizationSettings(NamedTuple):
@@ -1739,6 +1739,150 @@ def screen_compensation(means3D, opacities, raster_settings, scales=None, rotati
     return _ScreenCompensation.apply(means3D, opacities, scales, rotations, cov3D_precomp, vm, raster_settings)
 
 
+# 3-D smoothing filter (DESIGN.md 2, M16; 4.17): the other half of Mip-Splatting.  Every Gaussian is bounded from below in size
+# by the highest sampling rate at which any training camera sees it; a filtered render is the plain render of the same model with
+# (s_eff, o_eff) in the place of the scales and the opacity, so the rasterizer and every opt-in output only see two tensors.
+FILTER3D_CAMERA_CHUNK = _C.FILTER3D_CAMERA_CHUNK
+_filter3d_probe = None             # tests: a callable (name) run in front of every msgs_filter3d_* / msgs_smoothing_filter_* call
+
+
+def _camera_table(cameras, device=None):
+    """[V, 20] float32: world_view_transform (16, the layout the rasterizer's viewmatrix has), fx, fy, W, H.  The matrices are
+    stacked where they live and the focal lengths are formed in double on the host: cameras on the host give a host table that
+    travels in one transfer, cameras already on `device` only send their [V, 4] intrinsics.  device=None: the host table."""
+    import math
+    mats, intr = [], []
+    for cam in cameras:
+        M = cam.world_view_transform
+        if not torch.is_tensor(M):
+            M = torch.as_tensor(M, dtype=torch.float32)
+        if M.shape != (4, 4):
+            raise ValueError("compute_3d_filter: world_view_transform must be [4,4]")
+        mats.append(M)
+        W, H = float(cam.image_width), float(cam.image_height)
+        intr.append((W / (2.0 * math.tan(0.5 * float(cam.FoVx))), H / (2.0 * math.tan(0.5 * float(cam.FoVy))), W, H))
+    if not mats:
+        raise ValueError("compute_3d_filter: at least one camera is needed")
+    if len({m.device for m in mats}) > 1:
+        mats = [m.cpu() for m in mats]
+    M = torch.stack(mats).detach().float().reshape(len(mats), 16)
+    intr = torch.tensor(intr, dtype=torch.float64).float()
+    if device is None or M.device.type == "cpu":
+        table = torch.cat([M.cpu(), intr], dim=1).contiguous()
+        return table if device is None else table.to(device)
+    return torch.cat([M.to(device), intr.to(device)], dim=1).contiguous()
+
+
+@torch.no_grad()
+def compute_3d_filter(means3D, cameras, rule="per_camera", variance=0.2):
+    """(filter_3D [P,1] float32, valid_points [P] bool) of Mip-Splatting's 3-D smoothing filter for the centres `means3D` and the
+    camera set `cameras` (any sequence of objects with world_view_transform, FoVx, FoVy, image_width, image_height).  Camera n
+    sees a centre iff its view depth t.z exceeds 0.2 and its projection lies within 15 % of the image around it;
+        rule="per_camera":     nu = max over the seeing cameras of fx_n / t.z      (the paper; right for mixed focal lengths)
+        rule="mip_splatting":  nu = (max fx over ALL cameras) / (min t.z over the seeing cameras)      (the published code)
+    and filter_3D = sqrt(variance) / nu.  valid_points tells which centres some camera sees; the others take the largest filter
+    of those (the published code's distance[~valid].max()); if none is seen the filter is 0 everywhere, which smoothing_filter()
+    reads as the identity.  One sweep kernel over the whole set (the camera table travels in one copy) on the current stream,
+    without a host read-back; the same bits on every run.  Carries no gradient.  Recompute it whenever the model's rows change
+    (after every densification) and, as Mip-Splatting does, every 100 iterations."""
+    if rule not in _C.FILTER3D_RULES:
+        raise ValueError(f"compute_3d_filter: rule must be one of {sorted(_C.FILTER3D_RULES)}, not {rule!r}")
+    if not float(variance) > 0.0:
+        raise ValueError("compute_3d_filter: variance must be positive")
+    if means3D.dim() != 2 or means3D.shape[1] != 3:
+        raise ValueError("compute_3d_filter: means3D must be [P,3]")
+    cameras = list(cameras)
+    if not cameras:
+        raise ValueError("compute_3d_filter: at least one camera is needed")
+    dev = means3D.device
+    if dev.type != "cuda":
+        raise RuntimeError("diff_gaussian_rasterization (MI355X build): tensors must live on a HIP device")
+    P, V = int(means3D.shape[0]), len(cameras)
+    filt = torch.empty(P, 1, dtype=torch.float32, device=dev)
+    valid = torch.empty(P, dtype=torch.bool, device=dev)
+    if P == 0:
+        return filt, valid
+    means = _f32c(means3D.detach())
+    with _on_device(dev):
+        cams = _camera_table(cameras, dev)
+        scratch = _bytes(_C.lib.msgs_filter3d_scratch_bytes(P, V), dev)
+        if _filter3d_probe is not None:
+            _filter3d_probe("msgs_filter3d_sweep")
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _C.check(_C.lib.msgs_filter3d_sweep(P, _ptr(means), V, _ptr(cams), _C.FILTER3D_RULES[rule], float(variance), _ptr(filt),
+                                            _ptr(valid), _ptr(scratch), scratch.numel(), stream), "msgs_filter3d_sweep")
+    return filt, valid
+
+
+def _check_filter_rows(scales, opacities, filter_3D):
+    P = int(scales.shape[0])
+    if scales.dim() != 2 or scales.shape[1] != 3:
+        raise ValueError("smoothing_filter: scales must be [P,3]")
+    if opacities.numel() != P or filter_3D.numel() != P:
+        raise ValueError(f"smoothing_filter: {P} rows of scales, {opacities.numel()} opacities and {filter_3D.numel()} rows of "
+                         "filter_3D — a filter computed before a densification is stale: run compute_3d_filter again")
+    return P
+
+
+class _SmoothingFilter(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, scales, opacities, filter_3D, raw):
+        P, dev = int(scales.shape[0]), scales.device
+        if dev.type != "cuda":
+            raise RuntimeError("diff_gaussian_rasterization (MI355X build): tensors must live on a HIP device")
+        ctx.shapes, ctx.raw, ctx.P, ctx.dev = (scales.shape, opacities.shape), bool(raw), P, dev
+        s_eff = torch.empty(P, 3, dtype=torch.float32, device=dev)
+        o_eff = torch.empty(opacities.shape, dtype=torch.float32, device=dev)
+        if P == 0:
+            return s_eff, o_eff
+        s, o, f = _f32c(scales.detach()), _f32c(opacities.detach()), _f32c(filter_3D.detach())
+        if _filter3d_probe is not None:
+            _filter3d_probe("msgs_smoothing_filter_forward")
+        with _on_device(dev):
+            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            _C.check(_C.lib.msgs_smoothing_filter_forward(P, int(ctx.raw), _ptr(s), _ptr(o), _ptr(f), _ptr(s_eff), _ptr(o_eff),
+                                                          stream), "msgs_smoothing_filter_forward")
+        ctx.save_for_backward(s, o, f)
+        return s_eff, o_eff
+
+    @staticmethod
+    def backward(ctx, g_s_eff, g_o_eff):
+        P, dev = ctx.P, ctx.dev
+        new = torch.zeros if P == 0 or (g_s_eff is None and g_o_eff is None) else torch.empty   # (the kernel writes every row)
+        g_s = new(ctx.shapes[0], dtype=torch.float32, device=dev)
+        g_o = new(ctx.shapes[1], dtype=torch.float32, device=dev)
+        if new is torch.zeros:
+            return g_s, g_o, None, None
+        s, o, f = ctx.saved_tensors
+        gs = None if g_s_eff is None else _f32c(g_s_eff)
+        go = None if g_o_eff is None else _f32c(g_o_eff)
+        if _filter3d_probe is not None:
+            _filter3d_probe("msgs_smoothing_filter_backward")
+        with _on_device(dev):
+            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            _C.check(_C.lib.msgs_smoothing_filter_backward(P, int(ctx.raw), _ptr(s), _ptr(o), _ptr(f), _ptr(gs), _ptr(go),
+                                                           _ptr(g_s), _ptr(g_o), stream), "msgs_smoothing_filter_backward")
+        return g_s, g_o, None, None
+
+
+def smoothing_filter(scales, opacities, filter_3D, raw=False):
+    """(scales_eff [P,3], opacities_eff in opacities' shape), float32: the model's getters under the 3-D smoothing filter
+    f = filter_3D [P,1] (compute_3d_filter),
+        s_eff_k = sqrt(s_k^2 + f^2),     o_eff = o r_0 r_1 r_2,   r_k = s_k / s_eff_k     (= o sqrt(det S^2 / det(S^2 + f^2 I)))
+    Rendering the same model with them in the place of its scales and opacities IS the filtered render.  A row with f == 0 is
+    passed through bit for bit; s_k == 0 under f > 0 gives s_eff_k = f, o_eff = 0 and finite gradients.  raw=True takes the
+    LEAVES — log-scales and opacity logits — and applies exp and sigmoid inside the kernel, with the rasterizer's own
+    expressions; the gradients then land on the leaves and the exp / sigmoid nodes leave autograd.  Differentiable in scales and
+    opacities, not in filter_3D.  One streaming HIP kernel forward and one backward.  ValueError when the row counts differ."""
+    _check_filter_rows(scales, opacities, filter_3D)
+    if filter_3D.requires_grad:
+        filter_3D = filter_3D.detach()
+    s_eff, o_eff = _SmoothingFilter.apply(scales, opacities, filter_3D, bool(raw))
+    # not the reference's getters: the rasterizer skips the chained mode for them without its warning
+    s_eff._msgs_filtered = o_eff._msgs_filtered = True
+    return s_eff, o_eff
+
+
 # Contribution scores (DESIGN.md 2, M11; 4.11): what every Gaussian did to the images of one or many views, the criterion of
 # contribution-based pruning (LightGaussian's global significance, RadSplat's max contribution, Mini-Splatting's importance).
 # With w_ip = alpha_ip T_ip, the blend weight of Gaussian i in pixel p, and an optional per-pixel weight map m_p >= 0:
@@ -2051,7 +2195,8 @@ class GaussianRasterizer(nn.Module):
             # o rho is not the sigmoid getter: straight to the plain route (no chained mode, none of its warning)
             opacities = self._opacities(means3D, opacities, scales, rotations, cov3D_precomp)
         elif chain_reference_getters and torch.is_grad_enabled() and shs is not None and cov3D_precomp is None \
-                and means3D.shape[0] > 0 and means3D.device.type == "cuda":
+                and means3D.shape[0] > 0 and means3D.device.type == "cuda" \
+                and not (getattr(scales, "_msgs_filtered", False) or getattr(opacities, "_msgs_filtered", False)):
             leaves = _match_reference_getters(means3D, shs, opacities, scales, rotations)
             if leaves is None and not _warned_chain[0] and all(
                     t is not None and t.grad_fn is not None for t in (shs, opacities, scales, rotations)):

@@ -81,6 +81,10 @@ class DensifyStats(C.Structure):
                 ("base_mask", C.c_void_p)]
 
 
+# msgs_filter3d_sweep (include/msgs.h): floats per camera row, camera rows staged per pass of the sweep, the two rules
+FILTER3D_CAMERA_FLOATS, FILTER3D_CAMERA_CHUNK = 20, 64
+FILTER3D_RULES = {"per_camera": 0, "mip_splatting": 1}
+
 DENSIFY_PRUNE, DENSIFY_GROW, DENSIFY_PRUNE_MASK, DENSIFY_APPEND = 0, 1, 2, 3
 (DR_COPY, DR_ZERO, DR_COPY_CLEAR_COL, DR_SPLIT_XYZ, DR_SPLIT_SCALE, DR_SPLIT_DIV, DR_GROW_OPACITY, DR_GROW_SCALE, DR_GROW_MUL,
  DR_CONST, DR_APPEND) = range(11)
@@ -228,6 +232,14 @@ def _load():
     lib.msgs_screen_compensation_forward.argtypes = [C.POINTER(View), C.POINTER(Gaussians), vp, vp]
     lib.msgs_screen_compensation_backward.restype = C.c_int
     lib.msgs_screen_compensation_backward.argtypes = [C.POINTER(View), C.POINTER(Gaussians), vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    lib.msgs_filter3d_scratch_bytes.restype = sz
+    lib.msgs_filter3d_scratch_bytes.argtypes = [C.c_int32, C.c_int32]
+    lib.msgs_filter3d_sweep.restype = C.c_int
+    lib.msgs_filter3d_sweep.argtypes = [C.c_int32, vp, C.c_int32, vp, C.c_int32, C.c_float, vp, vp, vp, sz, vp]
+    lib.msgs_smoothing_filter_forward.restype = C.c_int
+    lib.msgs_smoothing_filter_forward.argtypes = [C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp]
+    lib.msgs_smoothing_filter_backward.restype = C.c_int
+    lib.msgs_smoothing_filter_backward.argtypes = [C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.msgs_backward_per_gaussian.restype = C.c_int
     lib.msgs_backward_per_gaussian.argtypes = [C.POINTER(View), C.POINTER(Gaussians), vp, vp, sz, vp, C.POINTER(Grads), vp]
     lib.msgs_sh_grad_from_views.restype = C.c_int
@@ -306,6 +318,8 @@ EXPORTS = ("msgs_abi_version", "msgs_error_string", "msgs_geom_bytes", "msgs_sta
            "msgs_distortion_forward", "msgs_distortion_backward",
            "msgs_median_depth_forward", "msgs_median_depth_backward",
            "msgs_screen_compensation_forward", "msgs_screen_compensation_backward", "msgs_screen_compensation_scratch_bytes",
+           "msgs_filter3d_scratch_bytes", "msgs_filter3d_sweep", "msgs_smoothing_filter_forward",
+           "msgs_smoothing_filter_backward",
            "msgs_set_depth_sort", "msgs_depth_sort_stats")
 
 

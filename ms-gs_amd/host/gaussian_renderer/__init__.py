@@ -61,6 +61,14 @@ def _colour_inputs(cam, pc, pipe, override_color):
     return dict(shs=None, colors_precomp=torch.clamp_min(rgb + 0.5, 0.0))
 
 
+def _refuse_filter_3d(pc, who):
+    """The raw-parameter routes read the model's leaves themselves: on a model that carries a 3-D smoothing filter
+    (filter3d.compute_3D_filter) they would render the UNFILTERED model without saying so."""
+    if getattr(pc, "filter_3D", None) is not None:
+        raise ValueError(f"{who}: the model carries a filter_3D, which this route would ignore; render through "
+                         "filter3d.render_with_3d_filter(), or filter3d.bake_3d_filter(pc) first")
+
+
 def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, override_color=None,
            filter_small=False, filter_large=False, fade_size=1.0):
     """Render `pc` from `viewpoint_camera`.  `bg_color` must already live on the GPU."""
@@ -100,6 +108,7 @@ def render_fused(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_mod
     GaussianModel, scene/gaussian_model.py:53-58) to the rasterizer, which evaluates the getters' activations
     (:127-153) and the SH concatenation (:144-149) inside its kernels.  Same result dict as render(); gradients land
     on the same leaf Parameters.  Not usable with override_color / convert_SHs_python / compute_cov3D_python."""
+    _refuse_filter_3d(pc, "render_fused")
     xyz = pc._xyz
     # gradient sink for the screen-space means: the op never reads its values, so — unlike render(), which keeps the
     # reference's `zeros_like(...) + 0` — a leaf without the fill and add kernels will do (.grad is populated the same)
@@ -124,6 +133,7 @@ def render_with_alpha(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scalin
     settings = _settings(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, filter_small, filter_large, fade_size)
     rasterizer = GaussianRasterizer(raster_settings=settings, return_alpha=True)
     if fused:
+        _refuse_filter_3d(pc, "fused=True")
         if override_color is not None:
             raise ValueError("render_with_alpha: fused=True cannot be combined with override_color")
         xyz = pc._xyz
@@ -168,6 +178,7 @@ def render_with_absgrad(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scal
     settings = _settings(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, filter_small, filter_large, fade_size)
     rasterizer = GaussianRasterizer(raster_settings=settings, return_alpha=alpha, absgrad=True)
     if fused:
+        _refuse_filter_3d(pc, "fused=True")
         if override_color is not None:
             raise ValueError("render_with_absgrad: fused=True cannot be combined with override_color")
         xyz = pc._xyz
@@ -214,6 +225,7 @@ def render_with_features(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, fea
     settings = _settings(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, filter_small, filter_large, fade_size)
     rasterizer = GaussianRasterizer(raster_settings=settings).with_features(features)
     if fused:
+        _refuse_filter_3d(pc, "fused=True")
         if override_color is not None:
             raise ValueError("render_with_features: fused=True cannot be combined with override_color")
         xyz = pc._xyz
@@ -260,6 +272,7 @@ def render_with_distortion(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, s
     settings = _settings(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, filter_small, filter_large, fade_size)
     rasterizer = GaussianRasterizer(raster_settings=settings, return_alpha=alpha).with_distortion()
     if fused:
+        _refuse_filter_3d(pc, "fused=True")
         if override_color is not None:
             raise ValueError("render_with_distortion: fused=True cannot be combined with override_color")
         xyz = pc._xyz
@@ -343,6 +356,7 @@ def render_with_median_depth(viewpoint_camera, pc, pipe, bg_color: torch.Tensor,
     settings = _settings(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, filter_small, filter_large, fade_size)
     rasterizer = GaussianRasterizer(raster_settings=settings, return_alpha=alpha).with_median_depth()
     if fused:
+        _refuse_filter_3d(pc, "fused=True")
         if override_color is not None:
             raise ValueError("render_with_median_depth: fused=True cannot be combined with override_color")
         xyz = pc._xyz

@@ -4,7 +4,8 @@ without the plyfile dependency (binary_little_endian PLY read and written with n
 
 PLY vertex properties, in order: x y z nx ny nz | f_dc_0..2 | f_rest_0..44 | opacity | occ_multiplier_0..3 |
 dc_delta_{0..3}_{0..2} | scale_0..2 | rot_0..3 | base_gaussian_mask (uchar; the reference passes a numpy bool, which
-plyfile stores as uchar) | max_pixel_sizes | min_pixel_sizes; everything else float32.  SH coefficients are stored
+plyfile stores as uchar) | max_pixel_sizes | min_pixel_sizes [| filter_3D, only on a model that carries Mip-Splatting's 3-D
+smoothing filter]; everything else float32.  SH coefficients are stored
 channel-major (transpose(1, 2) of the [P, K, 3] parameter), as the reference does.
 
 capture()/restore(): the reference's restore() unpacks (max_radii2D, min_pixel_sizes, base_gaussian_mask,
@@ -111,6 +112,10 @@ def save_ply(model, path):
     cols["base_gaussian_mask"] = cpu(model.base_gaussian_mask).astype(np.bool_)
     cols["max_pixel_sizes"] = cpu(model.max_pixel_sizes).astype(np.float32)
     cols["min_pixel_sizes"] = cpu(model.min_pixel_sizes).astype(np.float32)
+    # Mip-Splatting's 3-D smoothing filter (filter3d.compute_3D_filter): one more column, and only on a model that carries one —
+    # every other model writes the file it always wrote
+    if getattr(model, "filter_3D", None) is not None:
+        cols["filter_3D"] = cpu(model.filter_3D).reshape(P).astype(np.float32)
     write_ply(path, cols)
 
 
@@ -144,6 +149,8 @@ def load_ply(model, path, device="cuda", max_sh_degree=3, n_lvl_occ=4, n_lvl_dc=
     model.base_gaussian_mask = torch.from_numpy(np.asarray(v["base_gaussian_mask"]).astype(np.bool_)).to(device)
     model.max_pixel_sizes = t(col("max_pixel_sizes"))
     model.min_pixel_sizes = t(col("min_pixel_sizes"))
+    if "filter_3D" in names:
+        model.filter_3D = t(col("filter_3D")[:, None])
     model.active_sh_degree = max_sh_degree
     model.max_sh_degree = max_sh_degree
     return model

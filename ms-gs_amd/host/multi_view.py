@@ -27,7 +27,7 @@ GPU changes.
 import torch
 
 import diff_gaussian_rasterization as dgr
-from gaussian_renderer import render as _render
+from gaussian_renderer import _refuse_filter_3d, render as _render
 
 _GETTERS = ("get_features", "get_opacity", "get_scaling", "get_rotation")
 # the leaf parameters of the reference's GaussianModel (/root/reference/scene/gaussian_model.py:53-58)
@@ -119,6 +119,7 @@ class ViewPipeline:
         getters' autograd nodes are then never run.  If autograd had to run them, the first view's backward would free the graph
         the other views share.  So the sweep shares them only when the op will recognise them (checked here on the model's own
         tensors) and the pipeline settings keep the SH / covariance inside the op; train_views verifies every view afterwards."""
+        _refuse_filter_3d(pc, "ViewPipeline")          # (DESIGN.md 2, M16: the pipelined sweeps render the model's own getters)
         if not share_getters:
             return pc
         shared = SharedGetters(pc).prime()
