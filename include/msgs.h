@@ -570,6 +570,39 @@ int msgs_smoothing_filter_backward(int32_t P, int32_t raw, const float* scales, 
                                    const float* dL_dscales_eff, const float* dL_dopacities_eff, float* dL_dscales,
                                    float* dL_dopacities, void* stream);
 
+/* ---- normal maps: Gaussian normals and depth-to-normal (DESIGN.md SPEC M17, 4.18) ------------------------------------------ */
+/* msgs_gaussian_normals_forward: normals [P,3] float32, the shortest axis of every Gaussian turned towards the camera.
+ *     k = 0; if s_1 < s_k: k = 1; if s_2 < s_k: k = 2        (strict; comparisons only: log-scales, activated and filtered
+ *                                                             scales select the same axis)
+ *     q = r / max(||r||, 1e-12),   n = column k of R(q)      (the R of Sigma = R S^2 R^T; raw or normalised quaternions)
+ *     sigma = -1 iff n . (campos - p) < 0, else +1
+ *     world != 0: sigma n;   world == 0: the view-space vector sigma sum_j n_j viewmatrix[4 j + c]
+ * viewmatrix [16] (the layout of msgs_view_t::viewmatrix) and campos [3] are DEVICE pointers.  A row with a non-finite input or
+ * result is exactly (0, 0, 0).  flags [P] (one byte per row: k, the sign, valid) is all the backward keeps.
+ * msgs_gaussian_normals_backward writes every row of dL_drotations [P,4]: through column k of R and through the normalisation
+ * (no gradient through the norm where its clamp is active); k, sigma and the camera are constants, an invalid row gets zeros.
+ * means3D and scales have no gradient.
+ *
+ * msgs_depth_normal_forward: normal [3,H,W] float32 from a map depth [H,W] of view depths.  Pixel (x, y) back-projects to
+ * P = (a_x z, a_y z, z), a_x = ((2 x + 1) / W - 1) tanfovx, a_y likewise; u = P(x, y+1) - P(x, y-1), v = P(x+1, y) - P(x-1, y),
+ * c = u x v, n = c / ||c|| (a fronto-parallel plane: (0, 0, -1)).  Valid iff 1 <= x <= W-2, 1 <= y <= H-2, the four depths are
+ * finite and > 0 and ||c||^2 is finite and > 0; every other pixel is exactly 0.  world != 0: rotated into world space,
+ * w_j = sum_k viewmatrix[4 j + k] n_k (viewmatrix: DEVICE pointer, may be NULL with world == 0).
+ * msgs_depth_normal_backward writes every pixel of dL_ddepth [H,W]: a gather, in a fixed order, of the shares of the (up to
+ * four) valid stencils a pixel belongs to; no atomics, the same bits on every run.  The camera is a constant.
+ * All four: everything on `stream`, no synchronisation; P == 0 / W H == 0: nothing is launched. */
+#define MSGS_DEPTH_NORMAL_TILE_W 64            /* the tile of the depth-to-normal kernels (tests place seams from these) */
+#define MSGS_DEPTH_NORMAL_TILE_H 8
+int msgs_gaussian_normals_forward(int32_t P, const float* means3D, const float* scales, const float* rotations,
+                                  const float* viewmatrix, const float* campos, int32_t world, float* normals, uint8_t* flags,
+                                  void* stream);
+int msgs_gaussian_normals_backward(int32_t P, const float* rotations, const uint8_t* flags, const float* viewmatrix,
+                                   int32_t world, const float* dL_dnormals, float* dL_drotations, void* stream);
+int msgs_depth_normal_forward(int32_t W, int32_t H, float tanfovx, float tanfovy, const float* depth, const float* viewmatrix,
+                              int32_t world, float* normal, void* stream);
+int msgs_depth_normal_backward(int32_t W, int32_t H, float tanfovx, float tanfovy, const float* depth, const float* viewmatrix,
+                               int32_t world, const float* dL_dnormal, float* dL_ddepth, void* stream);
+
 /* msgs_backward_per_gaussian: the per-Gaussian half of msgs_backward ALONE (2-D covariance backward, projection, SH,
  * scale / quaternion chain — upstream's computeCov2DCUDA + preprocessCUDA backward, SURVEY 2.2 K8 + K9) on per-Gaussian
  * 2-D gradients supplied by the caller instead of the blend backward's sums: sums2d [P,9] DOUBLES (device) =

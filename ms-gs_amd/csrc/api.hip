@@ -1119,6 +1119,60 @@ int msgs_smoothing_filter_backward(int32_t P, int32_t raw, const float* scales, 
 }
 }  // extern "C"
 
+// ---- normal maps: Gaussian normals and depth-to-normal (SPEC M17) ----
+namespace {
+// the kernels index pixels in int and tile the image with a 2-D grid
+bool depth_normal_shape_ok(int32_t W, int32_t H) {
+    if (W < 0 || H < 0) return false;
+    if (W == 0 || H == 0) return true;
+    return (int64_t)W * H <= INT32_MAX / 4 && (H + MSGS_DEPTH_NORMAL_TILE_H - 1) / MSGS_DEPTH_NORMAL_TILE_H <= 65535;
+}
+}  // namespace
+
+extern "C" {
+int msgs_gaussian_normals_forward(int32_t P, const float* means3D, const float* scales, const float* rotations,
+                                  const float* viewmatrix, const float* campos, int32_t world, float* normals, uint8_t* flags,
+                                  void* stream) {
+    if (P < 0) return MSGS_ERR_INVALID_ARG;
+    if (P == 0) return MSGS_OK;
+    if (!means3D || !scales || !rotations || !viewmatrix || !campos || !normals || !flags) return MSGS_ERR_INVALID_ARG;
+    if ((uintptr_t)rotations & 15) return MSGS_ERR_INVALID_ARG;          // read as float4 rows
+    HIP_TRY(launch_gaussian_normals_forward(P, means3D, scales, rotations, viewmatrix, campos, world != 0, normals, flags,
+                                            (hipStream_t)stream));
+    return MSGS_OK;
+}
+
+int msgs_gaussian_normals_backward(int32_t P, const float* rotations, const uint8_t* flags, const float* viewmatrix,
+                                   int32_t world, const float* dL_dnormals, float* dL_drotations, void* stream) {
+    if (P < 0) return MSGS_ERR_INVALID_ARG;
+    if (P == 0) return MSGS_OK;
+    if (!rotations || !flags || !dL_dnormals || !dL_drotations || (!world && !viewmatrix)) return MSGS_ERR_INVALID_ARG;
+    if (((uintptr_t)rotations | (uintptr_t)dL_drotations) & 15) return MSGS_ERR_INVALID_ARG;
+    HIP_TRY(launch_gaussian_normals_backward(P, rotations, flags, viewmatrix, world != 0, dL_dnormals, dL_drotations,
+                                             (hipStream_t)stream));
+    return MSGS_OK;
+}
+
+int msgs_depth_normal_forward(int32_t W, int32_t H, float tanfovx, float tanfovy, const float* depth, const float* viewmatrix,
+                              int32_t world, float* normal, void* stream) {
+    if (!depth_normal_shape_ok(W, H)) return MSGS_ERR_INVALID_ARG;
+    if (W == 0 || H == 0) return MSGS_OK;
+    if (!depth || !normal || (world && !viewmatrix)) return MSGS_ERR_INVALID_ARG;
+    HIP_TRY(launch_depth_normal_forward(W, H, tanfovx, tanfovy, depth, viewmatrix, world != 0, normal, (hipStream_t)stream));
+    return MSGS_OK;
+}
+
+int msgs_depth_normal_backward(int32_t W, int32_t H, float tanfovx, float tanfovy, const float* depth, const float* viewmatrix,
+                               int32_t world, const float* dL_dnormal, float* dL_ddepth, void* stream) {
+    if (!depth_normal_shape_ok(W, H)) return MSGS_ERR_INVALID_ARG;
+    if (W == 0 || H == 0) return MSGS_OK;
+    if (!depth || !dL_dnormal || !dL_ddepth || (world && !viewmatrix)) return MSGS_ERR_INVALID_ARG;
+    HIP_TRY(launch_depth_normal_backward(W, H, tanfovx, tanfovy, depth, viewmatrix, world != 0, dL_dnormal, dL_ddepth,
+                                         (hipStream_t)stream));
+    return MSGS_OK;
+}
+}  // extern "C"
+
 namespace {
 int backward_impl(const msgs_view_t* view, const msgs_gaussians_t* g, const int32_t* radii, const void* geom_v,
                   size_t geom_bytes, int64_t D, const void* binning_v, size_t binning_bytes, const void* image_v,

@@ -893,6 +893,17 @@ hipError_t launch_smoothing_filter_forward(int P, bool raw, const float* scales,
 hipError_t launch_smoothing_filter_backward(int P, bool raw, const float* scales, const float* opacities, const float* filter_3D,
                                             const float* dL_dscales_eff, const float* dL_dopacities_eff, float* dL_dscales,
                                             float* dL_dopacities, hipStream_t s);
+// normals.hip — msgs_gaussian_normals_* and msgs_depth_normal_* (SPEC M17): per-Gaussian normals (flags: one byte per row for
+// the backward) and the normal map of a depth map with its gathered backward; viewmatrix / campos are device pointers
+hipError_t launch_gaussian_normals_forward(int P, const float* means3D, const float* scales, const float* rotations,
+                                           const float* viewmatrix, const float* campos, bool world, float* normals,
+                                           uint8_t* flags, hipStream_t s);
+hipError_t launch_gaussian_normals_backward(int P, const float* rotations, const uint8_t* flags, const float* viewmatrix,
+                                            bool world, const float* dL_dnormals, float* dL_drotations, hipStream_t s);
+hipError_t launch_depth_normal_forward(int W, int H, float tanfovx, float tanfovy, const float* depth, const float* viewmatrix,
+                                       bool world, float* normal, hipStream_t s);
+hipError_t launch_depth_normal_backward(int W, int H, float tanfovx, float tanfovy, const float* depth, const float* viewmatrix,
+                                        bool world, const float* dL_dnormal, float* dL_ddepth, hipStream_t s);
 // msgs_median_depth_* (SPEC M15): the median-depth map [H,W] and the id map of its Gaussians (front-to-back replay with early
 // exit); the backward adds dL/dmedian_depth of every pixel to slot 9 (dL/dz) of its Gaussian's record
 hipError_t launch_blend_median_depth_forward(const ViewParams& vp, const char* geom, const uint32_t* ids, const uint2* ranges,

@@ -29,7 +29,8 @@ from . import _backend as _C
 
 __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "rasterize_gaussians_raw",
            "deferred_forward", "GradAccumulator", "set_grad_accumulator", "ContributionScores", "ContributionAccumulator",
-           "screen_compensation", "compute_3d_filter", "smoothing_filter", "FILTER3D_CAMERA_CHUNK"]
+           "screen_compensation", "compute_3d_filter", "smoothing_filter", "FILTER3D_CAMERA_CHUNK",
+           "gaussian_normals", "depth_to_normal", "DEPTH_NORMAL_TILE_W", "DEPTH_NORMAL_TILE_H"]
 
 
 class GaussianRasterizationSettings(NamedTuple):
@@ -1881,6 +1882,146 @@ def smoothing_filter(scales, opacities, filter_3D, raw=False):
     # not the reference's getters: the rasterizer skips the chained mode for them without its warning
     s_eff._msgs_filtered = o_eff._msgs_filtered = True
     return s_eff, o_eff
+
+
+# Normal maps (4.18): the two halves of a depth-normal consistency loss.  gaussian_normals() gives every
+# Gaussian the normal that with_features() splats; depth_to_normal() turns a depth map into the normals of the surface it
+# describes.  Both are small streaming kernels outside the rasterizer.
+DEPTH_NORMAL_TILE_W, DEPTH_NORMAL_TILE_H = _C.DEPTH_NORMAL_TILE_W, _C.DEPTH_NORMAL_TILE_H
+_normals_probe = None              # tests: a callable (name) run in front of every msgs_gaussian_normals_* / msgs_depth_normal_* call
+_HIP_ONLY = "diff_gaussian_rasterization (MI355X build): tensors must live on a HIP device"
+
+
+def _camera_constant(t, n, dev, name):
+    """viewmatrix / campos of the settings as `n` contiguous float32 on `dev`, detached: constants of both functions"""
+    t = torch.as_tensor(t).detach()
+    if t.numel() != n:
+        raise ValueError(f"{name} must have {n} elements, got {tuple(t.shape)}")
+    return _f32c(t.to(dev)).reshape(-1)
+
+
+class _GaussianNormals(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, means3D, scales, rotations, viewmatrix, campos, world):
+        P, dev = int(means3D.shape[0]), means3D.device
+        if dev.type != "cuda":
+            raise RuntimeError(_HIP_ONLY)
+        ctx.P, ctx.dev, ctx.world, ctx.shape = P, dev, bool(world), rotations.shape
+        normals = torch.empty(P, 3, dtype=torch.float32, device=dev)
+        if P == 0:
+            return normals
+        m, s, r = _f32c(means3D.detach()), _f32c(scales.detach()), _f32c(rotations.detach())
+        vm, cp = _camera_constant(viewmatrix, 16, dev, "viewmatrix"), _camera_constant(campos, 3, dev, "campos")
+        flags = torch.empty(P, dtype=torch.uint8, device=dev)
+        if _normals_probe is not None:
+            _normals_probe("msgs_gaussian_normals_forward")
+        with _on_device(dev):
+            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            _C.check(_C.lib.msgs_gaussian_normals_forward(P, _ptr(m), _ptr(s), _ptr(r), _ptr(vm), _ptr(cp), int(ctx.world),
+                                                          _ptr(normals), _ptr(flags), stream), "msgs_gaussian_normals_forward")
+        ctx.save_for_backward(r, flags, vm)
+        return normals
+
+    @staticmethod
+    def backward(ctx, g_normals):
+        P, dev = ctx.P, ctx.dev
+        if P == 0 or g_normals is None:
+            return None, None, torch.zeros(ctx.shape, dtype=torch.float32, device=dev), None, None, None
+        r, flags, vm = ctx.saved_tensors
+        g = _f32c(g_normals)
+        g_rot = torch.empty(P, 4, dtype=torch.float32, device=dev)
+        if _normals_probe is not None:
+            _normals_probe("msgs_gaussian_normals_backward")
+        with _on_device(dev):
+            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            _C.check(_C.lib.msgs_gaussian_normals_backward(P, _ptr(r), _ptr(flags), _ptr(vm), int(ctx.world), _ptr(g),
+                                                           _ptr(g_rot), stream), "msgs_gaussian_normals_backward")
+        return None, None, g_rot.view(ctx.shape), None, None, None
+
+
+def gaussian_normals(means3D, scales, rotations, raster_settings, world=False):
+    """normals [P,3] float32: the shortest axis of every Gaussian, turned towards the camera of `raster_settings` — what
+    2DGS / GOF / PGSR splat as rend_normal (feed it to GaussianRasterizer.with_features()).
+        k = 0; if s_1 < s_k: k = 1; if s_2 < s_k: k = 2        (strict: ties go to the lowest index)
+        q = r / max(||r||, 1e-12),  n = column k of R(q)       (the R of Sigma = R S^2 R^T)
+        sigma = -1 iff n . (campos - p) < 0, else +1
+    world=True returns sigma n; by default the vector is rotated into view space with the 3x3 block of viewmatrix, the space
+    depth_to_normal() works in.  `scales` only enter the comparison, so log-scales, activated scales and smoothing_filter()ed
+    scales select the same axis, and `rotations` are normalised here (harmless on the model's getter): the leaves may be passed
+    as they are.  A row with a non-finite input or result is exactly (0, 0, 0) and has no gradient.  Differentiable in
+    `rotations` only — through column k of R and the normalisation; the selection, the sign and the camera are constants, and
+    means3D / scales receive nothing.  One streaming HIP kernel forward and one backward.  float64 and
+    strided inputs are converted; ValueError when the row counts differ."""
+    if means3D.dim() != 2 or means3D.shape[1] != 3:
+        raise ValueError("gaussian_normals: means3D must be [P,3]")
+    P = int(means3D.shape[0])
+    if scales.dim() != 2 or tuple(scales.shape) != (P, 3):
+        raise ValueError(f"gaussian_normals: scales must be [{P},3], got {tuple(scales.shape)}")
+    if rotations.dim() != 2 or tuple(rotations.shape) != (P, 4):
+        raise ValueError(f"gaussian_normals: rotations must be [{P},4], got {tuple(rotations.shape)}")
+    return _GaussianNormals.apply(means3D, scales, rotations, raster_settings.viewmatrix, raster_settings.campos, bool(world))
+
+
+class _DepthToNormal(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, depth, viewmatrix, W, H, tanfovx, tanfovy, world):
+        dev = depth.device
+        if dev.type != "cuda":
+            raise RuntimeError(_HIP_ONLY)
+        ctx.dev, ctx.world, ctx.geometry, ctx.shape = dev, bool(world), (W, H, float(tanfovx), float(tanfovy)), depth.shape
+        normal = torch.empty(3, H, W, dtype=torch.float32, device=dev)
+        if W * H == 0:
+            return normal
+        z = _f32c(depth.detach())
+        vm = _camera_constant(viewmatrix, 16, dev, "viewmatrix") if world else None
+        if _normals_probe is not None:
+            _normals_probe("msgs_depth_normal_forward")
+        with _on_device(dev):
+            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            _C.check(_C.lib.msgs_depth_normal_forward(W, H, ctx.geometry[2], ctx.geometry[3], _ptr(z), _ptr(vm), int(ctx.world),
+                                                      _ptr(normal), stream), "msgs_depth_normal_forward")
+        ctx.save_for_backward(z, *(() if vm is None else (vm,)))
+        return normal
+
+    @staticmethod
+    def backward(ctx, g_normal):
+        dev = ctx.dev
+        W, H, tx, ty = ctx.geometry
+        if W * H == 0 or g_normal is None:
+            return (torch.zeros(ctx.shape, dtype=torch.float32, device=dev),) + (None,) * 6
+        z = ctx.saved_tensors[0]
+        vm = ctx.saved_tensors[1] if ctx.world else None
+        g = _f32c(g_normal)
+        g_depth = torch.empty(H, W, dtype=torch.float32, device=dev)
+        if _normals_probe is not None:
+            _normals_probe("msgs_depth_normal_backward")
+        with _on_device(dev):
+            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            _C.check(_C.lib.msgs_depth_normal_backward(W, H, tx, ty, _ptr(z), _ptr(vm), int(ctx.world), _ptr(g), _ptr(g_depth),
+                                                       stream), "msgs_depth_normal_backward")
+        return (g_depth.view(ctx.shape),) + (None,) * 6
+
+
+def depth_to_normal(depth, raster_settings, world=False):
+    """normal [3,H,W] float32 of the surface a map of view depths `depth` [H,W] describes (median_depth, depth / alpha, a sensor
+    map ...) under the camera of `raster_settings` (image_width, image_height, tanfovx, tanfovy): 2DGS's depth_to_normal, the
+    surf_normal of a depth-normal consistency loss.  Pixel (x, y) back-projects to P = (a_x z, a_y z, z) with
+    a_x = ((2 x + 1) / W - 1) tanfovx, the ray through the pixel centre;
+        u = P(x, y+1) - P(x, y-1),   v = P(x+1, y) - P(x-1, y),   n = u x v / ||u x v||
+    so a fronto-parallel plane gives (0, 0, -1), facing the camera like gaussian_normals().  The pixel's own depth does not
+    enter.  A pixel on the image border, with a stencil depth that is not finite and > 0 (a hole) or with a degenerate cross
+    product is exactly 0 and passes no gradient.  world=True rotates the map into world space with the 3x3 block of viewmatrix
+    (w_j = sum_k V[4 j + k] n_k).  Differentiable in `depth`; the camera is a constant.  The backward is a gather in a fixed
+    order, without atomics: the same bits on every run.  One tiled HIP kernel forward and one backward.
+    float64 and strided maps are converted and a [1,H,W] map is taken as [H,W]; ValueError when the shape is not the settings'."""
+    H, W = int(raster_settings.image_height), int(raster_settings.image_width)
+    if depth.dim() == 3 and depth.shape[0] == 1:
+        depth = depth[0]
+    if depth.dim() != 2 or tuple(depth.shape) != (H, W):
+        raise ValueError(f"depth_to_normal: depth must be [{H},{W}] (image_height, image_width of the settings), got "
+                         f"{tuple(depth.shape)}")
+    return _DepthToNormal.apply(depth, raster_settings.viewmatrix if world else None, W, H, float(raster_settings.tanfovx),
+                                float(raster_settings.tanfovy), bool(world))
 
 
 # Contribution scores (DESIGN.md 2, M11; 4.11): what every Gaussian did to the images of one or many views, the criterion of

@@ -84,6 +84,8 @@ class DensifyStats(C.Structure):
 # msgs_filter3d_sweep (include/msgs.h): floats per camera row, camera rows staged per pass of the sweep, the two rules
 FILTER3D_CAMERA_FLOATS, FILTER3D_CAMERA_CHUNK = 20, 64
 FILTER3D_RULES = {"per_camera": 0, "mip_splatting": 1}
+# msgs_depth_normal_* (include/msgs.h): the tile of the depth-to-normal kernels
+DEPTH_NORMAL_TILE_W, DEPTH_NORMAL_TILE_H = 64, 8
 
 DENSIFY_PRUNE, DENSIFY_GROW, DENSIFY_PRUNE_MASK, DENSIFY_APPEND = 0, 1, 2, 3
 (DR_COPY, DR_ZERO, DR_COPY_CLEAR_COL, DR_SPLIT_XYZ, DR_SPLIT_SCALE, DR_SPLIT_DIV, DR_GROW_OPACITY, DR_GROW_SCALE, DR_GROW_MUL,
@@ -240,6 +242,14 @@ def _load():
     lib.msgs_smoothing_filter_forward.argtypes = [C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp]
     lib.msgs_smoothing_filter_backward.restype = C.c_int
     lib.msgs_smoothing_filter_backward.argtypes = [C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.msgs_gaussian_normals_forward.restype = C.c_int
+    lib.msgs_gaussian_normals_forward.argtypes = [C.c_int32, vp, vp, vp, vp, vp, C.c_int32, vp, vp, vp]
+    lib.msgs_gaussian_normals_backward.restype = C.c_int
+    lib.msgs_gaussian_normals_backward.argtypes = [C.c_int32, vp, vp, vp, C.c_int32, vp, vp, vp]
+    lib.msgs_depth_normal_forward.restype = C.c_int
+    lib.msgs_depth_normal_forward.argtypes = [C.c_int32, C.c_int32, C.c_float, C.c_float, vp, vp, C.c_int32, vp, vp]
+    lib.msgs_depth_normal_backward.restype = C.c_int
+    lib.msgs_depth_normal_backward.argtypes = [C.c_int32, C.c_int32, C.c_float, C.c_float, vp, vp, C.c_int32, vp, vp, vp]
     lib.msgs_backward_per_gaussian.restype = C.c_int
     lib.msgs_backward_per_gaussian.argtypes = [C.POINTER(View), C.POINTER(Gaussians), vp, vp, sz, vp, C.POINTER(Grads), vp]
     lib.msgs_sh_grad_from_views.restype = C.c_int
@@ -320,6 +330,8 @@ EXPORTS = ("msgs_abi_version", "msgs_error_string", "msgs_geom_bytes", "msgs_sta
            "msgs_screen_compensation_forward", "msgs_screen_compensation_backward", "msgs_screen_compensation_scratch_bytes",
            "msgs_filter3d_scratch_bytes", "msgs_filter3d_sweep", "msgs_smoothing_filter_forward",
            "msgs_smoothing_filter_backward",
+           "msgs_gaussian_normals_forward", "msgs_gaussian_normals_backward", "msgs_depth_normal_forward",
+           "msgs_depth_normal_backward",
            "msgs_set_depth_sort", "msgs_depth_sort_stats")
 
 
