@@ -57,6 +57,7 @@ extern "C" {
 #define MSGS_ERR_TOO_MANY (-3)     /* more than 2^32-1 tile instances                                */
 #define MSGS_ERR_SH_DEGREE (-4)    /* sh_degree outside 0..3 or (sh_degree+1)^2 > sh_coeffs          */
 #define MSGS_ERR_INTERNAL (-5)     /* a bounded inter-workgroup wait expired (sort/scan look-back)     */
+#define MSGS_ERR_NO_WEIGHT (-6)    /* msgs_mcmc_sample: no row of positive weight to draw from         */
 
 #define MSGS_TILE 16               /* 16x16 pixel tiles                     */
 
@@ -908,6 +909,69 @@ typedef struct msgs_densify_apply {
     const msgs_densify_tensor_t* tensors;
 } msgs_densify_apply_t;
 int msgs_densify_apply(const msgs_densify_apply_t* apply, const void* scratch, size_t scratch_bytes, void* stream);
+
+/* ---- MCMC densification: sampling, relocation, capped growth, position noise (DESIGN.md SPEC M18, 4.19) -----------------
+ * The model surgery of "3D Gaussian Splatting as Markov Chain Monte Carlo" for a trainer with a fixed budget of Gaussians.
+ *
+ * Sampling.  w_i = sigmoid(opacity_i) in double, 0 where dead[i] (dead may be NULL) or the logit is NaN; the CDF is the inclusive
+ * prefix sum of w in double, summed in one fixed order, monotone, and exactly flat over rows of weight 0.  Draw j takes the first
+ * row whose CDF exceeds u_j * total (u float64 in [0,1)); a product that rounds up to the total takes the last row of positive
+ * weight.  A row of weight 0 is never taken; the same inputs give the same bits on every run.
+ *   msgs_mcmc_prepare   builds the CDF and the stable list of dead rows in `scratch` and reads back
+ *                       counts_host[4] = { dead rows, rows of positive weight, 0, 0 }: the call's only host synchronisation.
+ *   msgs_mcmc_sample    prepare + draw: source[n] int32 (row of each draw), count[P] int32 (draws per row).  n == 0 launches
+ *                       nothing; no row of positive weight: MSGS_ERR_NO_WEIGHT, source and count are not written.
+ *
+ * Relocation rule, for a row drawn count times, N = min(count + 1, MSGS_MCMC_N_MAX), logit x, log-scales s, in double:
+ *     log(1 - o) = -softplus(x),  o_new = -expm1(log(1 - o) / N),
+ *     D = sum_{i=1..N} sum_{k=0..i-1} C(i-1, k) (-1)^k / sqrt(k+1) o_new^(k+1),  c = o / D,
+ *     s_new = s + log c (all three axes),  x_new = logit(clamp(o_new, 0.005, 1 - 2^-24)) = log o_new - log(1 - o) / N unclamped.
+ *
+ *   msgs_mcmc_relocate  after msgs_mcmc_prepare on the same scratch and the same opacity: draws n rows with u [n], computes
+ *                       (x_new, s_new, c) of every drawn row from its old values into scratch, then writes
+ *                         in_place != 0: dead row number j (row order) <- draw j; n must be the number of dead rows
+ *                         in_place == 0: row j of every tensor's `fresh` block <- draw j (tensors with fresh == NULL: skipped)
+ *                       by each tensor's rule, and every drawn row itself: x_new, s_new, pixel sizes * c, and zeros in its rows of
+ *                       exp_avg / exp_avg_sq wherever a tensor carries them.  Rows neither written nor drawn are not touched.
+ *                       No host synchronisation.  n <= P.
+ *
+ *   msgs_mcmc_noise     xyz += R S^2 R^T xi * gain / (1 + exp(-100 (0.005 - sigmoid(opacity)))) in place, float32; S = exp(scaling),
+ *                       R the rotation of rotation / max(|rotation|, 1e-12) as msgs_forward* forms it, xi = draws [P,3],
+ *                       gain = noise_lr * xyz_lr.  One streaming launch, no synchronisation. */
+#define MSGS_MCMC_N_MAX 51
+#define MSGS_MCMC_MAX_TENSORS 16
+#define MSGS_MR_COPY 0               /* the source's row                              */
+#define MSGS_MR_ZERO 1               /* zeros (false for bool)                        */
+#define MSGS_MR_OPACITY 2            /* x_new of the source            (width 1)      */
+#define MSGS_MR_SCALE 3              /* s_new of the source            (width 3)      */
+#define MSGS_MR_PIX_MAX 4            /* the source's max_pixel_sizes * c (width 1)    */
+#define MSGS_MR_PIX_MIN 5            /* the source's min_pixel_sizes * c (width 1)    */
+typedef struct msgs_mcmc_tensor {
+    void* data;                      /* [P, width] the model's tensor: source rows are read; written rows when in place */
+    void* fresh;                     /* [n, width] the new rows when not in place, or NULL */
+    float* exp_avg;                  /* [P, width] optimizer moments zeroed in drawn rows, or NULL */
+    float* exp_avg_sq;
+    int32_t width;                   /* elements per row */
+    int32_t elem_bytes;              /* 4 float32, 8 int64, 1 bool (COPY and ZERO only) */
+    int32_t rule;                    /* MSGS_MR_*; exactly one OPACITY and one SCALE tensor */
+    int32_t reserved;
+} msgs_mcmc_tensor_t;
+typedef struct msgs_mcmc_relocate {
+    int64_t P;
+    int64_t n;                       /* draws */
+    int32_t in_place;
+    int32_t n_tensors;
+    const double* u;                 /* [n] uniforms in [0,1) */
+    const msgs_mcmc_tensor_t* tensors;
+} msgs_mcmc_relocate_t;
+size_t msgs_mcmc_scratch_bytes(int64_t P);
+int msgs_mcmc_prepare(int64_t P, const float* opacity, const uint8_t* dead, void* scratch, size_t scratch_bytes,
+                      int64_t* counts_host, void* stream);
+int msgs_mcmc_sample(int64_t P, const float* opacity, const uint8_t* dead, int64_t n, const double* u, int32_t* source,
+                     int32_t* count, void* scratch, size_t scratch_bytes, void* stream);
+int msgs_mcmc_relocate(const msgs_mcmc_relocate_t* r, void* scratch, size_t scratch_bytes, void* stream);
+int msgs_mcmc_noise(int64_t P, float* xyz, const float* scaling, const float* rotation, const float* opacity,
+                    const float* draws, float gain, void* stream);
 
 /* ---- fused photometric loss ----------------------------------------------------------------
  * loss = (1 - lambda_dssim) * l1_loss(img, gt) + lambda_dssim * (1 - ssim(img, gt))   (/root/reference/train.py:209-211)

@@ -84,6 +84,7 @@ const char* msgs_error_string(int code) {
         case MSGS_ERR_TOO_MANY: return "more than 2^32-1 tile instances";
         case MSGS_ERR_SH_DEGREE: return "sh_degree must be 0..3 and (sh_degree+1)^2 <= sh_coeffs";
         case MSGS_ERR_INTERNAL: return "internal error: a look-back wait in the sort/scan kernels timed out";
+        case MSGS_ERR_NO_WEIGHT: return "no row of positive weight to sample from";
         default: return code > 0 ? hipGetErrorString((hipError_t)code) : "unknown error";
     }
 }
@@ -1477,6 +1478,51 @@ int msgs_densify_apply(const msgs_densify_apply_t* apply, const void* scratch, s
     if (int rc = densify_check_apply(*apply)) return rc;
     if (scratch_bytes < densify_scratch_bytes(apply->P, apply->n_append)) return MSGS_ERR_CAPACITY;
     return densify_apply(*apply, (const char*)scratch, (hipStream_t)stream);
+}
+
+// ---- MCMC densification: sampling, relocation, position noise (SPEC M18) ----
+size_t msgs_mcmc_scratch_bytes(int64_t P) { return mcmc_scratch_bytes(P > 0 ? P : 0); }
+
+static int mcmc_rows_ok(int64_t P, const float* opacity, const void* scratch, size_t scratch_bytes) {
+    if (P < 0 || !scratch || (P > 0 && !opacity)) return MSGS_ERR_INVALID_ARG;
+    if (P >= ((int64_t)1 << 31)) return MSGS_ERR_TOO_MANY;
+    if (scratch_bytes < mcmc_scratch_bytes(P)) return MSGS_ERR_CAPACITY;
+    return MSGS_OK;
+}
+
+int msgs_mcmc_prepare(int64_t P, const float* opacity, const uint8_t* dead, void* scratch, size_t scratch_bytes,
+                      int64_t* counts_host, void* stream) {
+    if (!counts_host) return MSGS_ERR_INVALID_ARG;
+    if (int rc = mcmc_rows_ok(P, opacity, scratch, scratch_bytes)) return rc;
+    counts_host[0] = counts_host[1] = counts_host[2] = counts_host[3] = 0;
+    if (P == 0) return MSGS_OK;
+    return mcmc_prepare(P, opacity, dead, (char*)scratch, counts_host, (hipStream_t)stream);
+}
+
+int msgs_mcmc_sample(int64_t P, const float* opacity, const uint8_t* dead, int64_t n, const double* u, int32_t* source,
+                     int32_t* count, void* scratch, size_t scratch_bytes, void* stream) {
+    if (n < 0 || (n > 0 && (!u || !source || !count))) return MSGS_ERR_INVALID_ARG;
+    if (int rc = mcmc_rows_ok(P, opacity, scratch, scratch_bytes)) return rc;
+    if (n == 0) return MSGS_OK;
+    if (P == 0) return MSGS_ERR_NO_WEIGHT;
+    if (n >= ((int64_t)1 << 31)) return MSGS_ERR_TOO_MANY;
+    return mcmc_sample(P, opacity, dead, n, u, source, count, (char*)scratch, (hipStream_t)stream);
+}
+
+int msgs_mcmc_relocate(const msgs_mcmc_relocate_t* r, void* scratch, size_t scratch_bytes, void* stream) {
+    if (!r || !scratch) return MSGS_ERR_INVALID_ARG;
+    if (int rc = mcmc_check_relocate(*r)) return rc;
+    if (scratch_bytes < mcmc_scratch_bytes(r->P)) return MSGS_ERR_CAPACITY;
+    if (r->P == 0 || r->n == 0) return MSGS_OK;
+    return mcmc_relocate(*r, (char*)scratch, (hipStream_t)stream);
+}
+
+int msgs_mcmc_noise(int64_t P, float* xyz, const float* scaling, const float* rotation, const float* opacity,
+                    const float* draws, float gain, void* stream) {
+    if (P < 0 || (P > 0 && (!xyz || !scaling || !rotation || !opacity || !draws))) return MSGS_ERR_INVALID_ARG;
+    if (P >= ((int64_t)1 << 31)) return MSGS_ERR_TOO_MANY;
+    HIP_TRY(launch_mcmc_noise(P, xyz, scaling, rotation, opacity, draws, gain, (hipStream_t)stream));
+    return MSGS_OK;
 }
 
 static int loss_args_ok(const float* img, const float* gt, int32_t C, int32_t H, int32_t W, float lambda) {

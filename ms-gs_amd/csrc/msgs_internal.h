@@ -807,6 +807,16 @@ int densify_check_apply(const msgs_densify_apply_t& a);
 int densify_select(const msgs_densify_select_t& s, char* scratch, int64_t* counts_host, hipStream_t st);
 int densify_apply(const msgs_densify_apply_t& a, const char* scratch, hipStream_t st);
 
+// mcmc.hip
+size_t mcmc_scratch_bytes(int64_t P);
+int mcmc_prepare(int64_t P, const float* opacity, const uint8_t* dead, char* scratch, int64_t* counts_host, hipStream_t st);
+int mcmc_sample(int64_t P, const float* opacity, const uint8_t* dead, int64_t n, const double* u, int32_t* source, int32_t* count,
+                char* scratch, hipStream_t st);
+int mcmc_check_relocate(const msgs_mcmc_relocate_t& a);
+int mcmc_relocate(const msgs_mcmc_relocate_t& a, char* scratch, hipStream_t st);
+hipError_t launch_mcmc_noise(int64_t P, float* xyz, const float* scaling, const float* rotation, const float* opacity,
+                             const float* draws, float gain, hipStream_t st);
+
 // loss.hip
 size_t loss_scratch_bytes(int C, int H, int W);
 void ssim_window_host(float w[11]);

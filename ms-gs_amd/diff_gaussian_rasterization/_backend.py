@@ -114,6 +114,22 @@ class DensifyApply(C.Structure):         # msgs_densify_apply_t
                 ("tensors", C.POINTER(DensifyTensor))]
 
 
+# msgs_mcmc_* (include/msgs.h): the error of a draw from no weight, the cap of N, the rules of msgs_mcmc_tensor_t
+ERR_NO_WEIGHT = -6
+MCMC_N_MAX, MCMC_MAX_TENSORS = 51, 16
+MR_COPY, MR_ZERO, MR_OPACITY, MR_SCALE, MR_PIX_MAX, MR_PIX_MIN = range(6)
+
+
+class McmcTensor(C.Structure):           # msgs_mcmc_tensor_t
+    _fields_ = [("data", C.c_void_p), ("fresh", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p),
+                ("width", C.c_int32), ("elem_bytes", C.c_int32), ("rule", C.c_int32), ("reserved", C.c_int32)]
+
+
+class McmcRelocate(C.Structure):         # msgs_mcmc_relocate_t
+    _fields_ = [("P", C.c_int64), ("n", C.c_int64), ("in_place", C.c_int32), ("n_tensors", C.c_int32),
+                ("u", C.c_void_p), ("tensors", C.POINTER(McmcTensor))]
+
+
 class Timing(C.Structure):
     _fields_ = [("ev", C.c_void_p * (2 * K_COUNT))]
 
@@ -279,6 +295,16 @@ def _load():
     lib.msgs_densify_select.argtypes = [C.POINTER(DensifySelect), vp, sz, C.POINTER(C.c_int64), vp]
     lib.msgs_densify_apply.restype = C.c_int
     lib.msgs_densify_apply.argtypes = [C.POINTER(DensifyApply), vp, sz, vp]
+    lib.msgs_mcmc_scratch_bytes.restype = sz
+    lib.msgs_mcmc_scratch_bytes.argtypes = [C.c_int64]
+    lib.msgs_mcmc_prepare.restype = C.c_int
+    lib.msgs_mcmc_prepare.argtypes = [C.c_int64, vp, vp, vp, sz, C.POINTER(C.c_int64), vp]
+    lib.msgs_mcmc_sample.restype = C.c_int
+    lib.msgs_mcmc_sample.argtypes = [C.c_int64, vp, vp, C.c_int64, vp, vp, vp, vp, sz, vp]
+    lib.msgs_mcmc_relocate.restype = C.c_int
+    lib.msgs_mcmc_relocate.argtypes = [C.POINTER(McmcRelocate), vp, sz, vp]
+    lib.msgs_mcmc_noise.restype = C.c_int
+    lib.msgs_mcmc_noise.argtypes = [C.c_int64, vp, vp, vp, vp, vp, C.c_float, vp]
     lib.msgs_loss_scratch_bytes.restype = sz
     lib.msgs_loss_scratch_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
     lib.msgs_loss_forward.restype = C.c_int
@@ -332,6 +358,7 @@ EXPORTS = ("msgs_abi_version", "msgs_error_string", "msgs_geom_bytes", "msgs_sta
            "msgs_smoothing_filter_backward",
            "msgs_gaussian_normals_forward", "msgs_gaussian_normals_backward", "msgs_depth_normal_forward",
            "msgs_depth_normal_backward",
+           "msgs_mcmc_scratch_bytes", "msgs_mcmc_prepare", "msgs_mcmc_sample", "msgs_mcmc_relocate", "msgs_mcmc_noise",
            "msgs_set_depth_sort", "msgs_depth_sort_stats")
 
 
