@@ -973,6 +973,44 @@ int msgs_mcmc_relocate(const msgs_mcmc_relocate_t* r, void* scratch, size_t scra
 int msgs_mcmc_noise(int64_t P, float* xyz, const float* scaling, const float* rotation, const float* opacity,
                     const float* draws, float gain, void* stream);
 
+/* ---- bilateral-grid colour correction (DESIGN.md SPEC M19, 4.20) -------------------------------------------------------------
+ * A per-image grid [12,GL,GY,GX] float32 of 3x4 affine colour transforms (channel 4 c + j = entry (c, j)) over (x, y, guide),
+ * sliced per pixel of image [3,H,W] float32 with trilinear interpolation:
+ *     fx = (x + 0.5) / W (GX - 1),  fy = (y + 0.5) / H (GY - 1),  z = 0.299 r + 0.587 g + 0.114 b,  fz = clamp(z, 0, 1) (GL - 1)
+ *     along an axis of size G > 1: cell k = min(floor(f), G - 2), weights 1 - t and t, t = f - k; size 1: coordinate 0, weight 1
+ *     A = sum over the 8 corners of w grid[:, kz, ky, kx],   out_c = A[c,0] r + A[c,1] g + A[c,2] b + A[c,3]
+ * (grid_sample, bilinear, border padding, align_corners).  1 <= GX, GY <= 256, 1 <= GL <= 32, W, H >= 1, W H < 2^29; anything
+ * else returns MSGS_ERR_INVALID_ARG and launches nothing.  A non-finite pixel never indexes outside the grid; only its own
+ * output, its own dL_dimage and the grid nodes it touches can carry its NaN.
+ * msgs_bilagrid_slice_backward: `want` selects the halves (MSGS_BILAGRID_GRAD_IMAGE: dL_dimage [3,H,W], every pixel written;
+ * MSGS_BILAGRID_GRAD_GRID: dL_dgrid [12,GL,GY,GX], every entry written); the pointer of a half that is not wanted is ignored.
+ * dL_dimage is the direct term A[:, :3]^T dL_dout plus, where 0 < z < 1 (open at both ends), the guide term
+ * (sum_c dL_dout_c dout_c/dfz) (GL - 1) (0.299, 0.587, 0.114).  dL_dgrid is summed in one fixed order without float atomics
+ * (per wave, then per node over the slab of wave windows in `scratch`): the same bits on every run.  scratch (>=
+ * msgs_bilagrid_scratch_bytes, 16-byte aligned, no clearing needed) is only used for the grid half.
+ * msgs_bilagrid_tv_forward: tv [1] (device) = sum over the three spatial axes of the mean squared forward difference of the
+ * bank grids [N,12,GL,GY,GX] along that axis (an axis of size 1 adds 0), summed in double in a fixed order; scratch >=
+ * msgs_bilagrid_tv_scratch_bytes(N 12 GL GY GX), 8-byte aligned.  msgs_bilagrid_tv_backward: dL_dgrids = upstream * dtv/dgrids,
+ * a gather; upstream is a DEVICE scalar (NULL = 1).  Everything on `stream`, no synchronisation. */
+#define MSGS_BILAGRID_TILE_W 64            /* the pixel tile of the slice kernels (tests place seams from these) */
+#define MSGS_BILAGRID_TILE_H 16
+#define MSGS_BILAGRID_WINDOW_CELLS 16      /* xy grid nodes a tile's LDS window holds; larger windows read global memory */
+#define MSGS_BILAGRID_MAX_XY 256
+#define MSGS_BILAGRID_MAX_L 32
+#define MSGS_BILAGRID_GRAD_IMAGE 1
+#define MSGS_BILAGRID_GRAD_GRID 2
+size_t msgs_bilagrid_scratch_bytes(int32_t W, int32_t H, int32_t GX, int32_t GY, int32_t GL);
+int msgs_bilagrid_slice_forward(int32_t W, int32_t H, int32_t GX, int32_t GY, int32_t GL, const float* image,
+                                const float* grid, float* out, void* stream);
+int msgs_bilagrid_slice_backward(int32_t W, int32_t H, int32_t GX, int32_t GY, int32_t GL, const float* image,
+                                 const float* grid, const float* dL_dout, int32_t want, float* dL_dimage, float* dL_dgrid,
+                                 void* scratch, size_t scratch_bytes, void* stream);
+size_t msgs_bilagrid_tv_scratch_bytes(int64_t n_elements);
+int msgs_bilagrid_tv_forward(int64_t N, int32_t GX, int32_t GY, int32_t GL, const float* grids, float* tv, void* scratch,
+                             size_t scratch_bytes, void* stream);
+int msgs_bilagrid_tv_backward(int64_t N, int32_t GX, int32_t GY, int32_t GL, const float* grids, const float* upstream,
+                              float* dL_dgrids, void* stream);
+
 /* ---- fused photometric loss ----------------------------------------------------------------
  * loss = (1 - lambda_dssim) * l1_loss(img, gt) + lambda_dssim * (1 - ssim(img, gt))   (/root/reference/train.py:209-211)
  * with l1_loss / ssim of /root/reference/utils/loss_utils.py:17-18,32-63 (window 11, sigma 1.5, zero padding, mean).

@@ -1525,6 +1525,66 @@ int msgs_mcmc_noise(int64_t P, float* xyz, const float* scaling, const float* ro
     return MSGS_OK;
 }
 
+// ---- bilateral-grid colour correction (SPEC M19) ----
+static int bilagrid_shape_ok(int32_t W, int32_t H, int32_t GX, int32_t GY, int32_t GL) {
+    if (GX < 1 || GY < 1 || GL < 1 || GX > MSGS_BILAGRID_MAX_XY || GY > MSGS_BILAGRID_MAX_XY || GL > MSGS_BILAGRID_MAX_L) return 0;
+    if (W < 1 || H < 1 || (int64_t)W * H >= ((int64_t)1 << 29)) return 0;
+    return (H + MSGS_BILAGRID_TILE_H - 1) / MSGS_BILAGRID_TILE_H <= 65535;
+}
+
+static int64_t bilagrid_bank_elements(int64_t N, int32_t GX, int32_t GY, int32_t GL) {
+    if (N < 0 || GX < 1 || GY < 1 || GL < 1 || GX > MSGS_BILAGRID_MAX_XY || GY > MSGS_BILAGRID_MAX_XY || GL > MSGS_BILAGRID_MAX_L)
+        return -1;
+    const int64_t per = (int64_t)12 * GL * GY * GX;
+    if (N > (((int64_t)1 << 38) / per)) return -1;          // the backward's launch: one thread per element
+    return N * per;
+}
+
+size_t msgs_bilagrid_scratch_bytes(int32_t W, int32_t H, int32_t GX, int32_t GY, int32_t GL) {
+    return bilagrid_shape_ok(W, H, GX, GY, GL) ? bilagrid_scratch_bytes(W, H, GX, GY, GL) : 0;
+}
+
+int msgs_bilagrid_slice_forward(int32_t W, int32_t H, int32_t GX, int32_t GY, int32_t GL, const float* image,
+                                const float* grid, float* out, void* stream) {
+    if (!bilagrid_shape_ok(W, H, GX, GY, GL) || !image || !grid || !out) return MSGS_ERR_INVALID_ARG;
+    HIP_TRY(launch_bilagrid_slice_forward(W, H, GX, GY, GL, image, grid, out, (hipStream_t)stream));
+    return MSGS_OK;
+}
+
+int msgs_bilagrid_slice_backward(int32_t W, int32_t H, int32_t GX, int32_t GY, int32_t GL, const float* image,
+                                 const float* grid, const float* dL_dout, int32_t want, float* dL_dimage, float* dL_dgrid,
+                                 void* scratch, size_t scratch_bytes, void* stream) {
+    if (!bilagrid_shape_ok(W, H, GX, GY, GL) || !image || !grid || !dL_dout) return MSGS_ERR_INVALID_ARG;
+    if (want & ~(MSGS_BILAGRID_GRAD_IMAGE | MSGS_BILAGRID_GRAD_GRID)) return MSGS_ERR_INVALID_ARG;
+    const bool wi = want & MSGS_BILAGRID_GRAD_IMAGE, wg = want & MSGS_BILAGRID_GRAD_GRID;
+    if ((wi && !dL_dimage) || (wg && (!dL_dgrid || !scratch || ((uintptr_t)scratch & 15)))) return MSGS_ERR_INVALID_ARG;
+    if (wg && scratch_bytes < bilagrid_scratch_bytes(W, H, GX, GY, GL)) return MSGS_ERR_CAPACITY;
+    if (!wi && !wg) return MSGS_OK;
+    HIP_TRY(launch_bilagrid_slice_backward(W, H, GX, GY, GL, image, grid, dL_dout, wi ? dL_dimage : nullptr,
+                                           wg ? dL_dgrid : nullptr, (char*)scratch, (hipStream_t)stream));
+    return MSGS_OK;
+}
+
+size_t msgs_bilagrid_tv_scratch_bytes(int64_t n_elements) { return bilagrid_tv_scratch_bytes(n_elements < 0 ? 0 : n_elements); }
+
+int msgs_bilagrid_tv_forward(int64_t N, int32_t GX, int32_t GY, int32_t GL, const float* grids, float* tv, void* scratch,
+                             size_t scratch_bytes, void* stream) {
+    const int64_t n = bilagrid_bank_elements(N, GX, GY, GL);
+    if (n < 0 || !tv || !scratch || ((uintptr_t)scratch & 7) || (n > 0 && !grids)) return MSGS_ERR_INVALID_ARG;
+    if (scratch_bytes < bilagrid_tv_scratch_bytes(n)) return MSGS_ERR_CAPACITY;
+    HIP_TRY(launch_bilagrid_tv_forward(N, GX, GY, GL, grids, tv, (char*)scratch, (hipStream_t)stream));
+    return MSGS_OK;
+}
+
+int msgs_bilagrid_tv_backward(int64_t N, int32_t GX, int32_t GY, int32_t GL, const float* grids, const float* upstream,
+                              float* dL_dgrids, void* stream) {
+    const int64_t n = bilagrid_bank_elements(N, GX, GY, GL);
+    if (n < 0 || (n > 0 && (!grids || !dL_dgrids))) return MSGS_ERR_INVALID_ARG;
+    if (n == 0) return MSGS_OK;
+    HIP_TRY(launch_bilagrid_tv_backward(N, GX, GY, GL, grids, upstream, dL_dgrids, (hipStream_t)stream));
+    return MSGS_OK;
+}
+
 static int loss_args_ok(const float* img, const float* gt, int32_t C, int32_t H, int32_t W, float lambda) {
     if (!img || !gt || C < 1 || H < 1 || W < 1 || !(lambda >= 0.f && lambda <= 1.f)) return MSGS_ERR_INVALID_ARG;
     if ((int64_t)C * H * W > (int64_t)1 << 31 || C > 65535) return MSGS_ERR_TOO_MANY;

@@ -817,6 +817,19 @@ int mcmc_relocate(const msgs_mcmc_relocate_t& a, char* scratch, hipStream_t st);
 hipError_t launch_mcmc_noise(int64_t P, float* xyz, const float* scaling, const float* rotation, const float* opacity,
                              const float* draws, float gain, hipStream_t st);
 
+// bilagrid.hip — msgs_bilagrid_* (SPEC M19): the slice of a bilateral grid with both gradients (dL_dimage / dL_dgrid null = that
+// half is skipped; scratch only for the grid half) and the total variation of a bank
+size_t bilagrid_scratch_bytes(int W, int H, int GX, int GY, int GL);
+hipError_t launch_bilagrid_slice_forward(int W, int H, int GX, int GY, int GL, const float* image, const float* grid, float* out,
+                                         hipStream_t st);
+hipError_t launch_bilagrid_slice_backward(int W, int H, int GX, int GY, int GL, const float* image, const float* grid,
+                                          const float* dL_dout, float* dL_dimage, float* dL_dgrid, char* scratch, hipStream_t st);
+size_t bilagrid_tv_scratch_bytes(int64_t n);
+hipError_t launch_bilagrid_tv_forward(int64_t N, int GX, int GY, int GL, const float* grids, float* tv, char* scratch,
+                                      hipStream_t st);
+hipError_t launch_bilagrid_tv_backward(int64_t N, int GX, int GY, int GL, const float* grids, const float* upstream,
+                                       float* dL_dgrids, hipStream_t st);
+
 // loss.hip
 size_t loss_scratch_bytes(int C, int H, int W);
 void ssim_window_host(float w[11]);

@@ -30,7 +30,8 @@ from . import _backend as _C
 __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "rasterize_gaussians_raw",
            "deferred_forward", "GradAccumulator", "set_grad_accumulator", "ContributionScores", "ContributionAccumulator",
            "screen_compensation", "compute_3d_filter", "smoothing_filter", "FILTER3D_CAMERA_CHUNK",
-           "gaussian_normals", "depth_to_normal", "DEPTH_NORMAL_TILE_W", "DEPTH_NORMAL_TILE_H"]
+           "gaussian_normals", "depth_to_normal", "DEPTH_NORMAL_TILE_W", "DEPTH_NORMAL_TILE_H",
+           "bilateral_slice", "total_variation_loss", "BILAGRID_TILE_W", "BILAGRID_TILE_H", "BILAGRID_WINDOW_CELLS"]
 
 
 class GaussianRasterizationSettings(NamedTuple):
@@ -2022,6 +2023,143 @@ def depth_to_normal(depth, raster_settings, world=False):
                          f"{tuple(depth.shape)}")
     return _DepthToNormal.apply(depth, raster_settings.viewmatrix if world else None, W, H, float(raster_settings.tanfovx),
                                 float(raster_settings.tanfovy), bool(world))
+
+
+# Bilateral-grid colour correction (4.20): the per-image correction a trainer places between render() and the
+# photometric loss.  Two functions outside the rasterizer; host/bilagrid.py holds the module that owns a bank of grids.
+BILAGRID_TILE_W, BILAGRID_TILE_H, BILAGRID_WINDOW_CELLS = _C.BILAGRID_TILE_W, _C.BILAGRID_TILE_H, _C.BILAGRID_WINDOW_CELLS
+_bilagrid_probe = None             # tests: a callable (name) run in front of every msgs_bilagrid_* call
+
+
+def _bilagrid_sizes(grid, where):
+    """(GX, GY, GL) of a grid [12,GL,GY,GX]; the sizes the kernels take, anything else is refused"""
+    if grid.dim() != 4 or grid.shape[0] != 12:
+        raise ValueError(f"{where}: grid must be [12,GL,GY,GX], got {tuple(grid.shape)}")
+    GL, GY, GX = (int(v) for v in grid.shape[1:])
+    if not (1 <= GX <= _C.BILAGRID_MAX_XY and 1 <= GY <= _C.BILAGRID_MAX_XY and 1 <= GL <= _C.BILAGRID_MAX_L):
+        raise ValueError(f"{where}: grid sizes must satisfy 1 <= GX, GY <= {_C.BILAGRID_MAX_XY} and 1 <= GL <= "
+                         f"{_C.BILAGRID_MAX_L}, got GX={GX} GY={GY} GL={GL}")
+    return GX, GY, GL
+
+
+class _BilateralSlice(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, image, grid):
+        dev = image.device
+        if dev.type != "cuda" or grid.device != dev:
+            raise RuntimeError(_HIP_ONLY)
+        H, W = int(image.shape[1]), int(image.shape[2])
+        GX, GY, GL = _bilagrid_sizes(grid, "bilateral_slice")
+        ctx.dev, ctx.geometry, ctx.shapes = dev, (W, H, GX, GY, GL), (image.shape, grid.shape)
+        out = torch.empty(3, H, W, dtype=torch.float32, device=dev)
+        if W * H == 0:
+            return out
+        im, gr = _f32c(image.detach()), _f32c(grid.detach())
+        if _bilagrid_probe is not None:
+            _bilagrid_probe("msgs_bilagrid_slice_forward")
+        with _on_device(dev):
+            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            _C.check(_C.lib.msgs_bilagrid_slice_forward(W, H, GX, GY, GL, _ptr(im), _ptr(gr), _ptr(out), stream),
+                     "msgs_bilagrid_slice_forward")
+        ctx.save_for_backward(im, gr)
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        dev = ctx.dev
+        W, H, GX, GY, GL = ctx.geometry
+        want_image, want_grid = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if W * H == 0 or g_out is None:
+            return (torch.zeros(ctx.shapes[0], dtype=torch.float32, device=dev) if want_image else None,
+                    torch.zeros(ctx.shapes[1], dtype=torch.float32, device=dev) if want_grid else None)
+        im, gr = ctx.saved_tensors
+        g = _f32c(g_out)
+        g_image = torch.empty(3, H, W, dtype=torch.float32, device=dev) if want_image else None
+        g_grid = torch.empty(12, GL, GY, GX, dtype=torch.float32, device=dev) if want_grid else None
+        scratch, nbytes = None, 0
+        if want_grid:
+            nbytes = int(_C.lib.msgs_bilagrid_scratch_bytes(W, H, GX, GY, GL))
+            scratch = _bytes(nbytes, dev)
+        want = (_C.BILAGRID_GRAD_IMAGE if want_image else 0) | (_C.BILAGRID_GRAD_GRID if want_grid else 0)
+        if _bilagrid_probe is not None:
+            _bilagrid_probe("msgs_bilagrid_slice_backward")
+        with _on_device(dev):
+            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            _C.check(_C.lib.msgs_bilagrid_slice_backward(W, H, GX, GY, GL, _ptr(im), _ptr(gr), _ptr(g), want, _ptr(g_image),
+                                                         _ptr(g_grid), _ptr(scratch), nbytes, stream),
+                     "msgs_bilagrid_slice_backward")
+        return (g_image.view(ctx.shapes[0]) if want_image else None), (g_grid if want_grid else None)
+
+
+def bilateral_slice(image, grid):
+    """out [3,H,W] float32: `image` [3,H,W] (the layout of render()["render"]) corrected by ONE image's bilateral grid
+    `grid` [12,GL,GY,GX] — channel 4 c + j is entry (c, j) of a 3x4 affine colour transform, stored over (x, y, luminance):
+        fx = (x + 0.5) / W (GX - 1),  fy = (y + 0.5) / H (GY - 1),  z = 0.299 r + 0.587 g + 0.114 b,  fz = clamp(z, 0, 1) (GL - 1)
+        A = trilinear interpolation of the grid at (fx, fy, fz),   out_c = A[c,0] r + A[c,1] g + A[c,2] b + A[c,3]
+    which is F.grid_sample(bilinear, border, align_corners=True) followed by the affine product (gsplat's use_bilateral_grid,
+    "Bilateral Guided Radiance Field Processing").  The identity grid (eye(4)[:3].flatten() in every cell) returns the image
+    bit for bit; a 1x1x1 grid is upstream 3DGS's 3x4 exposure matrix.  Differentiable in both arguments; the guide is computed
+    from the image being corrected and its gradient flows (where 0 < z < 1, open at both ends — grid_sample's convention, so a
+    black pixel gets the direct term only).  A frozen grid or a detached image skips its half of the backward.  grid.grad is
+    summed in one fixed order without float atomics: the same bits on every run.  1 <= GX, GY <= 256 and 1 <= GL <= 32, anything
+    else raises ValueError.  A NaN or Inf pixel stays inside the grid; only its own output, its own gradient and the grid nodes
+    it touches can carry its NaN.  float64 and strided inputs are converted.  HIP kernels only."""
+    if image.dim() != 3 or image.shape[0] != 3:
+        raise ValueError(f"bilateral_slice: image must be [3,H,W], got {tuple(image.shape)}")
+    _bilagrid_sizes(grid, "bilateral_slice")
+    return _BilateralSlice.apply(image, grid)
+
+
+class _TotalVariation(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, grids):
+        dev = grids.device
+        if dev.type != "cuda":
+            raise RuntimeError(_HIP_ONLY)
+        N, _, GL, GY, GX = (int(v) for v in grids.shape)
+        ctx.dev, ctx.sizes, ctx.shape = dev, (N, GX, GY, GL), grids.shape
+        tv = torch.zeros(1, dtype=torch.float32, device=dev)
+        if N == 0:
+            return tv[0]
+        gr = _f32c(grids.detach())
+        nbytes = int(_C.lib.msgs_bilagrid_tv_scratch_bytes(gr.numel()))
+        scratch = _bytes(nbytes, dev)
+        if _bilagrid_probe is not None:
+            _bilagrid_probe("msgs_bilagrid_tv_forward")
+        with _on_device(dev):
+            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            _C.check(_C.lib.msgs_bilagrid_tv_forward(N, GX, GY, GL, _ptr(gr), _ptr(tv), _ptr(scratch), nbytes, stream),
+                     "msgs_bilagrid_tv_forward")
+        ctx.save_for_backward(gr)
+        return tv[0]
+
+    @staticmethod
+    def backward(ctx, g_tv):
+        dev = ctx.dev
+        N, GX, GY, GL = ctx.sizes
+        g_grids = torch.zeros(ctx.shape, dtype=torch.float32, device=dev)
+        if N == 0 or g_tv is None:
+            return g_grids
+        (gr,) = ctx.saved_tensors
+        up = _f32c(g_tv.detach().to(dev)).reshape(1)
+        if _bilagrid_probe is not None:
+            _bilagrid_probe("msgs_bilagrid_tv_backward")
+        with _on_device(dev):
+            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            _C.check(_C.lib.msgs_bilagrid_tv_backward(N, GX, GY, GL, _ptr(gr), _ptr(up), _ptr(g_grids), stream),
+                     "msgs_bilagrid_tv_backward")
+        return g_grids
+
+
+def total_variation_loss(grids):
+    """scalar: the total variation of a bank of bilateral grids `grids` [N,12,GL,GY,GX] — the sum over the three spatial axes of
+    the mean, over every (n, channel, position), of the squared forward difference along that axis; an axis of size 1 adds 0
+    (gsplat's total_variation_loss).  Summed in double in a fixed order (the same bits on every run); differentiable, the
+    backward is a gather scaled by the upstream scalar, which is read on the device.  Two HIP kernels forward, one backward."""
+    if grids.dim() != 5 or grids.shape[1] != 12:
+        raise ValueError(f"total_variation_loss: grids must be [N,12,GL,GY,GX], got {tuple(grids.shape)}")
+    _bilagrid_sizes(grids[0] if grids.shape[0] else grids.new_zeros((12,) + tuple(grids.shape[2:])), "total_variation_loss")
+    return _TotalVariation.apply(grids)
 
 
 # Contribution scores (DESIGN.md 2, M11; 4.11): what every Gaussian did to the images of one or many views, the criterion of

@@ -86,6 +86,11 @@ FILTER3D_CAMERA_FLOATS, FILTER3D_CAMERA_CHUNK = 20, 64
 FILTER3D_RULES = {"per_camera": 0, "mip_splatting": 1}
 # msgs_depth_normal_* (include/msgs.h): the tile of the depth-to-normal kernels
 DEPTH_NORMAL_TILE_W, DEPTH_NORMAL_TILE_H = 64, 8
+# msgs_bilagrid_* (include/msgs.h): the pixel tile of the slice kernels, the xy nodes a tile's LDS window holds, the size limits
+# and the bits of `want`
+BILAGRID_TILE_W, BILAGRID_TILE_H, BILAGRID_WINDOW_CELLS = 64, 16, 16
+BILAGRID_MAX_XY, BILAGRID_MAX_L = 256, 32
+BILAGRID_GRAD_IMAGE, BILAGRID_GRAD_GRID = 1, 2
 
 DENSIFY_PRUNE, DENSIFY_GROW, DENSIFY_PRUNE_MASK, DENSIFY_APPEND = 0, 1, 2, 3
 (DR_COPY, DR_ZERO, DR_COPY_CLEAR_COL, DR_SPLIT_XYZ, DR_SPLIT_SCALE, DR_SPLIT_DIV, DR_GROW_OPACITY, DR_GROW_SCALE, DR_GROW_MUL,
@@ -266,6 +271,18 @@ def _load():
     lib.msgs_depth_normal_forward.argtypes = [C.c_int32, C.c_int32, C.c_float, C.c_float, vp, vp, C.c_int32, vp, vp]
     lib.msgs_depth_normal_backward.restype = C.c_int
     lib.msgs_depth_normal_backward.argtypes = [C.c_int32, C.c_int32, C.c_float, C.c_float, vp, vp, C.c_int32, vp, vp, vp]
+    lib.msgs_bilagrid_scratch_bytes.restype = sz
+    lib.msgs_bilagrid_scratch_bytes.argtypes = [C.c_int32] * 5
+    lib.msgs_bilagrid_slice_forward.restype = C.c_int
+    lib.msgs_bilagrid_slice_forward.argtypes = [C.c_int32] * 5 + [vp, vp, vp, vp]
+    lib.msgs_bilagrid_slice_backward.restype = C.c_int
+    lib.msgs_bilagrid_slice_backward.argtypes = [C.c_int32] * 5 + [vp, vp, vp, C.c_int32, vp, vp, vp, sz, vp]
+    lib.msgs_bilagrid_tv_scratch_bytes.restype = sz
+    lib.msgs_bilagrid_tv_scratch_bytes.argtypes = [C.c_int64]
+    lib.msgs_bilagrid_tv_forward.restype = C.c_int
+    lib.msgs_bilagrid_tv_forward.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, sz, vp]
+    lib.msgs_bilagrid_tv_backward.restype = C.c_int
+    lib.msgs_bilagrid_tv_backward.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp]
     lib.msgs_backward_per_gaussian.restype = C.c_int
     lib.msgs_backward_per_gaussian.argtypes = [C.POINTER(View), C.POINTER(Gaussians), vp, vp, sz, vp, C.POINTER(Grads), vp]
     lib.msgs_sh_grad_from_views.restype = C.c_int
@@ -358,6 +375,8 @@ EXPORTS = ("msgs_abi_version", "msgs_error_string", "msgs_geom_bytes", "msgs_sta
            "msgs_smoothing_filter_backward",
            "msgs_gaussian_normals_forward", "msgs_gaussian_normals_backward", "msgs_depth_normal_forward",
            "msgs_depth_normal_backward",
+           "msgs_bilagrid_scratch_bytes", "msgs_bilagrid_slice_forward", "msgs_bilagrid_slice_backward",
+           "msgs_bilagrid_tv_scratch_bytes", "msgs_bilagrid_tv_forward", "msgs_bilagrid_tv_backward",
            "msgs_mcmc_scratch_bytes", "msgs_mcmc_prepare", "msgs_mcmc_sample", "msgs_mcmc_relocate", "msgs_mcmc_noise",
            "msgs_set_depth_sort", "msgs_depth_sort_stats")
 
