@@ -741,6 +741,28 @@ int backward_camera_alpha(const msgs_view_t* view, const msgs_gaussians_t* g, co
     return backward_impl(view, g, radii, geom_v, geom_bytes, D, binning_v, binning_bytes, image_v, image_bytes, dL_dcolor,
                          dL_ddepth, dL_dalpha, scratch_v, scratch_bytes, grads, &cam, timing, stream);
 }
+
+// The forward state an opt-in replay reads (geometry, binning and image buffers of a P-Gaussian, D-instance forward of `view`) as
+// the pointers its launcher takes.  MSGS_ERR_INVALID_ARG for a missing buffer, then MSGS_ERR_CAPACITY for one too small for
+// msgs_geom_bytes / msgs_binning_bytes / msgs_image_bytes.  The caller has checked view, P, D and the image size.
+int replay_inputs(const msgs_view_t* view, int32_t P, const void* geom, size_t geom_bytes, int64_t D, const void* binning_v,
+                  size_t binning_bytes, const void* image_v, size_t image_bytes, ReplayInputs* in) {
+    if (!geom || !binning_v || !image_v) return MSGS_ERR_INVALID_ARG;
+    const int W = view->image_width, H = view->image_height;
+    if (geom_bytes < msgs_geom_bytes(P) || binning_bytes < msgs_binning_bytes(D, W, H) || image_bytes < msgs_image_bytes(W, H))
+        return MSGS_ERR_CAPACITY;
+    in->vp = make_view_params(view);
+    const BinningLayout BL(D, in->vp.gx * in->vp.gy);
+    const ImageLayout IL(W, H);
+    const char* binning = (const char*)binning_v;
+    const char* image = (const char*)image_v;
+    in->rec = (const GaussRec*)geom;                                         // GeomLayout::rec == 0
+    in->ids = (const uint32_t*)(binning + BL.ids);
+    in->ranges = (const uint2*)(binning + BL.ranges);
+    in->final_T = (const float*)(image + IL.final_T);
+    in->n_contrib = (const uint32_t*)(image + IL.n_contrib);
+    return MSGS_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -823,21 +845,14 @@ int msgs_absgrad(const msgs_view_t* view, int32_t P, const void* geom_v, size_t 
                  const float* dL_dalpha, void* scratch, size_t scratch_bytes, float* out_absgrad, void* stream) {
     if (!view || P < 0 || D < 0 || view->image_width < 1 || view->image_height < 1) return MSGS_ERR_INVALID_ARG;
     if (P == 0) return MSGS_OK;                                              // nothing to zero: out is [0, 3]
-    if (!out_absgrad || !dL_dcolor || !geom_v || !binning_v || !image_v || !scratch || !view->bg) return MSGS_ERR_INVALID_ARG;
+    if (!out_absgrad || !dL_dcolor || !scratch || !view->bg) return MSGS_ERR_INVALID_ARG;
     if ((uintptr_t)scratch & 7) return MSGS_ERR_INVALID_ARG;                 // rows of doubles
-    const int W = view->image_width, H = view->image_height;
-    if (geom_bytes < msgs_geom_bytes(P) || binning_bytes < msgs_binning_bytes(D, W, H) || image_bytes < msgs_image_bytes(W, H) ||
-        scratch_bytes < msgs_absgrad_scratch_bytes(P))
-        return MSGS_ERR_CAPACITY;
+    ReplayInputs in;
+    const int st = replay_inputs(view, P, geom_v, geom_bytes, D, binning_v, binning_bytes, image_v, image_bytes, &in);
+    if (st != MSGS_OK) return st;
+    if (scratch_bytes < msgs_absgrad_scratch_bytes(P)) return MSGS_ERR_CAPACITY;
     hipStream_t s = (hipStream_t)stream;
-    const ViewParams vp = make_view_params(view);
-    const BinningLayout BL(D, vp.gx * vp.gy);
-    const ImageLayout IL(W, H);
-    const char* binning = (const char*)binning_v;
-    const char* image = (const char*)image_v;
-    HIP_TRY(launch_blend_absgrad(vp, P, (const char*)geom_v, (const uint32_t*)(binning + BL.ids), (const uint2*)(binning + BL.ranges),
-                                 (const float*)(image + IL.final_T), (const uint32_t*)(image + IL.n_contrib), dL_dcolor, dL_ddepth,
-                                 dL_dalpha, (double*)scratch, out_absgrad, s));
+    HIP_TRY(launch_blend_absgrad(in, P, dL_dcolor, dL_ddepth, dL_dalpha, (double*)scratch, out_absgrad, s));
     return debug_sync(view, s);
 }
 
@@ -850,22 +865,15 @@ int msgs_contrib_accumulate(const msgs_view_t* view, int32_t P, const void* geom
     if ((uintptr_t)acc & 7) return MSGS_ERR_INVALID_ARG;                     // rows of {double, uint64, uint32}
     if (acc_bytes < msgs_contrib_scratch_bytes(P)) return MSGS_ERR_CAPACITY;
     const bool replay = P > 0 && D > 0;                                      // no instance: no pair, nothing to add
-    const int W = view->image_width, H = view->image_height;
+    ReplayInputs in;
     if (replay) {
-        if (!geom_v || !binning_v || !image_v) return MSGS_ERR_INVALID_ARG;
-        if (geom_bytes < msgs_geom_bytes(P) || binning_bytes < msgs_binning_bytes(D, W, H) || image_bytes < msgs_image_bytes(W, H))
-            return MSGS_ERR_CAPACITY;
+        const int st = replay_inputs(view, P, geom_v, geom_bytes, D, binning_v, binning_bytes, image_v, image_bytes, &in);
+        if (st != MSGS_OK) return st;
     }
     hipStream_t s = (hipStream_t)stream;
     if (clear_first && P > 0) HIP_TRY(launch_zero(acc, CONTRIB_ACC_BYTES * (size_t)P, s));
     if (!replay) return debug_sync(view, s);
-    const ViewParams vp = make_view_params(view);
-    const BinningLayout BL(D, vp.gx * vp.gy);
-    const ImageLayout IL(W, H);
-    const char* binning = (const char*)binning_v;
-    const char* image = (const char*)image_v;
-    HIP_TRY(launch_blend_contrib(vp, (const char*)geom_v, (const uint32_t*)(binning + BL.ids), (const uint2*)(binning + BL.ranges),
-                                 (const float*)(image + IL.final_T), (const uint32_t*)(image + IL.n_contrib), pixel_weights, acc, s));
+    HIP_TRY(launch_blend_contrib(in, pixel_weights, acc, s));
     return debug_sync(view, s);
 }
 
@@ -892,17 +900,11 @@ int msgs_features_forward(const msgs_view_t* view, int32_t P, const void* geom_v
         HIP_TRY(launch_zero(out, sizeof(float) * (size_t)C * W * H, s));
         return debug_sync(view, s);
     }
-    if (!geom_v || !binning_v || !image_v || !features || ((uintptr_t)features & 3)) return MSGS_ERR_INVALID_ARG;
-    if (geom_bytes < msgs_geom_bytes(P) || binning_bytes < msgs_binning_bytes(D, W, H) || image_bytes < msgs_image_bytes(W, H))
-        return MSGS_ERR_CAPACITY;
-    const ViewParams vp = make_view_params(view);
-    const BinningLayout BL(D, vp.gx * vp.gy);
-    const ImageLayout IL(W, H);
-    const char* binning = (const char*)binning_v;
-    const char* image = (const char*)image_v;
-    HIP_TRY(launch_blend_features_forward(vp, (const char*)geom_v, (const uint32_t*)(binning + BL.ids),
-                                          (const uint2*)(binning + BL.ranges), (const float*)(image + IL.final_T),
-                                          (const uint32_t*)(image + IL.n_contrib), features, C, out, s));
+    if (!features || ((uintptr_t)features & 3)) return MSGS_ERR_INVALID_ARG;
+    ReplayInputs in;
+    const int st = replay_inputs(view, P, geom_v, geom_bytes, D, binning_v, binning_bytes, image_v, image_bytes, &in);
+    if (st != MSGS_OK) return st;
+    HIP_TRY(launch_blend_features_forward(in, features, C, out, s));
     return debug_sync(view, s);
 }
 
@@ -919,21 +921,15 @@ int msgs_features_backward(const msgs_view_t* view, int32_t P, const void* geom_
         HIP_TRY(launch_zero(dL_dfeatures, sizeof(float) * (size_t)P * C, s));
         return debug_sync(view, s);
     }
-    if (!geom_v || !binning_v || !image_v || !features || !dL_dfeature_map || !scratch) return MSGS_ERR_INVALID_ARG;
+    if (!features || !dL_dfeature_map || !scratch) return MSGS_ERR_INVALID_ARG;
     if (((uintptr_t)features & 3) || ((uintptr_t)scratch & 7) || ((uintptr_t)grad_records & 7)) return MSGS_ERR_INVALID_ARG;
-    const int W = view->image_width, H = view->image_height;
-    if (geom_bytes < msgs_geom_bytes(P) || binning_bytes < msgs_binning_bytes(D, W, H) || image_bytes < msgs_image_bytes(W, H) ||
-        scratch_bytes < features_scratch_bytes(P) || (grad_records && grad_records_bytes < msgs_backward_scratch_bytes(P)))
+    ReplayInputs in;
+    const int st = replay_inputs(view, P, geom_v, geom_bytes, D, binning_v, binning_bytes, image_v, image_bytes, &in);
+    if (st != MSGS_OK) return st;
+    if (scratch_bytes < features_scratch_bytes(P) || (grad_records && grad_records_bytes < msgs_backward_scratch_bytes(P)))
         return MSGS_ERR_CAPACITY;
-    const ViewParams vp = make_view_params(view);
-    const BinningLayout BL(D, vp.gx * vp.gy);
-    const ImageLayout IL(W, H);
-    const char* binning = (const char*)binning_v;
-    const char* image = (const char*)image_v;
-    HIP_TRY(launch_blend_features_backward(vp, P, (const char*)geom_v, (const uint32_t*)(binning + BL.ids),
-                                           (const uint2*)(binning + BL.ranges), (const float*)(image + IL.final_T),
-                                           (const uint32_t*)(image + IL.n_contrib), features, C, dL_dfeature_map,
-                                           (grad_acc_t*)grad_records, (double*)scratch, dL_dfeatures, s));
+    HIP_TRY(launch_blend_features_backward(in, P, features, C, dL_dfeature_map, (grad_acc_t*)grad_records, (double*)scratch,
+                                           dL_dfeatures, s));
     return debug_sync(view, s);
 }
 
@@ -950,17 +946,10 @@ int msgs_distortion_forward(const msgs_view_t* view, int32_t P, const void* geom
         HIP_TRY(launch_zero(out_moment, sizeof(float) * (size_t)W * H, s));
         return debug_sync(view, s);
     }
-    if (!geom_v || !binning_v || !image_v) return MSGS_ERR_INVALID_ARG;
-    if (geom_bytes < msgs_geom_bytes(P) || binning_bytes < msgs_binning_bytes(D, W, H) || image_bytes < msgs_image_bytes(W, H))
-        return MSGS_ERR_CAPACITY;
-    const ViewParams vp = make_view_params(view);
-    const BinningLayout BL(D, vp.gx * vp.gy);
-    const ImageLayout IL(W, H);
-    const char* binning = (const char*)binning_v;
-    const char* image = (const char*)image_v;
-    HIP_TRY(launch_blend_distortion_forward(vp, (const char*)geom_v, (const uint32_t*)(binning + BL.ids),
-                                            (const uint2*)(binning + BL.ranges), (const float*)(image + IL.final_T),
-                                            (const uint32_t*)(image + IL.n_contrib), out_distortion, out_moment, s));
+    ReplayInputs in;
+    const int st = replay_inputs(view, P, geom_v, geom_bytes, D, binning_v, binning_bytes, image_v, image_bytes, &in);
+    if (st != MSGS_OK) return st;
+    HIP_TRY(launch_blend_distortion_forward(in, out_distortion, out_moment, s));
     return debug_sync(view, s);
 }
 
@@ -971,22 +960,13 @@ int msgs_distortion_backward(const msgs_view_t* view, int32_t P, const void* geo
     if (!view || P < 0 || D < 0 || view->image_width < 1 || view->image_height < 1) return MSGS_ERR_INVALID_ARG;
     if (g_deterministic.load() != 0) return MSGS_ERR_INVALID_ARG;            // its scratch holds another layout
     if (P == 0 || D == 0) return MSGS_OK;                                    // no pair: nothing for the records
-    if (!geom_v || !binning_v || !image_v || !moment || !dL_ddistortion || !grad_records || ((uintptr_t)grad_records & 7))
-        return MSGS_ERR_INVALID_ARG;
-    const int W = view->image_width, H = view->image_height;
-    if (geom_bytes < msgs_geom_bytes(P) || binning_bytes < msgs_binning_bytes(D, W, H) || image_bytes < msgs_image_bytes(W, H) ||
-        grad_records_bytes < msgs_backward_scratch_bytes(P))
-        return MSGS_ERR_CAPACITY;
+    if (!moment || !dL_ddistortion || !grad_records || ((uintptr_t)grad_records & 7)) return MSGS_ERR_INVALID_ARG;
+    ReplayInputs in;
+    const int st = replay_inputs(view, P, geom_v, geom_bytes, D, binning_v, binning_bytes, image_v, image_bytes, &in);
+    if (st != MSGS_OK) return st;
+    if (grad_records_bytes < msgs_backward_scratch_bytes(P)) return MSGS_ERR_CAPACITY;
     hipStream_t s = (hipStream_t)stream;
-    const ViewParams vp = make_view_params(view);
-    const BinningLayout BL(D, vp.gx * vp.gy);
-    const ImageLayout IL(W, H);
-    const char* binning = (const char*)binning_v;
-    const char* image = (const char*)image_v;
-    HIP_TRY(launch_blend_distortion_backward(vp, (const char*)geom_v, (const uint32_t*)(binning + BL.ids),
-                                             (const uint2*)(binning + BL.ranges), (const float*)(image + IL.final_T),
-                                             (const uint32_t*)(image + IL.n_contrib), moment, dL_ddistortion,
-                                             (grad_acc_t*)grad_records, s));
+    HIP_TRY(launch_blend_distortion_backward(in, moment, dL_ddistortion, (grad_acc_t*)grad_records, s));
     return debug_sync(view, s);
 }
 
@@ -1003,17 +983,10 @@ int msgs_median_depth_forward(const msgs_view_t* view, int32_t P, const void* ge
         HIP_TRY(hipMemsetAsync(out_median_id, 0xFF, sizeof(int32_t) * (size_t)W * H, s));      // every id -1
         return debug_sync(view, s);
     }
-    if (!geom_v || !binning_v || !image_v) return MSGS_ERR_INVALID_ARG;
-    if (geom_bytes < msgs_geom_bytes(P) || binning_bytes < msgs_binning_bytes(D, W, H) || image_bytes < msgs_image_bytes(W, H))
-        return MSGS_ERR_CAPACITY;
-    const ViewParams vp = make_view_params(view);
-    const BinningLayout BL(D, vp.gx * vp.gy);
-    const ImageLayout IL(W, H);
-    const char* binning = (const char*)binning_v;
-    const char* image = (const char*)image_v;
-    HIP_TRY(launch_blend_median_depth_forward(vp, (const char*)geom_v, (const uint32_t*)(binning + BL.ids),
-                                              (const uint2*)(binning + BL.ranges), (const uint32_t*)(image + IL.n_contrib),
-                                              out_median_depth, out_median_id, s));
+    ReplayInputs in;
+    const int st = replay_inputs(view, P, geom_v, geom_bytes, D, binning_v, binning_bytes, image_v, image_bytes, &in);
+    if (st != MSGS_OK) return st;
+    HIP_TRY(launch_blend_median_depth_forward(in, out_median_depth, out_median_id, s));
     return debug_sync(view, s);
 }
 

@@ -1052,10 +1052,124 @@ __global__ __launch_bounds__(64) void blend_backward_tile_kernel(ViewParams vp, 
 }
 
 // ---------------------------------------------------------------------------------------------
+// The skeleton of the opt-in tile-list replays below.  All of them run in the four-waves-per-tile shape of blend_backward_kernel
+// (one 256-thread workgroup per tile, one 8x8 quadrant per wave, whatever the tile count) and share its pixel mapping, its
+// per-batch staging of the tile's records into LDS and its per-wave compacted list of the staged entries that touch the wave's
+// quadrant.  A replay adds its per-pixel state, one more store per staged entry, and the walk over the compacted list.
+// (blend_backward_kernel itself spells the same steps out: folded onto these helpers its registers come out in another order.)
+// ---------------------------------------------------------------------------------------------
+// The pixel of a lane: wave w owns quadrant (w & 1, w >> 1) of the (XCD-swizzled) tile, lane l its pixel (l & 7, l >> 3).
+struct ReplayPixel {
+    int tile, tx, ty, tid, w, lane, px, py;
+    bool inside;
+    size_t pix;                                              // py * W + px (an index only where inside)
+};
+__device__ __forceinline__ ReplayPixel replay_pixel(const ViewParams& vp) {
+    ReplayPixel p;
+    const int num_tiles = vp.gx * vp.gy;
+    p.tile = swizzled_tile(blockIdx.x, num_tiles);
+    p.tx = p.tile % vp.gx; p.ty = p.tile / vp.gx;
+    p.tid = threadIdx.x; p.w = p.tid >> 6; p.lane = p.tid & 63;
+    p.px = p.tx * TILE + (p.w & 1) * 8 + (p.lane & 7);
+    p.py = p.ty * TILE + (p.w >> 1) * 8 + (p.lane >> 3);
+    p.inside = p.px < vp.W && p.py < vp.H;
+    p.pix = (size_t)p.py * vp.W + p.px;
+    return p;
+}
+// ... and what the staging and the walks take beside it.  (Inlined, the members are plain values of the kernel: one that is not
+// read behind the prologue holds no register during the walk.  A kernel that fills a BwdPix reads `inside` and `pix` once, into
+// locals: its loads of final_T and n_contrib then stay under ONE branch on `inside`; read through the struct between the stores
+// to the BwdPix, each load gets a branch and a kernel-argument fetch of its own.)
+struct ReplayTile : ReplayPixel {
+    float pxf, pyf, tx0, ty0;                                // the pixel and the tile's corner, as the pair arithmetic takes them
+    uint2 range;                                             // the tile's entries in `ids`
+    uint64_t lt_mask;                                        // the lanes below this one
+    size_t N;                                                // W * H: the plane stride of a [C,H,W] map
+};
+__device__ __forceinline__ ReplayTile replay_tile(const ViewParams& vp, const uint2* __restrict__ ranges) {
+    ReplayTile t;
+    static_cast<ReplayPixel&>(t) = replay_pixel(vp);
+    t.pxf = (float)t.px; t.pyf = (float)t.py;
+    t.tx0 = (float)(t.tx * TILE); t.ty0 = (float)(t.ty * TILE);
+    t.range = ranges[t.tile];
+    t.lt_mask = (1ull << t.lane) - 1ull;
+    t.N = (size_t)vp.W * vp.H;
+    return t;
+}
+// How far the tile's list is replayed, from `last` = the position behind the last entry the lane's pixel blended: a wave lists
+// entries below wave_last, the workgroup stages entries below tile_last.  Contains a barrier.
+struct ReplayEnds { uint32_t wave_last, tile_last; };
+__device__ __forceinline__ ReplayEnds replay_ends(uint32_t last, uint32_t (&s_wmax)[4], int w, int lane) {
+    ReplayEnds e;
+    e.wave_last = wave_max_u32(last);
+    if (lane == 0) s_wmax[w] = e.wave_last;
+    __syncthreads();
+    e.tile_last = max(max(s_wmax[0], s_wmax[1]), max(s_wmax[2], s_wmax[3]));
+    return e;
+}
+// This wave's list of the n staged entries (positions base .. base + n - 1 of the tile's list): the LDS slots, ascending, of those
+// below wave_last whose quadrant mask — mask_of(slot) — has the wave's bit.  Compacted by ballot; returns their number.
+template <class MaskOf>
+__device__ __forceinline__ int compact_quadrant_list(const ReplayTile& t, int base, int n, uint32_t wave_last, uint16_t* s_listw,
+                                                     MaskOf mask_of) {
+    int cnt = 0;
+#pragma unroll
+    for (int c = 0; c < BATCH / 64; ++c) {
+        const int e = c * 64 + t.lane;
+        const bool hit = e < n && (uint32_t)(base + e) < wave_last && ((mask_of(e) >> t.w) & 1u);
+        const uint64_t bal = __ballot(hit);
+        if (hit) s_listw[cnt + __popcll(bal & t.lt_mask)] = (uint16_t)e;
+        cnt += __popcll(bal);
+    }
+    return cnt;
+}
+// One batch of a replay, called behind the barrier that ends the previous batch: thread k stages entry base + k of the tile's
+// list into slot k (BATCH entries, fewer in the batch that reaches tile_last), a barrier, then every wave compacts its list into
+// s_listw; returns the list's length.  extra(k, id, r0, r1, r2) stores what else the kernel's walk reads of the entry, from its
+// id and its record as loaded.  Two LDS layouts:
+// colour — s_r0 = r0 with the doubled cross term, s_r1 = r1 whole (red and green in z, w), the quadrant masks in s_mask;
+template <class Extra>
+__device__ __forceinline__ int stage_and_list_colour(const ReplayTile& t, const GaussRec* rec, const uint32_t* ids, int base,
+                                                     const ReplayEnds& ends, float4* s_r0, float4* s_r1, uint32_t* s_mask,
+                                                     uint16_t* s_listw, Extra extra) {
+    const int n = min(BATCH, (int)ends.tile_last - base);
+    if (t.tid < n) {
+        const uint32_t id = ids[t.range.x + base + t.tid];
+        const float4 r0 = rec[id].r0, r1 = rec[id].r1;
+        const float4 r2 = rec[id].r2;
+        s_r0[t.tid] = doubled_w(r0); s_r1[t.tid] = r1;
+        extra(t.tid, id, r0, r1, r2);
+        s_mask[t.tid] = quadrant_mask(r0, r1.x, r2.w, t.tx0, t.ty0);
+    }
+    __syncthreads();
+    return compact_quadrant_list(t, base, n, ends.wave_last, s_listw, [=](int e) { return s_mask[e]; });
+}
+// packed, for the walks that read no colour — s_r1 = {C', p0', sign_test_bound, quadrant mask bits}: the bound and the mask ride
+// in the two colour slots instead of arrays of their own (2 KB of LDS less).  (extra goes first: the id is stored and dead
+// before the quadrant mask is worked out.)
+template <class Extra>
+__device__ __forceinline__ int stage_and_list_packed(const ReplayTile& t, const GaussRec* rec, const uint32_t* ids, int base,
+                                                     const ReplayEnds& ends, float4* s_r0, float4* s_r1, uint16_t* s_listw,
+                                                     Extra extra) {
+    const int n = min(BATCH, (int)ends.tile_last - base);
+    if (t.tid < n) {
+        const uint32_t id = ids[t.range.x + base + t.tid];
+        const float4 r0 = rec[id].r0, r1 = rec[id].r1;
+        const float4 r2 = rec[id].r2;
+        s_r0[t.tid] = doubled_w(r0);
+        extra(t.tid, id, r0, r1, r2);
+        s_r1[t.tid] = make_float4(r1.x, r1.y, sign_test_bound(r1.y), __uint_as_float(quadrant_mask(r0, r1.x, r2.w, t.tx0, t.ty0)));
+    }
+    __syncthreads();
+    return compact_quadrant_list(t, base, n, ends.wave_last, s_listw, [=](int e) { return __float_as_uint(s_r1[e].w); });
+}
+
+// ---------------------------------------------------------------------------------------------
 // Absgrad (DESIGN.md SPEC M10, 4.10; msgs_absgrad): sum_p |dL/dmean2D contribution of pixel p| per Gaussian, the densification
 // statistic of AbsGS.  The per-pixel terms exist only here, in front of the cross-pixel reduction, so this is ONE more replay of
-// the back-to-front walk of blend_backward_kernel (same staging, same quadrant lists, same pair_alpha / pair_valid / pair_grad,
-// hence the same pairs and the same q as the gradient itself) with a two-sum tail in the place of the nine-sum scatter:
+// the back-to-front walk of blend_backward_kernel (stage_and_list_colour with its extras: the same staging and quadrant lists;
+// the same pair_alpha / pair_valid / pair_grad, hence the same pairs and the same q as the gradient itself) with a two-sum tail
+// in the place of the nine-sum scatter:
 //     u = A' dx + Bh' dy,  w = C' dy + Bh' dx   (the log2-scaled conic of the staged record; r0.w holds 2 Bh')
 //     acc[id] += { sum_lanes |q u|, sum_lanes |q w| }
 // The factors ln2 W and ln2 H of dL/dmean2D (preprocess_backward_kernel) are applied once per Gaussian by absgrad_finish_kernel.
@@ -1096,7 +1210,7 @@ __device__ __forceinline__ void absgrad_walk(const uint16_t* lp, int cnt, int ba
     }
 }
 
-// One 256-thread workgroup per tile, one 8x8 quadrant per wave, as blend_backward_kernel (one shape for every tile count).
+// The replay skeleton (replay_tile, replay_ends, stage_and_list_colour) around BwdPix and absgrad_walk.
 template <bool DEPTH, bool ALPHA>
 __global__ __launch_bounds__(256) void blend_absgrad_kernel(ViewParams vp, const GaussRec* __restrict__ rec,
                                                             const uint32_t* __restrict__ ids,
@@ -1115,58 +1229,29 @@ __global__ __launch_bounds__(256) void blend_absgrad_kernel(ViewParams vp, const
     __shared__ uint16_t s_list[4][BATCH];
     __shared__ uint32_t s_wmax[4];
 
-    const int num_tiles = vp.gx * vp.gy;
-    const int tile = swizzled_tile(blockIdx.x, num_tiles);
-    const int tx = tile % vp.gx, ty = tile / vp.gx;
-    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
-    const int px = tx * TILE + (w & 1) * 8 + (lane & 7);
-    const int py = ty * TILE + (w >> 1) * 8 + (lane >> 3);
-    const bool inside = px < vp.W && py < vp.H;
-    const float pxf = (float)px, pyf = (float)py;
-    const float tx0 = (float)(tx * TILE), ty0 = (float)(ty * TILE);
-    const uint2 range = ranges[tile];
-    const uint64_t lt_mask = (1ull << lane) - 1ull;
-    const size_t N = (size_t)vp.W * vp.H;
-    const size_t pix = (size_t)py * vp.W + px;
-
+    const ReplayTile t = replay_tile(vp, ranges);
+    const bool inside = t.inside;
+    const size_t pix = t.pix;
     BwdPix st;
     st.T = inside ? final_T[pix] : 1.0f;
     st.last = inside ? n_contrib[pix] : 0u;
     st.dL0 = st.dL1 = st.dL2 = 0.f;
-    if (inside) { st.dL0 = dL_dcolor[pix]; st.dL1 = dL_dcolor[N + pix]; st.dL2 = dL_dcolor[2 * N + pix]; }
+    if (inside) { st.dL0 = dL_dcolor[pix]; st.dL1 = dL_dcolor[t.N + pix]; st.dL2 = dL_dcolor[2 * t.N + pix]; }
     st.dLd = (DEPTH && inside) ? dL_ddepth[pix] : 0.f;
-
-    const uint32_t wave_last = wave_max_u32(st.last);
-    if (lane == 0) s_wmax[w] = wave_last;
-    __syncthreads();
-    const uint32_t tile_last = max(max(s_wmax[0], s_wmax[1]), max(s_wmax[2], s_wmax[3]));
+    const ReplayEnds ends = replay_ends(st.last, s_wmax, t.w, t.lane);
 
     bwd_pix_start_S<ALPHA>(st, vp, inside, pix, dL_dalpha);
 
-    const int nb = ((int)tile_last + BATCH - 1) / BATCH;
+    const int nb = ((int)ends.tile_last + BATCH - 1) / BATCH;
     for (int b = nb - 1; b >= 0; --b) {
         __syncthreads();                              // previous batch fully consumed
         const int base = b * BATCH;
-        const int n = min(BATCH, (int)tile_last - base);
-        if (tid < n) {
-            const uint32_t id = ids[range.x + base + tid];
-            const float4 r0 = rec[id].r0, r1 = rec[id].r1;
-            const float4 r2 = rec[id].r2;
-            s_r0[tid] = doubled_w(r0); s_r1[tid] = r1; s_b[tid] = make_float2(r2.x, sign_test_bound(r1.y)); s_id[tid] = id;
-            if constexpr (DEPTH) s_z[tid] = r2.y;
-            s_mask[tid] = quadrant_mask(r0, r1.x, r2.w, tx0, ty0);
-        }
-        __syncthreads();
-        int cnt = 0;
-#pragma unroll
-        for (int c = 0; c < BATCH / 64; ++c) {
-            const int e = c * 64 + lane;
-            const bool hit = e < n && (uint32_t)(base + e) < wave_last && ((s_mask[e] >> w) & 1u);
-            const uint64_t bal = __ballot(hit);
-            if (hit) s_list[w][cnt + __popcll(bal & lt_mask)] = (uint16_t)e;
-            cnt += __popcll(bal);
-        }
-        absgrad_walk<DEPTH>(s_list[w], cnt, base, s_r0, s_r1, s_b, s_id, pxf, pyf, st, lane, acc, s_z);
+        const int cnt = stage_and_list_colour(t, rec, ids, base, ends, s_r0, s_r1, s_mask, s_list[t.w],
+                                              [&](int k, uint32_t id, const float4&, const float4& r1, const float4& r2) {
+            s_b[k] = make_float2(r2.x, sign_test_bound(r1.y)); s_id[k] = id;
+            if constexpr (DEPTH) s_z[k] = r2.y;
+        });
+        absgrad_walk<DEPTH>(s_list[t.w], cnt, base, s_r0, s_r1, s_b, s_id, t.pxf, t.pyf, st, t.lane, acc, s_z);
     }
 }
 
@@ -1185,9 +1270,9 @@ __global__ __launch_bounds__(256) void absgrad_finish_kernel(int P, float sx, fl
 // optional weight map m_p >= 0,
 //     weight_sum = sum_p m_p w_ip,   weight_max = max_p m_p w_ip,   pixel_count = #{p : m_p > 0, pair (i, p) blended}
 // with w_ip = alpha_ip T_ip = PairGrad::dch, the weight of dL/dC in the colour gradient.  Like absgrad, w_ip exists only in front
-// of the cross-pixel reduction: one more replay of the back-to-front walk of blend_backward_kernel (same staging, quadrant lists,
-// pair_alpha / pair_valid, and pair_grad on a zero dL/dC — only its T recurrence and dch stay alive), with a three-value tail.
-// No dL inputs, no gradients.  Opt-in: nothing of the default path calls or shares a kernel with it.
+// of the cross-pixel reduction: one more replay of the back-to-front walk of blend_backward_kernel (stage_and_list_colour without
+// blue and depth; pair_alpha / pair_valid, and pair_grad on a zero dL/dC — only its T recurrence and dch stay alive), with a
+// three-value tail.  No dL inputs, no gradients.  Opt-in: nothing of the default path calls or shares a kernel with it.
 // ---------------------------------------------------------------------------------------------
 // One accumulator row per Gaussian (CONTRIB_ACC_BYTES): the caller owns it across views.
 struct ContribAcc {
@@ -1252,7 +1337,7 @@ __device__ __forceinline__ void contrib_walk(const uint16_t* lp, int cnt, int ba
     }
 }
 
-// One 256-thread workgroup per tile, one 8x8 quadrant per wave, as blend_absgrad_kernel (one shape for every tile count).
+// The replay skeleton around a BwdPix with zero dL/dC and contrib_walk.
 // pixel_weights [H,W] (WEIGHTED): a negative or NaN weight counts as 0; finite weights only reach the products.
 template <bool WEIGHTED>
 __global__ __launch_bounds__(256) void blend_contrib_kernel(ViewParams vp, const GaussRec* __restrict__ rec,
@@ -1269,19 +1354,9 @@ __global__ __launch_bounds__(256) void blend_contrib_kernel(ViewParams vp, const
     __shared__ uint16_t s_list[4][BATCH];
     __shared__ uint32_t s_wmax[4];
 
-    const int num_tiles = vp.gx * vp.gy;
-    const int tile = swizzled_tile(blockIdx.x, num_tiles);
-    const int tx = tile % vp.gx, ty = tile / vp.gx;
-    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
-    const int px = tx * TILE + (w & 1) * 8 + (lane & 7);
-    const int py = ty * TILE + (w >> 1) * 8 + (lane >> 3);
-    const bool inside = px < vp.W && py < vp.H;
-    const float pxf = (float)px, pyf = (float)py;
-    const float tx0 = (float)(tx * TILE), ty0 = (float)(ty * TILE);
-    const uint2 range = ranges[tile];
-    const uint64_t lt_mask = (1ull << lane) - 1ull;
-    const size_t pix = (size_t)py * vp.W + px;
-
+    const ReplayTile t = replay_tile(vp, ranges);
+    const bool inside = t.inside;
+    const size_t pix = t.pix;
     BwdPix st;
     st.T = inside ? final_T[pix] : 1.0f;
     st.last = inside ? n_contrib[pix] : 0u;
@@ -1293,36 +1368,18 @@ __global__ __launch_bounds__(256) void blend_contrib_kernel(ViewParams vp, const
         m = pw > 0.0f ? fminf(pw, 3.4028234664e38f) : 0.0f;    // NaN and negatives fail the comparison
     }
     const uint64_t wmask = __builtin_amdgcn_ballot_w64(m > 0.0f);
-    const uint32_t aoff = lane < 3 ? 8u * (uint32_t)lane : 0xFFFFFFFFu;      // byte offset of the lane's slot; none: no atomic
+    const uint32_t aoff = t.lane < 3 ? 8u * (uint32_t)t.lane : 0xFFFFFFFFu;  // byte offset of the lane's slot; none: no atomic
+    const ReplayEnds ends = replay_ends(st.last, s_wmax, t.w, t.lane);
 
-    const uint32_t wave_last = wave_max_u32(st.last);
-    if (lane == 0) s_wmax[w] = wave_last;
-    __syncthreads();
-    const uint32_t tile_last = max(max(s_wmax[0], s_wmax[1]), max(s_wmax[2], s_wmax[3]));
-
-    const int nb = ((int)tile_last + BATCH - 1) / BATCH;
+    const int nb = ((int)ends.tile_last + BATCH - 1) / BATCH;
     for (int b = nb - 1; b >= 0; --b) {
         __syncthreads();                              // previous batch fully consumed
         const int base = b * BATCH;
-        const int n = min(BATCH, (int)tile_last - base);
-        if (tid < n) {
-            const uint32_t id = ids[range.x + base + tid];
-            const float4 r0 = rec[id].r0, r1 = rec[id].r1;
-            const float4 r2 = rec[id].r2;
-            s_r0[tid] = doubled_w(r0); s_r1[tid] = r1; s_bound[tid] = sign_test_bound(r1.y); s_id[tid] = id;
-            s_mask[tid] = quadrant_mask(r0, r1.x, r2.w, tx0, ty0);
-        }
-        __syncthreads();
-        int cnt = 0;
-#pragma unroll
-        for (int c = 0; c < BATCH / 64; ++c) {
-            const int e = c * 64 + lane;
-            const bool hit = e < n && (uint32_t)(base + e) < wave_last && ((s_mask[e] >> w) & 1u);
-            const uint64_t bal = __ballot(hit);
-            if (hit) s_list[w][cnt + __popcll(bal & lt_mask)] = (uint16_t)e;
-            cnt += __popcll(bal);
-        }
-        contrib_walk<WEIGHTED>(s_list[w], cnt, base, s_r0, s_r1, s_bound, s_id, pxf, pyf, st, m, wmask, aoff, acc);
+        const int cnt = stage_and_list_colour(t, rec, ids, base, ends, s_r0, s_r1, s_mask, s_list[t.w],
+                                              [&](int k, uint32_t id, const float4&, const float4& r1, const float4&) {
+            s_bound[k] = sign_test_bound(r1.y); s_id[k] = id;
+        });
+        contrib_walk<WEIGHTED>(s_list[t.w], cnt, base, s_r0, s_r1, s_bound, s_id, t.pxf, t.pyf, st, m, wmask, aoff, acc);
     }
 }
 
@@ -1343,12 +1400,12 @@ __global__ __launch_bounds__(256) void contrib_finish_kernel(int P, const Contri
 //     F[c,p] = sum_i f_ic w_ip          dL/df_ic = sum_p G_cp w_ip          (G = dL/dF)
 // and, as C more colour channels, a share of dL/dalpha: q_f from e_ip = sum_c G_cp f_ic in the place of g_i with a recurrence S_f
 // of its own that starts at 0; its six geometry sums are ADDED to record slots 0..5 in front of the ordinary blend backward.
-// Two more replays of the back-to-front walk of blend_backward_kernel (quadrant lists, pair_alpha / pair_valid / pair_grad as
-// in blend_contrib_kernel: the same pairs, the same weights).  Staging as there, except that no colour is read here: the two
-// colour slots of the staged r1 carry the sign-test bound and the quadrant mask bits instead of arrays of their own — the 2 KB
-// of LDS that keep eight waves per SIMD beside the feature block.  Channels go in blocks of CB, one launch per block — every
-// block is linear and independent, the geometry sums included.  A block's CB features of each staged entry lie in LDS and are
-// read at a wave-uniform address.  Opt-in: nothing of the default path calls or shares a kernel with them.
+// Two more replays of the back-to-front walk of blend_backward_kernel (pair_alpha / pair_valid / pair_grad as in
+// blend_contrib_kernel: the same pairs, the same weights).  No colour is read here, so the staging is stage_and_list_packed: the
+// 2 KB of LDS it saves keep eight waves per SIMD beside the feature block, which its `extra` fills (stage_feature_row).
+// Channels go in blocks of CB, one launch per block — every block is linear and independent, the geometry sums included.  A
+// block's CB features of each staged entry lie in LDS and are read at a wave-uniform address.  Opt-in: nothing of the default
+// path calls or shares a kernel with them.
 // ---------------------------------------------------------------------------------------------
 constexpr int FEAT_CB = 8;          // channels per launch (the resource table behind the choice)
 
@@ -1398,7 +1455,7 @@ __device__ __forceinline__ void features_forward_walk(const uint16_t* lp, int cn
 }
 
 // out [C,H,W]: channels c0 .. c0 + CB - 1 (the real ones) of every inside pixel, plain stores; a pixel with no counted pair
-// stores 0.  One 256-thread workgroup per tile, one 8x8 quadrant per wave, as blend_contrib_kernel.
+// stores 0.  The replay skeleton around CB accumulators and features_forward_walk.
 template <int CB>
 __global__ __launch_bounds__(256) void blend_features_forward_kernel(ViewParams vp, const GaussRec* __restrict__ rec,
                                                                      const uint32_t* __restrict__ ids,
@@ -1413,20 +1470,9 @@ __global__ __launch_bounds__(256) void blend_features_forward_kernel(ViewParams 
     __shared__ uint16_t s_list[4][BATCH];
     __shared__ uint32_t s_wmax[4];
 
-    const int num_tiles = vp.gx * vp.gy;
-    const int tile = swizzled_tile(blockIdx.x, num_tiles);
-    const int tx = tile % vp.gx, ty = tile / vp.gx;
-    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
-    const int px = tx * TILE + (w & 1) * 8 + (lane & 7);
-    const int py = ty * TILE + (w >> 1) * 8 + (lane >> 3);
-    const bool inside = px < vp.W && py < vp.H;
-    const float pxf = (float)px, pyf = (float)py;
-    const float tx0 = (float)(tx * TILE), ty0 = (float)(ty * TILE);
-    const uint2 range = ranges[tile];
-    const uint64_t lt_mask = (1ull << lane) - 1ull;
-    const size_t N = (size_t)vp.W * vp.H;
-    const size_t pix = (size_t)py * vp.W + px;
-
+    const ReplayTile t = replay_tile(vp, ranges);
+    const bool inside = t.inside;
+    const size_t pix = t.pix;
     BwdPix st;
     st.T = inside ? final_T[pix] : 1.0f;
     st.last = inside ? n_contrib[pix] : 0u;
@@ -1435,41 +1481,22 @@ __global__ __launch_bounds__(256) void blend_features_forward_kernel(ViewParams 
     float acc[CB];
 #pragma unroll
     for (int c = 0; c < CB; ++c) acc[c] = 0.f;
+    const ReplayEnds ends = replay_ends(st.last, s_wmax, t.w, t.lane);
 
-    const uint32_t wave_last = wave_max_u32(st.last);
-    if (lane == 0) s_wmax[w] = wave_last;
-    __syncthreads();
-    const uint32_t tile_last = max(max(s_wmax[0], s_wmax[1]), max(s_wmax[2], s_wmax[3]));
-
-    const int nb = ((int)tile_last + BATCH - 1) / BATCH;
+    const int nb = ((int)ends.tile_last + BATCH - 1) / BATCH;
     for (int b = nb - 1; b >= 0; --b) {
         __syncthreads();                              // previous batch fully consumed
         const int base = b * BATCH;
-        const int n = min(BATCH, (int)tile_last - base);
-        if (tid < n) {
-            const uint32_t id = ids[range.x + base + tid];
-            const float4 r0 = rec[id].r0, r1 = rec[id].r1;
-            const float4 r2 = rec[id].r2;
-            s_r0[tid] = doubled_w(r0);
-            s_r1[tid] = make_float4(r1.x, r1.y, sign_test_bound(r1.y), __uint_as_float(quadrant_mask(r0, r1.x, r2.w, tx0, ty0)));
-            stage_feature_row<CB>(s_f + tid * (CB / 4), features, id, C, c0, vec != 0);
-        }
-        __syncthreads();
-        int cnt = 0;
-#pragma unroll
-        for (int c = 0; c < BATCH / 64; ++c) {
-            const int e = c * 64 + lane;
-            const bool hit = e < n && (uint32_t)(base + e) < wave_last && ((__float_as_uint(s_r1[e].w) >> w) & 1u);
-            const uint64_t bal = __ballot(hit);
-            if (hit) s_list[w][cnt + __popcll(bal & lt_mask)] = (uint16_t)e;
-            cnt += __popcll(bal);
-        }
-        features_forward_walk<CB>(s_list[w], cnt, base, s_r0, s_r1, s_f, pxf, pyf, st, acc);
+        const int cnt = stage_and_list_packed(t, rec, ids, base, ends, s_r0, s_r1, s_list[t.w],
+                                              [&](int k, uint32_t id, const float4&, const float4&, const float4&) {
+            stage_feature_row<CB>(s_f + k * (CB / 4), features, id, C, c0, vec != 0);
+        });
+        features_forward_walk<CB>(s_list[t.w], cnt, base, s_r0, s_r1, s_f, t.pxf, t.pyf, st, acc);
     }
     if (inside) {
 #pragma unroll
         for (int c = 0; c < CB; ++c)
-            if (c0 + c < C) out[(size_t)(c0 + c) * N + pix] = acc[c];
+            if (c0 + c < C) out[(size_t)(c0 + c) * t.N + pix] = acc[c];
     }
 }
 
@@ -1533,20 +1560,9 @@ __global__ __launch_bounds__(256) void blend_features_backward_kernel(ViewParams
     __shared__ uint16_t s_list[4][BATCH];
     __shared__ uint32_t s_wmax[4];
 
-    const int num_tiles = vp.gx * vp.gy;
-    const int tile = swizzled_tile(blockIdx.x, num_tiles);
-    const int tx = tile % vp.gx, ty = tile / vp.gx;
-    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
-    const int px = tx * TILE + (w & 1) * 8 + (lane & 7);
-    const int py = ty * TILE + (w >> 1) * 8 + (lane >> 3);
-    const bool inside = px < vp.W && py < vp.H;
-    const float pxf = (float)px, pyf = (float)py;
-    const float tx0 = (float)(tx * TILE), ty0 = (float)(ty * TILE);
-    const uint2 range = ranges[tile];
-    const uint64_t lt_mask = (1ull << lane) - 1ull;
-    const size_t N = (size_t)vp.W * vp.H;
-    const size_t pix = (size_t)py * vp.W + px;
-
+    const ReplayTile t = replay_tile(vp, ranges);
+    const bool inside = t.inside;
+    const size_t pix = t.pix;
     BwdPix st;
     st.T = inside ? final_T[pix] : 1.0f;
     st.last = inside ? n_contrib[pix] : 0u;
@@ -1555,42 +1571,24 @@ __global__ __launch_bounds__(256) void blend_features_backward_kernel(ViewParams
     st.S = 0.f;                                            // S_f: no background term
     float G[CB];
 #pragma unroll
-    for (int c = 0; c < CB; ++c) G[c] = (inside && c0 + c < C) ? dL_dF[(size_t)(c0 + c) * N + pix] : 0.f;
+    for (int c = 0; c < CB; ++c) G[c] = (inside && c0 + c < C) ? dL_dF[(size_t)(c0 + c) * t.N + pix] : 0.f;
+    const ReplayEnds ends = replay_ends(st.last, s_wmax, t.w, t.lane);
 
-    const uint32_t wave_last = wave_max_u32(st.last);
-    if (lane == 0) s_wmax[w] = wave_last;
-    __syncthreads();
-    const uint32_t tile_last = max(max(s_wmax[0], s_wmax[1]), max(s_wmax[2], s_wmax[3]));
-
-    const bool alane = IS_ATOMIC_LANE(false, lane);
-    const uint32_t aoff = row_reduce_component<false>(lane);
-    const bool flane = lane < 16 && !(lane & 2);           // the eight lanes that own components 0..7
+    const bool alane = IS_ATOMIC_LANE(false, t.lane);
+    const uint32_t aoff = row_reduce_component<false>(t.lane);
+    const bool flane = t.lane < 16 && !(t.lane & 2);       // the eight lanes that own components 0..7
     const uint32_t foff = aoff;
 
-    const int nb = ((int)tile_last + BATCH - 1) / BATCH;
+    const int nb = ((int)ends.tile_last + BATCH - 1) / BATCH;
     for (int b = nb - 1; b >= 0; --b) {
         __syncthreads();                              // previous batch fully consumed
         const int base = b * BATCH;
-        const int n = min(BATCH, (int)tile_last - base);
-        if (tid < n) {
-            const uint32_t id = ids[range.x + base + tid];
-            const float4 r0 = rec[id].r0, r1 = rec[id].r1;
-            const float4 r2 = rec[id].r2;
-            s_r0[tid] = doubled_w(r0); s_id[tid] = id;
-            s_r1[tid] = make_float4(r1.x, r1.y, sign_test_bound(r1.y), __uint_as_float(quadrant_mask(r0, r1.x, r2.w, tx0, ty0)));
-            if constexpr (GEOM) stage_feature_row<CB>(s_f + tid * (CB / 4), features, id, C, c0, vec != 0);
-        }
-        __syncthreads();
-        int cnt = 0;
-#pragma unroll
-        for (int c = 0; c < BATCH / 64; ++c) {
-            const int e = c * 64 + lane;
-            const bool hit = e < n && (uint32_t)(base + e) < wave_last && ((__float_as_uint(s_r1[e].w) >> w) & 1u);
-            const uint64_t bal = __ballot(hit);
-            if (hit) s_list[w][cnt + __popcll(bal & lt_mask)] = (uint16_t)e;
-            cnt += __popcll(bal);
-        }
-        features_backward_walk<CB, GEOM>(s_list[w], cnt, base, s_r0, s_r1, s_id, s_f, pxf, pyf, st, G, alane, aoff,
+        const int cnt = stage_and_list_packed(t, rec, ids, base, ends, s_r0, s_r1, s_list[t.w],
+                                              [&](int k, uint32_t id, const float4&, const float4&, const float4&) {
+            s_id[k] = id;
+            if constexpr (GEOM) stage_feature_row<CB>(s_f + k * (CB / 4), features, id, C, c0, vec != 0);
+        });
+        features_backward_walk<CB, GEOM>(s_list[t.w], cnt, base, s_r0, s_r1, s_id, s_f, t.pxf, t.pyf, st, G, alane, aoff,
                                          grad_rec, flane, foff, acc);
     }
 }
@@ -1613,9 +1611,10 @@ __global__ __launch_bounds__(256) void features_finish_kernel(int P, int C, int 
 // w_i = alpha_i T_i, z_i the view depth the depth map blends):
 //     Dist = 2 sum_{j<i} w_i w_j (z_i - z_j) = 2 sum_i w_i (R_i - z_i (T_{i+1} - T_f)),     R_i = sum_{k>i} w_k z_k
 // Quadratic in the weights, so it exists only inside the walk: two more replays of blend_backward_kernel's back-to-front walk
-// (staging and quadrant lists of blend_features_*, plus s_z).  Back to front the suffix moment R_i and the suffix weight
-// T_{i+1} - T_f are what the walk has in hand; the backward needs the prefix too and takes it from M = sum_i w_i z_i, which the
-// forward stores:  sum_{j<i} w_j z_j = M - R_i - w_i z_i,  sum_{j<i} w_j = 1 - T_i.  With B_i = 1 + T_f - T_i - T_{i+1}
+// (stage_and_list_packed, with s_z — and s_id in the backward — as the extra).  Back to front the suffix moment R_i and the
+// suffix weight T_{i+1} - T_f are what the walk has in hand; the backward needs the prefix too and takes it from
+// M = sum_i w_i z_i, which the forward stores:  sum_{j<i} w_j z_j = M - R_i - w_i z_i,  sum_{j<i} w_j = 1 - T_i.
+// With B_i = 1 + T_f - T_i - T_{i+1}
 //     dDist/dw_i = 2 (z_i B_i - (M - R_i - w_i z_i) + R_i)          dDist/dz_i = 2 w_i B_i
 // G dDist/dw_i enters the S recurrence as the pair's only colour (S starts at 0: no background term), exactly as e does in
 // features_backward_walk; the six sums of q go to record slots 0..5 and sum G dDist/dz_i to slot 9 through reduce_and_add<true>.
@@ -1640,35 +1639,6 @@ __device__ __forceinline__ DistStep dist_step(float& T, const PairAlpha& a, uint
 // R += w z~: ONE expression for both kernels (explicit fmaf: no contraction choice left to the compiler)
 __device__ __forceinline__ float dist_moment_add(float R, float w, float zt) { return fmaf(w, zt, R); }
 
-// Staging and quadrant lists shared by the two kernels.  s_r1: {C', p0', sign_test_bound, quadrant mask bits} as in the feature
-// kernels.  Returns the number of entries in this wave's list.
-template <bool IDS>
-__device__ __forceinline__ int dist_stage_and_list(const GaussRec* __restrict__ rec, const uint32_t* __restrict__ ids, uint32_t first,
-                                                   int base, int n, int tid, int w, int lane, uint32_t wave_last, uint64_t lt_mask,
-                                                   float tx0, float ty0, float4* s_r0, float4* s_r1, float* s_z, uint32_t* s_id,
-                                                   uint16_t* s_listw) {
-    if (tid < n) {
-        const uint32_t id = ids[first + base + tid];
-        const float4 r0 = rec[id].r0, r1 = rec[id].r1;
-        const float4 r2 = rec[id].r2;
-        s_r0[tid] = doubled_w(r0);
-        s_r1[tid] = make_float4(r1.x, r1.y, sign_test_bound(r1.y), __uint_as_float(quadrant_mask(r0, r1.x, r2.w, tx0, ty0)));
-        s_z[tid] = r2.y;
-        if constexpr (IDS) s_id[tid] = id;
-    }
-    __syncthreads();
-    int cnt = 0;
-#pragma unroll
-    for (int c = 0; c < BATCH / 64; ++c) {
-        const int e = c * 64 + lane;
-        const bool hit = e < n && (uint32_t)(base + e) < wave_last && ((__float_as_uint(s_r1[e].w) >> w) & 1u);
-        const uint64_t bal = __ballot(hit);
-        if (hit) s_listw[cnt + __popcll(bal & lt_mask)] = (uint16_t)e;
-        cnt += __popcll(bal);
-    }
-    return cnt;
-}
-
 // out_distortion [H,W] = Dist, out_moment [H,W] = M = sum_i w_i (z_i - z_ref): plain stores for the inside pixels; a pixel with
 // fewer than two counted pairs stores Dist = 0.  One 256-thread workgroup per tile, one 8x8 quadrant per wave.
 __global__ __launch_bounds__(256) void blend_distortion_forward_kernel(ViewParams vp, const GaussRec* __restrict__ rec,
@@ -1683,41 +1653,26 @@ __global__ __launch_bounds__(256) void blend_distortion_forward_kernel(ViewParam
     __shared__ uint16_t s_list[4][BATCH];
     __shared__ uint32_t s_wmax[4];
 
-    const int num_tiles = vp.gx * vp.gy;
-    const int tile = swizzled_tile(blockIdx.x, num_tiles);
-    const int tx = tile % vp.gx, ty = tile / vp.gx;
-    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
-    const int px = tx * TILE + (w & 1) * 8 + (lane & 7);
-    const int py = ty * TILE + (w >> 1) * 8 + (lane >> 3);
-    const bool inside = px < vp.W && py < vp.H;
-    const float pxf = (float)px, pyf = (float)py;
-    const float tx0 = (float)(tx * TILE), ty0 = (float)(ty * TILE);
-    const uint2 range = ranges[tile];
-    const uint64_t lt_mask = (1ull << lane) - 1ull;
-    const size_t pix = (size_t)py * vp.W + px;
-
-    const float Tf = inside ? final_T[pix] : 1.0f;
-    const uint32_t last = inside ? n_contrib[pix] : 0u;
+    const ReplayTile t = replay_tile(vp, ranges);
+    const float Tf = t.inside ? final_T[t.pix] : 1.0f;
+    const uint32_t last = t.inside ? n_contrib[t.pix] : 0u;
     float T = Tf, R = 0.f, acc = 0.f;
+    const ReplayEnds ends = replay_ends(last, s_wmax, t.w, t.lane);
+    const float zref = ends.tile_last > 0u ? rec[ids[t.range.x]].r2.y : 0.f;      // (a tile that blended has a first entry)
 
-    const uint32_t wave_last = wave_max_u32(last);
-    if (lane == 0) s_wmax[w] = wave_last;
-    __syncthreads();
-    const uint32_t tile_last = max(max(s_wmax[0], s_wmax[1]), max(s_wmax[2], s_wmax[3]));
-    const float zref = tile_last > 0u ? rec[ids[range.x]].r2.y : 0.f;      // (a tile that blended has a first entry)
-
-    const int nb = ((int)tile_last + BATCH - 1) / BATCH;
+    const int nb = ((int)ends.tile_last + BATCH - 1) / BATCH;
     for (int b = nb - 1; b >= 0; --b) {
         __syncthreads();                              // previous batch fully consumed
         const int base = b * BATCH;
-        const int n = min(BATCH, (int)tile_last - base);
-        const int cnt = dist_stage_and_list<false>(rec, ids, range.x, base, n, tid, w, lane, wave_last, lt_mask, tx0, ty0, s_r0,
-                                                   s_r1, s_z, nullptr, s_list[w]);
-        const uint16_t* lp = s_list[w];
+        const int cnt = stage_and_list_packed(t, rec, ids, base, ends, s_r0, s_r1, s_list[t.w],
+                                              [&](int k, uint32_t, const float4&, const float4&, const float4& r2) {
+            s_z[k] = r2.y;
+        });
+        const uint16_t* lp = s_list[t.w];
         for (int j = cnt - 1; j >= 0; --j) {
             const int e = lp[j];
             const float4 r0 = s_r0[e], r1 = s_r1[e];
-            const float dx = r0.x - pxf, dy = r0.y - pyf;
+            const float dx = r0.x - t.pxf, dy = r0.y - t.pyf;
             const PairAlpha a = pair_alpha(r0, r1, dx, dy);
             const uint64_t validm = pair_valid(a, (uint32_t)(base + e), last, r1.z);
             if (validm == 0) continue;
@@ -1728,7 +1683,7 @@ __global__ __launch_bounds__(256) void blend_distortion_forward_kernel(ViewParam
             R = dist_moment_add(R, d.w, zt);
         }
     }
-    if (inside) { out_distortion[pix] = 2.0f * acc; out_moment[pix] = R; }
+    if (t.inside) { out_distortion[t.pix] = 2.0f * acc; out_moment[t.pix] = R; }
 }
 
 // dL_ddist [H,W] = G, moment [H,W] = the forward's out_moment.  ADDS the six sums of q to record slots 0..5 and
@@ -1747,47 +1702,32 @@ __global__ __launch_bounds__(256) void blend_distortion_backward_kernel(ViewPara
     __shared__ uint16_t s_list[4][BATCH];
     __shared__ uint32_t s_wmax[4];
 
-    const int num_tiles = vp.gx * vp.gy;
-    const int tile = swizzled_tile(blockIdx.x, num_tiles);
-    const int tx = tile % vp.gx, ty = tile / vp.gx;
-    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
-    const int px = tx * TILE + (w & 1) * 8 + (lane & 7);
-    const int py = ty * TILE + (w >> 1) * 8 + (lane >> 3);
-    const bool inside = px < vp.W && py < vp.H;
-    const float pxf = (float)px, pyf = (float)py;
-    const float tx0 = (float)(tx * TILE), ty0 = (float)(ty * TILE);
-    const uint2 range = ranges[tile];
-    const uint64_t lt_mask = (1ull << lane) - 1ull;
-    const size_t pix = (size_t)py * vp.W + px;
-
-    const float Tf = inside ? final_T[pix] : 1.0f;
-    const uint32_t last = inside ? n_contrib[pix] : 0u;
-    const float G2 = inside ? 2.0f * dL_ddist[pix] : 0.f;
-    const float M = inside ? moment[pix] : 0.f;
+    const ReplayTile t = replay_tile(vp, ranges);
+    const float Tf = t.inside ? final_T[t.pix] : 1.0f;
+    const uint32_t last = t.inside ? n_contrib[t.pix] : 0u;
+    const float G2 = t.inside ? 2.0f * dL_ddist[t.pix] : 0.f;
+    const float M = t.inside ? moment[t.pix] : 0.f;
     const float oneTf = 1.0f + Tf;
     float T = Tf, R = 0.f, S = 0.f;
+    const ReplayEnds ends = replay_ends(last, s_wmax, t.w, t.lane);
+    const float zref = ends.tile_last > 0u ? rec[ids[t.range.x]].r2.y : 0.f;      // the forward's
 
-    const uint32_t wave_last = wave_max_u32(last);
-    if (lane == 0) s_wmax[w] = wave_last;
-    __syncthreads();
-    const uint32_t tile_last = max(max(s_wmax[0], s_wmax[1]), max(s_wmax[2], s_wmax[3]));
-    const float zref = tile_last > 0u ? rec[ids[range.x]].r2.y : 0.f;      // the forward's
+    const bool alane = IS_ATOMIC_LANE(true, t.lane);
+    const uint32_t aoff = row_reduce_component<true>(t.lane);
 
-    const bool alane = IS_ATOMIC_LANE(true, lane);
-    const uint32_t aoff = row_reduce_component<true>(lane);
-
-    const int nb = ((int)tile_last + BATCH - 1) / BATCH;
+    const int nb = ((int)ends.tile_last + BATCH - 1) / BATCH;
     for (int b = nb - 1; b >= 0; --b) {
         __syncthreads();                              // previous batch fully consumed
         const int base = b * BATCH;
-        const int n = min(BATCH, (int)tile_last - base);
-        const int cnt = dist_stage_and_list<true>(rec, ids, range.x, base, n, tid, w, lane, wave_last, lt_mask, tx0, ty0, s_r0,
-                                                  s_r1, s_z, s_id, s_list[w]);
-        const uint16_t* lp = s_list[w];
+        const int cnt = stage_and_list_packed(t, rec, ids, base, ends, s_r0, s_r1, s_list[t.w],
+                                              [&](int k, uint32_t id, const float4&, const float4&, const float4& r2) {
+            s_z[k] = r2.y; s_id[k] = id;
+        });
+        const uint16_t* lp = s_list[t.w];
         for (int j = cnt - 1; j >= 0; --j) {
             const int e = lp[j];
             const float4 r0 = s_r0[e], r1 = s_r1[e];
-            const float dx = r0.x - pxf, dy = r0.y - pyf;
+            const float dx = r0.x - t.pxf, dy = r0.y - t.pyf;
             const PairAlpha a = pair_alpha(r0, r1, dx, dy);
             const uint64_t validm = pair_valid(a, (uint32_t)(base + e), last, r1.z);
             if (validm == 0) continue;
@@ -1816,8 +1756,8 @@ __global__ __launch_bounds__(256) void blend_distortion_backward_kernel(ViewPara
 // rule): the entry whose blending takes T to <= 0.5, or the last blended entry of a ray that never gets there.
 //     median_depth = z_m (GaussRec.r2.y, the depth the depth map blends; 0.0f where nothing was blended)
 //     median_id    = its row in the model (-1 where nothing was blended)
-// T_i exists only inside the walk, hence one more replay of the tile lists (staging and quadrant lists of the distortion
-// kernels) — but FRONT TO BACK, unlike the other replays: the selection compares T_i itself with 0.5, and only the forward's own
+// T_i exists only inside the walk, hence one more replay of the tile lists (stage_and_list_packed with s_z and s_id as the
+// extra) — but FRONT TO BACK, unlike the other replays: the selection compares T_i itself with 0.5, and only the forward's own
 // recurrence from T_1 = 1 reproduces the bits the render blended with (T_f divided back up differs in the last places, which
 // flips the entry on a ray that crosses near 0.5).  Front to back also ends early: a lane is finished once T <= 0.5 after a blend
 // or at n_contrib, a wave leaves its list and the workgroup its batch loop when all their lanes are.  While T_i > 0.5 and
@@ -1839,43 +1779,28 @@ __global__ __launch_bounds__(256) void blend_median_depth_forward_kernel(ViewPar
     __shared__ uint16_t s_list[4][BATCH];
     __shared__ uint32_t s_wmax[4];
 
-    const int num_tiles = vp.gx * vp.gy;
-    const int tile = swizzled_tile(blockIdx.x, num_tiles);
-    const int tx = tile % vp.gx, ty = tile / vp.gx;
-    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
-    const int px = tx * TILE + (w & 1) * 8 + (lane & 7);
-    const int py = ty * TILE + (w >> 1) * 8 + (lane >> 3);
-    const bool inside = px < vp.W && py < vp.H;
-    const float pxf = (float)px, pyf = (float)py;
-    const float tx0 = (float)(tx * TILE), ty0 = (float)(ty * TILE);
-    const uint2 range = ranges[tile];
-    const uint64_t lt_mask = (1ull << lane) - 1ull;
-    const size_t pix = (size_t)py * vp.W + px;
-
-    const uint32_t last = inside ? n_contrib[pix] : 0u;
+    const ReplayTile t = replay_tile(vp, ranges);
+    const uint32_t last = t.inside ? n_contrib[t.pix] : 0u;
     float T = 1.0f, zm = 0.0f;
     int32_t idm = -1;
-
-    const uint32_t wave_last = wave_max_u32(last);
-    if (lane == 0) s_wmax[w] = wave_last;
-    __syncthreads();
-    const uint32_t tile_last = max(max(s_wmax[0], s_wmax[1]), max(s_wmax[2], s_wmax[3]));
+    const ReplayEnds ends = replay_ends(last, s_wmax, t.w, t.lane);
 
     uint64_t open = __builtin_amdgcn_ballot_w64(last > 0u);          // lanes that have not reached their median entry yet
 
-    for (int base = 0; base < (int)tile_last; base += BATCH) {
+    for (int base = 0; base < (int)ends.tile_last; base += BATCH) {
         if (__syncthreads_and(open == 0)) break;      // every lane of the tile is finished; the barrier also protects the batch
-        const int n = min(BATCH, (int)tile_last - base);
         // (a finished wave stages its share of the batch and compacts nothing)
-        const uint32_t list_last = open ? wave_last : 0u;
-        const int cnt = dist_stage_and_list<true>(rec, ids, range.x, base, n, tid, w, lane, list_last, lt_mask, tx0, ty0, s_r0,
-                                                  s_r1, s_z, s_id, s_list[w]);
-        const uint16_t* lp = s_list[w];
+        const uint32_t list_last = open ? ends.wave_last : 0u;
+        const int cnt = stage_and_list_packed(t, rec, ids, base, ReplayEnds{list_last, ends.tile_last}, s_r0, s_r1, s_list[t.w],
+                                              [&](int k, uint32_t id, const float4&, const float4&, const float4& r2) {
+            s_z[k] = r2.y; s_id[k] = id;
+        });
+        const uint16_t* lp = s_list[t.w];
         for (int j = 0; j < cnt; ++j) {
             if (open == 0) break;
             const int e = lp[j];
             const float4 r0 = s_r0[e], r1 = s_r1[e];
-            const float dx = r0.x - pxf, dy = r0.y - pyf;
+            const float dx = r0.x - t.pxf, dy = r0.y - t.pyf;
             const PairAlpha a = pair_alpha(r0, r1, dx, dy);
             const uint32_t pos = (uint32_t)(base + e);
             const uint64_t validm = pair_valid(a, pos, last, r1.z) & open;
@@ -1893,27 +1818,20 @@ __global__ __launch_bounds__(256) void blend_median_depth_forward_kernel(ViewPar
             open &= ~at_end;
         }
     }
-    if (inside) { out_depth[pix] = zm; out_id[pix] = idm; }
+    if (t.inside) { out_depth[t.pix] = zm; out_id[t.pix] = idm; }
 }
 
 // median_id [H,W], dL_dmedian [H,W] = G: ADDS sum_{p: median_id[p] = i} G_p to slot 9 of record i.  The pixel mapping of the
-// blend kernels, so that a wave holds one 8x8 block: neighbouring pixels mostly share their median Gaussian, and one lane per
-// 80-byte record is the worst shape for an atomic wave-instruction.  The lanes of a wave that hold the same id are combined first
-// (leader's id broadcast, ballot of the equal lanes, wave total of their G) and the leader issues ONE add per distinct id.
+// replays (replay_pixel), so that a wave holds one 8x8 block: neighbouring pixels mostly share their median Gaussian, and one
+// lane per 80-byte record is the worst shape for an atomic wave-instruction.  The lanes of a wave that hold the same id are
+// combined first (leader's id broadcast, ballot of the equal lanes, wave total of their G) and the leader issues ONE add per
+// distinct id.
 __global__ __launch_bounds__(256) void median_depth_backward_kernel(ViewParams vp, int P, const int32_t* __restrict__ median_id,
                                                                     const float* __restrict__ dL_dmedian,
                                                                     grad_acc_t* __restrict__ grad_rec) {
-    const int num_tiles = vp.gx * vp.gy;
-    const int tile = swizzled_tile(blockIdx.x, num_tiles);
-    const int tx = tile % vp.gx, ty = tile / vp.gx;
-    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
-    const int px = tx * TILE + (w & 1) * 8 + (lane & 7);
-    const int py = ty * TILE + (w >> 1) * 8 + (lane >> 3);
-    const bool inside = px < vp.W && py < vp.H;
-    const size_t pix = (size_t)py * vp.W + px;
-
-    const int32_t id = inside ? median_id[pix] : -1;
-    const float g = inside ? dL_dmedian[pix] : 0.f;
+    const ReplayPixel p = replay_pixel(vp);
+    const int32_t id = p.inside ? median_id[p.pix] : -1;
+    const float g = p.inside ? dL_dmedian[p.pix] : 0.f;
     uint64_t rem = __builtin_amdgcn_ballot_w64(id >= 0 && id < P);   // (an id outside the model adds nothing)
     while (rem != 0) {
         const int leader = __builtin_ctzll(rem);
@@ -1921,7 +1839,7 @@ __global__ __launch_bounds__(256) void median_depth_backward_kernel(ViewParams v
         const bool mine = id == cur;
         const uint64_t same = __builtin_amdgcn_ballot_w64(mine);
         const float tot = wave_allreduce_sum(mine ? g : 0.f);
-        if (lane == leader) unsafeAtomicAdd(grad_rec + (size_t)cur * GRAD_REC_FLOATS + 9, (grad_acc_t)tot);
+        if (p.lane == leader) unsafeAtomicAdd(grad_rec + (size_t)cur * GRAD_REC_FLOATS + 9, (grad_acc_t)tot);
         rem &= ~same;
     }
 }
@@ -2171,35 +2089,30 @@ hipError_t launch_blend_backward(const ViewParams& vp, const char* geom, const u
 
 // msgs_absgrad: zero fill of the [P, 2] double accumulator, the replay (one of four <DEPTH, ALPHA> instantiations, the four-waves-
 // per-tile shape whatever the tile count and whatever route the main backward takes), the finish.  P == 0 is the caller's.
-hipError_t launch_blend_absgrad(const ViewParams& vp, int P, const char* geom, const uint32_t* ids, const uint2* ranges,
-                                const float* final_T, const uint32_t* n_contrib, const float* dL_dcolor, const float* dL_ddepth,
+hipError_t launch_blend_absgrad(const ReplayInputs& in, int P, const float* dL_dcolor, const float* dL_ddepth,
                                 const float* dL_dalpha, double* acc, float* out, hipStream_t s) {
-    const int tiles = vp.gx * vp.gy;
+    const int tiles = in.vp.gx * in.vp.gy;
     hipError_t e = launch_zero(acc, 2 * sizeof(double) * (size_t)P, s);
     if (e != hipSuccess) return e;
-    const GaussRec* rec = reinterpret_cast<const GaussRec*>(geom);
     if (tiles > 0)
         with_bool(dL_ddepth != nullptr, [&](auto DEPTH) { with_bool(dL_dalpha != nullptr, [&](auto ALPHA) {
             hipLaunchKernelGGL((blend_absgrad_kernel<decltype(DEPTH)::value, decltype(ALPHA)::value>), dim3(tiles), dim3(256), 0, s,
-                               vp, rec, ids, ranges, final_T, n_contrib, dL_dcolor, acc, dL_ddepth, dL_dalpha);
+                               in.vp, in.rec, in.ids, in.ranges, in.final_T, in.n_contrib, dL_dcolor, acc, dL_ddepth, dL_dalpha);
         }); });
     constexpr float LN2 = 0.69314718055994530942f;
-    hipLaunchKernelGGL(absgrad_finish_kernel, dim3((P + 255) / 256), dim3(256), 0, s, P, LN2 * vp.W, LN2 * vp.H,
+    hipLaunchKernelGGL(absgrad_finish_kernel, dim3((P + 255) / 256), dim3(256), 0, s, P, LN2 * in.vp.W, LN2 * in.vp.H,
                        (const double*)acc, out);
     return hipGetLastError();
 }
 
 // msgs_contrib_accumulate: the replay (the four-waves-per-tile shape whatever the tile count) adds one view to `acc`, which the
 // caller cleared or carries over from earlier views; msgs_contrib_finish: the accumulator as three [P] arrays.
-hipError_t launch_blend_contrib(const ViewParams& vp, const char* geom, const uint32_t* ids, const uint2* ranges,
-                                const float* final_T, const uint32_t* n_contrib, const float* pixel_weights, void* acc,
-                                hipStream_t s) {
-    const int tiles = vp.gx * vp.gy;
+hipError_t launch_blend_contrib(const ReplayInputs& in, const float* pixel_weights, void* acc, hipStream_t s) {
+    const int tiles = in.vp.gx * in.vp.gy;
     if (tiles <= 0) return hipSuccess;
-    const GaussRec* rec = reinterpret_cast<const GaussRec*>(geom);
     with_bool(pixel_weights != nullptr, [&](auto WEIGHTED) {
-        hipLaunchKernelGGL((blend_contrib_kernel<decltype(WEIGHTED)::value>), dim3(tiles), dim3(256), 0, s, vp, rec, ids, ranges,
-                           final_T, n_contrib, pixel_weights, (ContribAcc*)acc);
+        hipLaunchKernelGGL((blend_contrib_kernel<decltype(WEIGHTED)::value>), dim3(tiles), dim3(256), 0, s, in.vp, in.rec, in.ids,
+                           in.ranges, in.final_T, in.n_contrib, pixel_weights, (ContribAcc*)acc);
     });
     return hipGetLastError();
 }
@@ -2214,35 +2127,29 @@ hipError_t launch_contrib_finish(int P, const void* acc, float* weight_sum, floa
 // count).  16-byte row loads where every row of the block starts on a 16-byte boundary.
 static bool feature_rows_vectorise(const float* features, int C) { return C % 4 == 0 && ((uintptr_t)features & 15) == 0; }
 
-hipError_t launch_blend_features_forward(const ViewParams& vp, const char* geom, const uint32_t* ids, const uint2* ranges,
-                                         const float* final_T, const uint32_t* n_contrib, const float* features, int C,
-                                         float* out, hipStream_t s) {
-    const int tiles = vp.gx * vp.gy;
+hipError_t launch_blend_features_forward(const ReplayInputs& in, const float* features, int C, float* out, hipStream_t s) {
+    const int tiles = in.vp.gx * in.vp.gy;
     if (tiles <= 0) return hipSuccess;
-    const GaussRec* rec = reinterpret_cast<const GaussRec*>(geom);
     const int vec = feature_rows_vectorise(features, C);
     for (int c0 = 0; c0 < C; c0 += FEAT_CB)
-        hipLaunchKernelGGL((blend_features_forward_kernel<FEAT_CB>), dim3(tiles), dim3(256), 0, s, vp, rec, ids, ranges, final_T,
-                           n_contrib, features, C, c0, vec, out);
+        hipLaunchKernelGGL((blend_features_forward_kernel<FEAT_CB>), dim3(tiles), dim3(256), 0, s, in.vp, in.rec, in.ids, in.ranges,
+                           in.final_T, in.n_contrib, features, C, c0, vec, out);
     return hipGetLastError();
 }
 
 // acc: [P, FEAT_CB] doubles, cleared here and again by every finish; grad_rec: NULL = no geometry share
-hipError_t launch_blend_features_backward(const ViewParams& vp, int P, const char* geom, const uint32_t* ids, const uint2* ranges,
-                                          const float* final_T, const uint32_t* n_contrib, const float* features, int C,
-                                          const float* dL_dF, grad_acc_t* grad_rec, double* acc, float* dL_dfeatures,
-                                          hipStream_t s) {
-    const int tiles = vp.gx * vp.gy;
+hipError_t launch_blend_features_backward(const ReplayInputs& in, int P, const float* features, int C, const float* dL_dF,
+                                          grad_acc_t* grad_rec, double* acc, float* dL_dfeatures, hipStream_t s) {
+    const int tiles = in.vp.gx * in.vp.gy;
     if (tiles <= 0 || P <= 0) return hipSuccess;
-    const GaussRec* rec = reinterpret_cast<const GaussRec*>(geom);
     const int vec = feature_rows_vectorise(features, C);
     hipError_t e = launch_zero(acc, sizeof(double) * FEAT_CB * (size_t)P, s);
     if (e != hipSuccess) return e;
     const unsigned finish_blocks = (unsigned)(((size_t)P * FEAT_CB + 255) / 256);
     for (int c0 = 0; c0 < C; c0 += FEAT_CB) {
         with_bool(grad_rec != nullptr, [&](auto GEOM) {
-            hipLaunchKernelGGL((blend_features_backward_kernel<FEAT_CB, decltype(GEOM)::value>), dim3(tiles), dim3(256), 0, s, vp,
-                               rec, ids, ranges, final_T, n_contrib, features, C, c0, vec, dL_dF, grad_rec, acc);
+            hipLaunchKernelGGL((blend_features_backward_kernel<FEAT_CB, decltype(GEOM)::value>), dim3(tiles), dim3(256), 0, s, in.vp,
+                               in.rec, in.ids, in.ranges, in.final_T, in.n_contrib, features, C, c0, vec, dL_dF, grad_rec, acc);
         });
         hipLaunchKernelGGL((features_finish_kernel<FEAT_CB>), dim3(finish_blocks), dim3(256), 0, s, P, C, c0, acc, dL_dfeatures);
     }
@@ -2251,32 +2158,28 @@ hipError_t launch_blend_features_backward(const ViewParams& vp, int P, const cha
 size_t features_scratch_bytes(int P) { return sizeof(double) * FEAT_CB * (size_t)(P > 0 ? P : 1); }
 
 // msgs_distortion_forward / _backward (SPEC M13): one launch each, the four-waves-per-tile shape whatever the tile count
-hipError_t launch_blend_distortion_forward(const ViewParams& vp, const char* geom, const uint32_t* ids, const uint2* ranges,
-                                           const float* final_T, const uint32_t* n_contrib, float* out_distortion,
-                                           float* out_moment, hipStream_t s) {
-    const int tiles = vp.gx * vp.gy;
+hipError_t launch_blend_distortion_forward(const ReplayInputs& in, float* out_distortion, float* out_moment, hipStream_t s) {
+    const int tiles = in.vp.gx * in.vp.gy;
     if (tiles <= 0) return hipSuccess;
-    hipLaunchKernelGGL(blend_distortion_forward_kernel, dim3(tiles), dim3(256), 0, s, vp, reinterpret_cast<const GaussRec*>(geom),
-                       ids, ranges, final_T, n_contrib, out_distortion, out_moment);
+    hipLaunchKernelGGL(blend_distortion_forward_kernel, dim3(tiles), dim3(256), 0, s, in.vp, in.rec, in.ids, in.ranges, in.final_T,
+                       in.n_contrib, out_distortion, out_moment);
     return hipGetLastError();
 }
-hipError_t launch_blend_distortion_backward(const ViewParams& vp, const char* geom, const uint32_t* ids, const uint2* ranges,
-                                            const float* final_T, const uint32_t* n_contrib, const float* moment,
-                                            const float* dL_ddist, grad_acc_t* grad_rec, hipStream_t s) {
-    const int tiles = vp.gx * vp.gy;
+hipError_t launch_blend_distortion_backward(const ReplayInputs& in, const float* moment, const float* dL_ddist,
+                                            grad_acc_t* grad_rec, hipStream_t s) {
+    const int tiles = in.vp.gx * in.vp.gy;
     if (tiles <= 0) return hipSuccess;
-    hipLaunchKernelGGL(blend_distortion_backward_kernel, dim3(tiles), dim3(256), 0, s, vp, reinterpret_cast<const GaussRec*>(geom),
-                       ids, ranges, final_T, n_contrib, moment, dL_ddist, grad_rec);
+    hipLaunchKernelGGL(blend_distortion_backward_kernel, dim3(tiles), dim3(256), 0, s, in.vp, in.rec, in.ids, in.ranges, in.final_T,
+                       in.n_contrib, moment, dL_ddist, grad_rec);
     return hipGetLastError();
 }
 
 // msgs_median_depth_forward / _backward (SPEC M15): one launch each, one workgroup per tile
-hipError_t launch_blend_median_depth_forward(const ViewParams& vp, const char* geom, const uint32_t* ids, const uint2* ranges,
-                                             const uint32_t* n_contrib, float* out_depth, int32_t* out_id, hipStream_t s) {
-    const int tiles = vp.gx * vp.gy;
+hipError_t launch_blend_median_depth_forward(const ReplayInputs& in, float* out_depth, int32_t* out_id, hipStream_t s) {
+    const int tiles = in.vp.gx * in.vp.gy;
     if (tiles <= 0) return hipSuccess;
-    hipLaunchKernelGGL(blend_median_depth_forward_kernel, dim3(tiles), dim3(256), 0, s, vp, reinterpret_cast<const GaussRec*>(geom),
-                       ids, ranges, n_contrib, out_depth, out_id);
+    hipLaunchKernelGGL(blend_median_depth_forward_kernel, dim3(tiles), dim3(256), 0, s, in.vp, in.rec, in.ids, in.ranges,
+                       in.n_contrib, out_depth, out_id);
     return hipGetLastError();
 }
 hipError_t launch_median_depth_backward(const ViewParams& vp, int P, const int32_t* median_id, const float* dL_dmedian,

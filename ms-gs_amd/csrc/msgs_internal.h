@@ -871,35 +871,35 @@ hipError_t launch_blend_backward(const ViewParams& vp, const char* geom, const u
                                  grad_acc_t* grad_rec, hipStream_t s, const uint32_t* tile_order = nullptr,
                                  const float* dL_ddepth = nullptr,    // non-null: the depth variants (record slot 9 = dL/dz)
                                  const float* dL_dalpha = nullptr);   // non-null: the alpha variants (S starts at bg.dL/dC - dL/dA)
+// What every opt-in replay of the tile lists reads of a forward's state: the view, the Gaussian records of the geometry buffer,
+// the tile lists of the binning buffer, and the per-pixel final transmittance and blended-entry count of the image buffer.
+struct ReplayInputs {
+    ViewParams vp;
+    const GaussRec* rec;
+    const uint32_t* ids;
+    const uint2* ranges;
+    const float* final_T;
+    const uint32_t* n_contrib;
+};
 // msgs_absgrad (SPEC M10): out [P, 3] float32 = {ln2 W sum_p |q u|, ln2 H sum_p |q w|, 0}; acc: [P, 2] doubles, cleared inside
-hipError_t launch_blend_absgrad(const ViewParams& vp, int P, const char* geom, const uint32_t* ids, const uint2* ranges,
-                                const float* final_T, const uint32_t* n_contrib, const float* dL_dcolor, const float* dL_ddepth,
+hipError_t launch_blend_absgrad(const ReplayInputs& in, int P, const float* dL_dcolor, const float* dL_ddepth,
                                 const float* dL_dalpha, double* acc, float* out, hipStream_t s);
 // msgs_contrib_* (SPEC M11): one accumulator row per Gaussian {double weight_sum, uint64 pixel_count, uint32 bits of weight_max,
 // pad}; the replay adds a view to it (pixel_weights [H,W] or NULL), the finish converts it to three [P] arrays
 constexpr size_t CONTRIB_ACC_BYTES = 24;
-hipError_t launch_blend_contrib(const ViewParams& vp, const char* geom, const uint32_t* ids, const uint2* ranges,
-                                const float* final_T, const uint32_t* n_contrib, const float* pixel_weights, void* acc,
-                                hipStream_t s);
+hipError_t launch_blend_contrib(const ReplayInputs& in, const float* pixel_weights, void* acc, hipStream_t s);
 hipError_t launch_contrib_finish(int P, const void* acc, float* weight_sum, float* weight_max, int64_t* pixel_count, hipStream_t s);
 // msgs_features_* (SPEC M12): features [P,C] splatted with the blend weights into out [C,H,W]; the backward adds the six
 // geometry sums of q_f into grad_rec (NULL = none) and writes dL_dfeatures [P,C] through acc (features_scratch_bytes(P))
 size_t features_scratch_bytes(int P);
-hipError_t launch_blend_features_forward(const ViewParams& vp, const char* geom, const uint32_t* ids, const uint2* ranges,
-                                         const float* final_T, const uint32_t* n_contrib, const float* features, int C,
-                                         float* out, hipStream_t s);
-hipError_t launch_blend_features_backward(const ViewParams& vp, int P, const char* geom, const uint32_t* ids, const uint2* ranges,
-                                          const float* final_T, const uint32_t* n_contrib, const float* features, int C,
-                                          const float* dL_dF, grad_acc_t* grad_rec, double* acc, float* dL_dfeatures,
-                                          hipStream_t s);
+hipError_t launch_blend_features_forward(const ReplayInputs& in, const float* features, int C, float* out, hipStream_t s);
+hipError_t launch_blend_features_backward(const ReplayInputs& in, int P, const float* features, int C, const float* dL_dF,
+                                          grad_acc_t* grad_rec, double* acc, float* dL_dfeatures, hipStream_t s);
 // msgs_distortion_* (SPEC M13): the depth-distortion map [H,W] and its moment map; the backward adds the six geometry sums of q
 // and the dL/dz sum (slot 9) into grad_rec
-hipError_t launch_blend_distortion_forward(const ViewParams& vp, const char* geom, const uint32_t* ids, const uint2* ranges,
-                                           const float* final_T, const uint32_t* n_contrib, float* out_distortion,
-                                           float* out_moment, hipStream_t s);
-hipError_t launch_blend_distortion_backward(const ViewParams& vp, const char* geom, const uint32_t* ids, const uint2* ranges,
-                                            const float* final_T, const uint32_t* n_contrib, const float* moment,
-                                            const float* dL_ddist, grad_acc_t* grad_rec, hipStream_t s);
+hipError_t launch_blend_distortion_forward(const ReplayInputs& in, float* out_distortion, float* out_moment, hipStream_t s);
+hipError_t launch_blend_distortion_backward(const ReplayInputs& in, const float* moment, const float* dL_ddist,
+                                            grad_acc_t* grad_rec, hipStream_t s);
 // antialias.hip — msgs_screen_compensation_* (SPEC M14): o_eff = o rho in front of K1, and its backward.  dL_dV NULL: no camera
 // sums and `rows` is not touched; otherwise rows >= screen_compensation_rows_bytes(P), 8-byte aligned
 size_t screen_compensation_rows_bytes(int P);
@@ -929,8 +929,7 @@ hipError_t launch_depth_normal_backward(int W, int H, float tanfovx, float tanfo
                                         bool world, const float* dL_dnormal, float* dL_ddepth, hipStream_t s);
 // msgs_median_depth_* (SPEC M15): the median-depth map [H,W] and the id map of its Gaussians (front-to-back replay with early
 // exit); the backward adds dL/dmedian_depth of every pixel to slot 9 (dL/dz) of its Gaussian's record
-hipError_t launch_blend_median_depth_forward(const ViewParams& vp, const char* geom, const uint32_t* ids, const uint2* ranges,
-                                             const uint32_t* n_contrib, float* out_depth, int32_t* out_id, hipStream_t s);
+hipError_t launch_blend_median_depth_forward(const ReplayInputs& in, float* out_depth, int32_t* out_id, hipStream_t s);
 hipError_t launch_median_depth_backward(const ViewParams& vp, int P, const int32_t* median_id, const float* dL_dmedian,
                                         grad_acc_t* grad_rec, hipStream_t s);
 // heaviest-first launch order of the one-wave-per-tile backward from the forward's per-tile traversal lengths

@@ -194,10 +194,18 @@ def test_map_against_per_pixel_backwards(kind):
 # ---------------------------------------------------------------------------------------------------------------------------
 # 4. invariants
 # ---------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("kind", ["sparse", "opaque", "F"])
+@pytest.mark.parametrize("kind", ["sparse", "opaque", "F", "deep"])
 def test_map_is_non_negative_and_zero_without_a_pair(kind):
+    """... and the backward on the same scenes ("deep": every tile list spans several staged batches, partial tiles in x and y;
+    "sparse": whole tiles empty) repeats bit for bit — a batch read before it is staged, or staged before it is consumed,
+    does not"""
     sc, cam = _scene_b(kind)[:2]
-    out, g = _run(sc, cam, Gx=_seed(cam.image_height, cam.image_width))
+    Gx = _seed(cam.image_height, cam.image_width)
+    out, g = _run(sc, cam, Gx=Gx)
+    again, g2 = _run(sc, cam, Gx=Gx)
+    assert torch.equal(out["distortion"].detach(), again["distortion"].detach())
+    _equal_grads(g, g2, kind)
+    assert g["xyz"].abs().max() > 0 or kind == "sparse"
     D = out["distortion"].detach()
     assert (D.max() > 0 or kind == "sparse") and D.min() >= -1e-6 * D.max()
     image = dgr._resolve(out["render"].grad_fn.state)[2]

@@ -235,10 +235,11 @@ def test_map_against_per_pixel_backwards(kind):
 # ---------------------------------------------------------------------------------------------------------------------------
 # 3. the colour route
 # ---------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("kind,C", [("A", 5), ("C", 5), ("S", 5), ("E", 5), ("A", 19)])
+@pytest.mark.parametrize("kind,C", [("A", 5), ("C", 5), ("S", 5), ("E", 5), ("A", 19), ("deep", 5)])
 @pytest.mark.parametrize("route", list(ROUTES))
 def test_gradients_equal_the_colour_route(kind, C, route):
-    sc, cam, st, smod, pipe, _ = _scene(kind)
+    # "deep" (test_absgrad_gpu._scene_b): every tile list spans several staged batches, partial tiles in x and y
+    sc, cam, st, smod, pipe, _ = _scene_b(kind)[:2] + ({}, 1.0, PIPE, {}) if kind == "deep" else _scene(kind)
     st = st or PLAIN
     h, w = cam.image_height, cam.image_width
     feats, G = _features(sc.P, C), _seed_map(C, h, w)
