@@ -105,11 +105,13 @@ def depth_key_f32(means3D, viewmatrix):
 
 def preprocess(means3D, opacities, view, *, scales=None, rotations=None, cov3D_precomp=None,
                shs=None, colors_precomp=None, max_pixel_sizes=None, min_pixel_sizes=None,
-               base_mask=None):
+               base_mask=None, dtype=torch.float64):
     """Per-Gaussian stage.  `view` is a dict with image_width/height, tanfovx/y, viewmatrix [4,4],
     projmatrix [4,4], campos [3], sh_degree, scale_modifier, filter_small, filter_large, fade_size.
-    Returns a dict of per-Gaussian tensors (float64; differentiable where meaningful)."""
-    dt = torch.float64
+    Returns a dict of per-Gaussian tensors (float64; differentiable where meaningful).  `dtype`:
+    torch.float32 evaluates the same expressions in float32 (tests/replay_truth.py: the reference's
+    own float32 distance from its float64 result)."""
+    dt = dtype
     P = means3D.shape[0]
     W, H = int(view["image_width"]), int(view["image_height"])
     V = view["viewmatrix"].to(dt)

@@ -4,9 +4,9 @@ gradients on two scenes, independent of the op:
 
     Dist_p = 2 sum_{j<i} w_ip w_jp (z_i - z_j),    w_ip = alpha_ip T_ip,    i = 1..n in tile-list order (front to back)
 
-The per-pixel weights come from oracle/torch_oracle.preprocess with the blend loop of torch_oracle.rasterize restated (the same
-alpha expression, validity, termination and borderline flags, and a zero means2D leaf added to the pixel centres): rasterize
-returns sums over the weights, not the weights.  tests/test_distortion_cpu.py pins the restated loop to rasterize (its sum w,
+The per-pixel weights come from oracle/torch_oracle.preprocess with the blend loop of torch_oracle.rasterize restated in
+tests/replay_truth.py (the same alpha expression, validity, termination and borderline flags, and a zero means2D leaf added to
+the pixel centres): rasterize returns sums over the weights, not the weights.  tests/test_distortion_cpu.py pins the restated loop to rasterize (its sum w,
 sum w z, counted pairs and borderline mask against 1 - final_T, the depth map, n_blended and the oracle's mask) and this file to
 compute().  All gradients are autograd's of sum G * Dist; G is seeded, uniform in (-0.5, 0.5), and zero on the oracle's borderline
 pixels, where the test leaves the map out of the comparison too.
@@ -28,10 +28,11 @@ for p in (ROOT, os.path.join(ROOT, "tests")):
 
 W, H, P, SCENE_SEED, G_SEED, FAR = 40, 24, 200, 1, 131, 2000.0
 PLAIN = dict(filter_small=False, filter_large=False, fade_size=1.0)
-MAX_BORDERLINE = 0.02          # of the image's pixels (the cap of make_absgrad_golden.py)
+import replay_truth as rt                        # noqa: E402  (tests/ is on the path now)
+from replay_truth import MAX_BORDERLINE, TILE, distortion_of, pixel_weights      # noqa: E402,F401  (the loop and the definition)
+
 PATH = os.path.join(HERE, "distortion_truth.npz")
 SCENES = ("F", "far")
-TILE = 16
 
 
 def scene(kind):
@@ -55,100 +56,18 @@ def seed_map():
     return torch.rand(H, W, generator=torch.Generator().manual_seed(G_SEED)) - 0.5
 
 
-def pixel_weights(pre, means2D, tx, ty):
-    """torch_oracle.rasterize's blend loop of tile (tx, ty), restated: (sel [n] Gaussian ids in list order, wgt [n, npix] float64
-    = alpha T of the blended pairs and 0 elsewhere, blended [n, npix] bool, borderline [npix] bool, (x0, x1, y0, y1)); None for a
-    tile with an empty list"""
-    dt = torch.float64
-    px, py = pre["px"] + means2D[:, 0], pre["py"] + means2D[:, 1]
-    vis = pre["visible"]
-    rminx, rminy, rmaxx, rmaxy = pre["rect"]
-    order_all = torch.argsort(pre["depth32"], stable=True)
-    vs = order_all[vis[order_all]]
-    sel = vs[(rminx[vs] <= tx) & (tx < rmaxx[vs]) & (rminy[vs] <= ty) & (ty < rmaxy[vs])]
-    x0, y0 = tx * TILE, ty * TILE
-    x1, y1 = min(x0 + TILE, W), min(y0 + TILE, H)
-    if sel.numel() == 0:
-        return None
-    ys, xs = torch.meshgrid(torch.arange(y0, y1, dtype=dt), torch.arange(x0, x1, dtype=dt), indexing="ij")
-    npix = ys.numel()
-    xs, ys = xs.reshape(-1), ys.reshape(-1)
-    dx = px[sel][:, None] - xs[None, :]
-    dy = py[sel][:, None] - ys[None, :]
-    con = pre["conic"][sel]
-    power = -0.5 * (con[:, 0:1] * dx * dx + con[:, 2:3] * dy * dy) - con[:, 1:2] * dx * dy
-    Gs = torch.exp(torch.clamp(power, max=0.0))
-    a_raw = pre["opacity"][sel][:, None] * Gs
-    alpha = a_raw + (torch.clamp(a_raw, max=0.99) - a_raw).detach()
-    valid = (power <= 0) & (alpha.detach() >= 1.0 / 255.0)
-    near = (power.detach() <= 0) & ((alpha.detach() - 1.0 / 255.0).abs() < 2e-6)
-    alpha_v = torch.where(valid, alpha, torch.zeros_like(alpha))
-    one_m = 1.0 - alpha_v
-    T_after = torch.cumprod(one_m, dim=0)
-    T_before = torch.cat([torch.ones(1, npix, dtype=dt), T_after[:-1]], dim=0)
-    fail = valid & (T_after.detach() < 1e-4)
-    near_t = valid & ((T_after.detach() - 1e-4).abs() < 1e-9)
-    any_fail = fail.any(dim=0)
-    first_fail = torch.where(any_fail, fail.to(torch.int64).argmax(dim=0), torch.full((npix,), sel.numel(), dtype=torch.int64))
-    idx = torch.arange(sel.numel())[:, None]
-    blended = valid & (idx < first_fail[None, :])
-    bl = ((near | near_t) & (idx <= first_fail[None, :])).any(dim=0)
-    wgt = torch.where(blended, alpha * T_before, torch.zeros_like(alpha))
-    return sel, wgt, blended, bl, (x0, x1, y0, y1)
-
-
-def distortion_of(wgt, z):
-    """the definition: 2 sum_{j<i} w_i w_j (z_i - z_j) per pixel; wgt [n, npix], z [n] in list order.  With prefix sums
-    A_i = sum_{j<i} w_j and Z_i = sum_{j<i} w_j z_j it is 2 sum_i w_i (z_i A_i - Z_i)."""
-    wz = wgt * z[:, None]
-    A = torch.cumsum(wgt, 0) - wgt
-    Z = torch.cumsum(wz, 0) - wz
-    return 2.0 * (wgt * (z[:, None] * A - Z)).sum(0)
-
-
 def restated(kind, leaves=None, view_edit=None):
-    """the restated loop over the whole image: dict of dist [H,W] (differentiable), wsum, wzsum [H,W], count [H,W] int64,
-    borderline [H,W] bool, radii [P], the leaves (means3D, opacities, scales, rotations, means2D), per-tile lists.
-    view_edit(view): edits the oracle's view dict first (float64 camera leaves for the camera gradient)"""
-    from oracle import torch_oracle as to
+    """the restated loop over the whole image (tests/replay_truth.render): dict of dist [H,W] (differentiable), wsum, wzsum [H,W],
+    count [H,W] int64, borderline [H,W] bool, radii [P], the leaves (means3D, opacities, scales, rotations, means2D), per-tile
+    lists.  view_edit(view): edits the oracle's view dict first (float64 camera leaves for the camera gradient)"""
     sc, cam = scene(kind)
-    dt = torch.float64
-    leaf = lambda t: t.detach().to(dt).clone().requires_grad_(True)
-    means3D, opac, scales, rots = leaves or (leaf(sc.means3D), leaf(sc.opacities), leaf(sc.scales), leaf(sc.rotations))
-    view = to.view_dict(cam, sh_degree=sc.sh_degree, **PLAIN)
-    if view_edit is not None:
-        view_edit(view)
-    pre = to.preprocess(means3D, opac, view, scales=scales, rotations=rots, shs=sc.shs, max_pixel_sizes=sc.max_pixel_sizes,
-                        min_pixel_sizes=sc.min_pixel_sizes, base_mask=sc.base_mask)
-    means2D = torch.zeros(P, 2, dtype=dt, requires_grad=True)
-    gx, gy = (W + TILE - 1) // TILE, (H + TILE - 1) // TILE
-    dist = torch.zeros(H, W, dtype=dt)
-    wsum, wzsum = torch.zeros(H, W, dtype=dt), torch.zeros(H, W, dtype=dt)
-    count = torch.zeros(H, W, dtype=torch.int64)
-    borderline = torch.zeros(H, W, dtype=torch.bool)
-    tiles = []
-    rows = []
-    for ty in range(gy):
-        parts = []
-        for tx in range(gx):
-            r = pixel_weights(pre, means2D, tx, ty)
-            x0, y0 = tx * TILE, ty * TILE
-            x1, y1 = min(x0 + TILE, W), min(y0 + TILE, H)
-            if r is None:
-                parts.append(torch.zeros(y1 - y0, x1 - x0, dtype=dt))
-                continue
-            sel, wgt, blended, bl, _ = r
-            z = pre["depth"][sel]
-            parts.append(distortion_of(wgt, z).view(y1 - y0, x1 - x0))
-            wsum[y0:y1, x0:x1] = wgt.detach().sum(0).view(y1 - y0, x1 - x0)
-            wzsum[y0:y1, x0:x1] = (wgt.detach() * z.detach()[:, None]).sum(0).view(y1 - y0, x1 - x0)
-            count[y0:y1, x0:x1] = blended.sum(0).view(y1 - y0, x1 - x0)
-            borderline[y0:y1, x0:x1] = bl.view(y1 - y0, x1 - x0)
-            tiles.append((x0, x1, y0, y1, wgt.detach(), z.detach()))
-        rows.append(torch.cat(parts, dim=1))
-    dist = torch.cat(rows, dim=0)
-    return dict(dist=dist, wsum=wsum, wzsum=wzsum, count=count, borderline=borderline, radii=pre["radii"],
-                leaves=(means3D, opac, scales, rots, means2D), tiles=tiles, view=view, scene=sc)
+    given = dict(zip(("means3D", "opacities", "scales", "rotations"), leaves)) if leaves else None
+    r = rt.render(sc, cam, PLAIN, leaves=given, view_edit=view_edit)
+    L = r.leaves
+    tiles = [(x0, x1, y0, y1, wgt, r.pre["depth"][sel].detach()) for (x0, x1, y0, y1, sel, wgt, _) in r.tiles]
+    return dict(dist=r.distortion, wsum=r.alpha.detach(), wzsum=r.depth.detach(), count=r.n_blended, borderline=r.borderline,
+                radii=r.radii, leaves=(L["means3D"], L["opacities"], L["scales"], L["rotations"], L["means2D"]), tiles=tiles,
+                view=r.view, scene=sc)
 
 
 def compute_scene(kind):

@@ -10,7 +10,10 @@ Two truths, both independent of the kernel under test:
 Both are compared with parity_utils.rel_err against BWD_RTOL, the project's gradient tolerance; the measured maxima are printed
 (pytest -s) and recorded in profiles/absgrad_notes.md.  Then: a loss on one pixel (absgrad == |grad|), the invariants, the
 untouched default path, the entries (two views in flight, depth slabs, occlusion cut-off), the densification statistic and
-the guards."""
+the guards.
+The float64 truth here lives on one 3 x 2-tile picture; for the breadth (lists of several 256-entry batches, early termination,
+filters with a fade, rigid poses, focal lengths, the scaling modifier, small models) see the seeded sweep of all opt-in outputs
+against the same kind of truth: tests/test_replay_sweep_gpu.py, tests/replay_cases.py, tests/replay_truth.py."""
 import contextlib
 import ctypes as C
 import os

@@ -10,7 +10,10 @@ Two truths, both independent of the kernel under test:
      is then w_ip of that pixel.  One whole-image backward with dL/dC = (m, 0, 0) must reproduce the weighted weight_sum.
 Counts are compared exactly, sums and maxima with parity_utils.rel_err against BWD_RTOL, the project's gradient tolerance; the
 measured maxima are printed (pytest -s) and recorded in profiles/contrib_notes.md.  Then: the invariants, accumulation over views,
-equal bits on every run and behind every forward route, the untouched default path, the host layer and the guards."""
+equal bits on every run and behind every forward route, the untouched default path, the host layer and the guards.
+The float64 truth here lives on one 3 x 2-tile picture; for the breadth (lists of several 256-entry batches, early termination,
+filters with a fade, rigid poses, focal lengths, the scaling modifier, small models) see the seeded sweep of all opt-in outputs
+against the same kind of truth: tests/test_replay_sweep_gpu.py, tests/replay_cases.py, tests/replay_truth.py."""
 import ctypes as C
 import os
 import types

@@ -12,7 +12,10 @@ References, none of them the kernels under test:
 Tolerances are the project's own for quantities of the same kind (BWD_RTOL, LIN_TOL of tests/test_depth_grad_gpu.py, CEIL of
 tests/test_camera_grad_gpu.py); the far map is held to 1e-5 of its maximum — a tenth of what the unshifted float32 formulas
 reach and thirty times what the shifted ones reach with exact weights (tests/test_distortion_cpu.py).  The measured maxima are
-printed (pytest -s) and recorded in profiles/distortion_notes.md."""
+printed (pytest -s) and recorded in profiles/distortion_notes.md.
+The float64 truth here lives on one 3 x 2-tile picture; for the breadth (lists of several 256-entry batches, early termination,
+filters with a fade, rigid poses, focal lengths, the scaling modifier, small models) see the seeded sweep of all opt-in outputs
+against the same kind of truth: tests/test_replay_sweep_gpu.py, tests/replay_cases.py, tests/replay_truth.py."""
 import copy
 import importlib.util
 import os

@@ -10,7 +10,10 @@ Three references, none of them the kernels under test:
   3  the colour route: the same model rendered with override_color triples over background 0, one backward per triple.
 Tolerances are the project's own for quantities of the same kind (BWD_RTOL, TOL and LIN_TOL of tests/test_depth_grad_gpu.py); the
 measured maxima are printed (pytest -s) and recorded in profiles/features_notes.md.  Then: channel blocks, never-read rows,
-linearity, the forward routes, the untouched default path, the other modes and the guards."""
+linearity, the forward routes, the untouched default path, the other modes and the guards.
+The float64 truth here lives on one 3 x 2-tile picture; for the breadth (lists of several 256-entry batches, early termination,
+filters with a fade, rigid poses, focal lengths, the scaling modifier, small models) see the seeded sweep of all opt-in outputs
+against the same kind of truth: tests/test_replay_sweep_gpu.py, tests/replay_cases.py, tests/replay_truth.py."""
 import contextlib
 import copy
 import os

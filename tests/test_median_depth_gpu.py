@@ -2,7 +2,7 @@
 
 Two independent truths:
   1  float64: tests/golden/median_depth_truth.npz (oracle/torch_oracle.preprocess + the blend loop restated by
-     make_distortion_golden.pixel_weights + the definition, autograd of sum G * median_depth for means3D and a viewmatrix leaf) on
+     tests/replay_truth.pixel_weights + the definition, autograd of sum G * median_depth for means3D and a viewmatrix leaf) on
      scene F (every pixel crosses 1/2) and "thin" (empty, crossing and never-crossing pixels).  G is zero on the fixture's mask
      (the oracle's borderline pixels and pixels with a blended T_{i+1} within 1e-4 of 0.5), which is also left out of the map
      comparisons; the mask covers <= 2 % of the image (asserted).
@@ -12,7 +12,10 @@ Two independent truths:
 Tolerances are the project's own for quantities of the same kind (FWD_ATOL, BWD_RTOL of tests/parity_utils.py, LIN_TOL of
 tests/test_depth_grad_gpu.py, CEIL of tests/test_camera_grad_gpu.py); ids are compared exactly.  The measured maxima are printed
 (pytest -s) and recorded in profiles/median_depth_notes.md.  The forward-route section runs the scenes of the route tests of
-tests/test_distortion_gpu.py (the smallest that reach a redo, forced slabs and closed occlusion blocks), forward only."""
+tests/test_distortion_gpu.py (the smallest that reach a redo, forced slabs and closed occlusion blocks), forward only.
+The float64 truth here lives on one 3 x 2-tile picture; for the breadth (lists of several 256-entry batches, early termination,
+filters with a fade, rigid poses, focal lengths, the scaling modifier, small models) see the seeded sweep of all opt-in outputs
+against the same kind of truth: tests/test_replay_sweep_gpu.py, tests/replay_cases.py, tests/replay_truth.py."""
 import copy
 import importlib.util
 import os
