@@ -3,13 +3,37 @@
 // with the reference's SSIM (/root/reference/utils/loss_utils.py:23-63: 11x11 Gaussian window, sigma 1.5, zero
 // padding, per-channel, C1 = 0.01^2, C2 = 0.03^2, mean over all elements) and its gradient w.r.t. img, produced in the
 // [C,H,W] layout the blend backward consumes.  The reference runs 5 grouped conv2d + ~15 elementwise kernels forward
-// and as many again backward; here it is two launches:
-//   ssim_stats_kernel   per 32x32 tile and channel: the five windowed moments (separable 11-tap passes through LDS),
-//                       the SSIM map, |img-gt|, block partial sums, and the three per-pixel derivative maps
-//                       A = dS/dmu1 (total), B = dS/dsigma1^2, Cm = dS/dsigma12
-//   ssim_grad_kernel    dL/dimg(q) = gs * [conv(A) + 2 img conv(B) + gt conv(Cm)](q) + gl * sign(img - gt)(q);
-//                       its first block also folds the partial sums in a fixed order (deterministic loss value)
+// and as many again backward; here it is two launches forward and one backward:
+//   ssim_stats_kernel    forward, per 32x32 tile and channel: five windowed moments (separable 11-tap passes through
+//                        LDS), the SSIM map, |img-gt|, block partial sums, and the three per-pixel derivative maps P, B, E
+//   loss_finalize_kernel forward: folds the partial sums in a fixed order (deterministic loss value)
+//   ssim_grad_kernel     backward: dL/dimg from the windowed sums of three maps built from P, B, E and the images' halo
 // Algorithmic HBM bytes per pixel-channel: stats 8 read + 12 written, grad 20 read + 4 written.
+//
+// Moments free of cancellation.  A render close to its target, a flat background, a saturated region: the windowed
+// variances are far below C2 = 9e-4 there, and sigma^2 = E[x^2] - mu^2 from float32 sums of x and x^2 carries their
+// 1e-7 rounding straight into sigma1^2 + sigma2^2 + C2; the gradient 2 x(q) conv(B) - conv(2 B mu1) is then the
+// difference of two terms of ~1/C2 that agree to a few per cent.  So nothing here is taken about 0:
+//   * the moments are those of y and d = x - y, not of x and y:  mu1 = mu2 + mu_d,  sigma12 = sigma2^2 + sigma_dy,
+//     sigma1^2 = sigma2^2 + 2 sigma_dy + sigma_d^2, hence
+//         a1 = 2 mu1 mu2 + C1,                 b1 = mu1^2 + mu2^2 + C1           = a1 + mu_d^2
+//         a2 = 2 (sigma2^2 + sigma_dy) + C2,   b2 = sigma1^2 + sigma2^2 + C2     = a2 + sigma_d^2
+//     and S = (a1 / b1)(a2 / b2) is exactly 1 on identical images;
+//   * each tile and channel takes pivots q = y and pd = x - y at the tile's centre pixel (clamped into the image) and
+//     convolves y' = y - q, d' = d - pd, y'^2, d'^2, y'd'; pixels outside the image are staged as -q and -pd, so the
+//     padding is still a true 0.  With S_w the total weight of the reference's 11x11 float32 window and
+//     delta = 1 - S_w, both summed in double on the host (delta = 6.9e-8 is what gives a constant image c its
+//     variance c^2 S_w delta: 4.4e-6 at c = 8, against C2 = 9e-4):
+//         mu2 = fma(q, S_w, M_y'),       sigma2^2 = (E_yy' - M_y'^2) + (2 q delta M_y' + q^2 S_w delta)
+//         sigma_dy = (E_yd' - M_y' M_d') + (delta (q M_d' + pd M_y') + q pd S_w delta),     mu_d, sigma_d^2 alike;
+//   * the gradient is  sum_p w(p - q) [dS/dmu1 + 2 B (d(q) - mu_d(p)) + E (y(q) - mu2(p))]  with
+//         B = dS/dsigma1^2 = -S / b2,     E = dS/dsigma12 + 2 B = 2 (a1 / b1) sigma_d^2 / b2^2   (0 when converged),
+//         dS/dmu1 = -2 (a2 / b2) mu_d (mu2 (mu1 + mu2) + C1) / b1^2,
+//     and both differences are formed from small quantities about the gradient tile's own pivots ty and td:
+//         d(q) - mu_d(p) = (d(q) - td) - (mu_d(p) - d(p)) - (d(p) - td),       y(q) - mu2(p) alike.
+//     The stats kernel leaves P = dS/dmu1 - 2 B (mu_d - d) - E (mu2 - y), taken from M' and never from mu itself;
+//     the gradient kernel convolves G = P - 2 B (d - td) - E (y - ty), B and E:
+//         dL/dimg(q) = gs * [conv(G) + 2 (d(q) - td) conv(B) + (y(q) - ty) conv(E)](q) + gl * sign(img - gt)(q)
 #include "msgs_internal.h"
 
 #pragma clang fp contract(off)
@@ -23,7 +47,7 @@ constexpr int LIN_STRIDE = LE + 1;  // 43: odd row stride, conflict-free column 
 constexpr int LH_STRIDE = LT + 1;   // 33
 constexpr int LOSS_THREADS = 256;
 
-struct SsimWindow { float w[11]; };
+struct SsimWindow { float w[11]; float S, D, SD; };   // taps; S_w, delta = 1 - S_w and S_w delta of the 2-D window
 
 void ssim_window_host(float w[11]) {
     // loss_utils.py:23-25: exp(-(x - 5)^2 / (2 sigma^2)) evaluated in double, stored as float32, divided by their
@@ -34,6 +58,19 @@ void ssim_window_host(float w[11]) {
         sum += (double)w[i];
     }
     for (int i = 0; i < 11; ++i) w[i] /= (float)sum;
+}
+
+static SsimWindow ssim_window() {
+    // loss_utils.py:28-29: the reference's 2-D window holds the float32 products of the taps; they sum to 1 - 6.9e-8
+    SsimWindow win;
+    ssim_window_host(win.w);
+    double sum = 0.0;
+    for (int i = 0; i < 11; ++i)
+        for (int j = 0; j < 11; ++j) sum += (double)(win.w[i] * win.w[j]);
+    win.S = (float)sum;
+    win.D = (float)(1.0 - sum);
+    win.SD = (float)(sum * (1.0 - sum));
+    return win;
 }
 
 __device__ __forceinline__ float block_sum_256(float v, float* red) {
@@ -100,7 +137,7 @@ __global__ __launch_bounds__(LOSS_THREADS) void ssim_stats_kernel(const float* _
                                                                    const float* __restrict__ gt, int H, int W,
                                                                    SsimWindow win, float* __restrict__ maps,
                                                                    float* __restrict__ partials, int write_maps) {
-    __shared__ float sx[LE * LIN_STRIDE], sy[LE * LIN_STRIDE];
+    __shared__ float sy[LE * LIN_STRIDE], sd[LE * LIN_STRIDE];      // y - q and (x - y) - pd
     __shared__ float hm[5 * LE * LH_STRIDE];
     __shared__ float red[4];
     const int ch = blockIdx.z;
@@ -108,23 +145,28 @@ __global__ __launch_bounds__(LOSS_THREADS) void ssim_stats_kernel(const float* _
     const size_t plane = (size_t)H * W;
     const float* X = img + ch * plane;
     const float* Y = gt + ch * plane;
+    const size_t oc = (size_t)min(y0 + LT / 2, H - 1) * W + min(x0 + LT / 2, W - 1);
+    const float q = Y[oc], pd = X[oc] - q;
     float l1 = 0.f;
     for (int i = threadIdx.x; i < LE * LE; i += LOSS_THREADS) {
         const int r = i / LE, c = i % LE;
         const int y = y0 + r - LR, x = x0 + c - LR;
-        float a = 0.f, b = 0.f;
+        float b = -q, d = -pd;
         if (x >= 0 && x < W && y >= 0 && y < H) {
-            a = X[(size_t)y * W + x];
+            const float a = X[(size_t)y * W + x];
             b = Y[(size_t)y * W + x];
-            if (r >= LR && r < LR + LT && c >= LR && c < LR + LT) l1 += fabsf(a - b);
+            d = a - b;
+            if (r >= LR && r < LR + LT && c >= LR && c < LR + LT) l1 += fabsf(d);
+            b -= q;
+            d -= pd;
         }
-        sx[r * LIN_STRIDE + c] = a;
         sy[r * LIN_STRIDE + c] = b;
+        sd[r * LIN_STRIDE + c] = d;
     }
     __syncthreads();
     horizontal_pass<5>(win, hm, [&](int r, int c, float v[5]) {
-        const float a = sx[r * LIN_STRIDE + c], b = sy[r * LIN_STRIDE + c];
-        v[0] = a; v[1] = b; v[2] = a * a; v[3] = b * b; v[4] = a * b;
+        const float b = sy[r * LIN_STRIDE + c], d = sd[r * LIN_STRIDE + c];
+        v[0] = b; v[1] = d; v[2] = b * b; v[3] = d * d; v[4] = b * d;
     });
     __syncthreads();
     const int c = threadIdx.x & 31, r0 = (threadIdx.x >> 5) * 4;
@@ -133,26 +175,33 @@ __global__ __launch_bounds__(LOSS_THREADS) void ssim_stats_kernel(const float* _
     constexpr float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;
     float ssim_sum = 0.f;
     const int x = x0 + c;
+    const float qd = q * win.D, pdd = pd * win.D;
+    const float qq = q * q * win.SD, pp = pd * pd * win.SD, qp = q * pd * win.SD;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const int y = y0 + r0 + j;
         if (x < W && y < H) {
-            const float m1 = mo[0][j], m2 = mo[1][j];
-            const float m1s = m1 * m1, m2s = m2 * m2, m12 = m1 * m2;
-            const float s1 = mo[2][j] - m1s, s2 = mo[3][j] - m2s, s12 = mo[4][j] - m12;
-            const float a1 = 2.f * m12 + C1, a2 = 2.f * s12 + C2;
-            const float b1 = m1s + m2s + C1, b2 = s1 + s2 + C2;
-            const float inv = 1.f / (b1 * b2);
-            const float S = (a1 * a2) * inv;
+            const float My = mo[0][j], Md = mo[1][j];
+            const float m2 = __fmaf_rn(q, win.S, My), md = __fmaf_rn(pd, win.S, Md), m1 = m2 + md;
+            const float s2 = (mo[2][j] - My * My) + (2.f * qd * My + qq);
+            const float sdd = (mo[3][j] - Md * Md) + (2.f * pdd * Md + pp);
+            const float sdy = (mo[4][j] - My * Md) + ((qd * Md + pdd * My) + qp);
+            const float a1 = 2.f * (m1 * m2) + C1, a2 = 2.f * (s2 + sdy) + C2;
+            const float b1 = a1 + md * md, b2 = a2 + sdd;
+            const float r1 = a1 / b1, r2 = a2 / b2;
+            const float S = r1 * r2;
             ssim_sum += S;
             if (write_maps) {
-                const float dS_ds12 = 2.f * a1 * inv;
-                const float dS_ds1 = -S / b2;
-                const float dS_dm1 = 2.f * m2 * a2 * inv - 2.f * m1 * S / b1;
+                const float inv1 = 1.f / b1, inv2 = 1.f / b2;
+                const float B = -S * inv2;
+                const float E = 2.f * r1 * sdd * inv2 * inv2;
+                const float dS_dm1 = -(2.f * r2 * md * (m2 * (m1 + m2) + C1)) * inv1 * inv1;
+                const int ci = (r0 + j + LR) * LIN_STRIDE + c + LR;
+                const float Dd = (Md - sd[ci]) - pdd, Dy = (My - sy[ci]) - qd;      // mu_d - d and mu2 - y at this pixel
                 const size_t o = (size_t)y * W + x;
-                maps[(0 * gridDim.z + ch) * plane + o] = dS_dm1 - 2.f * m1 * dS_ds1 - m2 * dS_ds12;
-                maps[(1 * gridDim.z + ch) * plane + o] = dS_ds1;
-                maps[(2 * gridDim.z + ch) * plane + o] = dS_ds12;
+                maps[(0 * gridDim.z + ch) * plane + o] = dS_dm1 - 2.f * B * Dd - E * Dy;
+                maps[(1 * gridDim.z + ch) * plane + o] = B;
+                maps[(2 * gridDim.z + ch) * plane + o] = E;
             }
         }
     }
@@ -209,13 +258,24 @@ __global__ __launch_bounds__(LOSS_THREADS) void ssim_grad_kernel(const float* __
     const int ch = blockIdx.z;
     const int x0 = blockIdx.x * LT, y0 = blockIdx.y * LT;
     const size_t plane = (size_t)H * W;
+    const float* X = img + ch * plane;
+    const float* Y = gt + ch * plane;
+    const size_t oc = (size_t)min(y0 + LT / 2, H - 1) * W + min(x0 + LT / 2, W - 1);
+    const float ty = Y[oc], td = X[oc] - ty;
     for (int i = threadIdx.x; i < LE * LE; i += LOSS_THREADS) {
         const int r = i / LE, c = i % LE;
         const int y = y0 + r - LR, x = x0 + c - LR;
-        const bool in = x >= 0 && x < W && y >= 0 && y < H;
-        const size_t o = (size_t)y * W + x;
-#pragma unroll
-        for (int m = 0; m < 3; ++m) sm[(m * LE + r) * LIN_STRIDE + c] = in ? maps[(m * gridDim.z + ch) * plane + o] : 0.f;
+        float G = 0.f, B = 0.f, E = 0.f;
+        if (x >= 0 && x < W && y >= 0 && y < H) {
+            const size_t o = (size_t)y * W + x;
+            const float b = Y[o], d = X[o] - b;
+            B = maps[(1 * gridDim.z + ch) * plane + o];
+            E = maps[(2 * gridDim.z + ch) * plane + o];
+            G = (maps[(0 * gridDim.z + ch) * plane + o] - 2.f * B * (d - td)) - E * (b - ty);
+        }
+        sm[(0 * LE + r) * LIN_STRIDE + c] = G;
+        sm[(1 * LE + r) * LIN_STRIDE + c] = B;
+        sm[(2 * LE + r) * LIN_STRIDE + c] = E;
     }
     __syncthreads();
     horizontal_pass<3>(win, hm, [&](int r, int c, float v[3]) {
@@ -233,11 +293,10 @@ __global__ __launch_bounds__(LOSS_THREADS) void ssim_grad_kernel(const float* __
     for (int j = 0; j < 4; ++j) {
         const int y = y0 + r0 + j;
         if (x < W && y < H) {
-            const size_t o = ch * plane + (size_t)y * W + x;
-            const float a = img[o], b = gt[o];
-            const float d = a - b;
+            const size_t o = (size_t)y * W + x;
+            const float b = Y[o], d = X[o] - b;
             const float sgn = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
-            dL_dimg[o] = gs * (g[0][j] + 2.f * a * g[1][j] + b * g[2][j]) + gl * sgn;
+            dL_dimg[ch * plane + o] = gs * (g[0][j] + 2.f * (d - td) * g[1][j] + (b - ty) * g[2][j]) + gl * sgn;
         }
     }
 }
@@ -250,8 +309,7 @@ size_t loss_scratch_bytes(int C, int H, int W) {
 
 hipError_t launch_loss_forward(const float* img, const float* gt, int C, int H, int W, float lambda, float* out3,
                                char* scratch, int write_maps, hipStream_t s) {
-    SsimWindow win;
-    ssim_window_host(win.w);
+    const SsimWindow win = ssim_window();
     const size_t plane = (size_t)H * W;
     float* maps = (float*)scratch;
     float* partials = (float*)(scratch + align256(3 * C * plane * sizeof(float)));
@@ -265,8 +323,7 @@ hipError_t launch_loss_forward(const float* img, const float* gt, int C, int H, 
 
 hipError_t launch_loss_backward(const float* img, const float* gt, int C, int H, int W, float lambda,
                                 const float* upstream, const char* scratch, float* dL_dimg, hipStream_t s) {
-    SsimWindow win;
-    ssim_window_host(win.w);
+    const SsimWindow win = ssim_window();
     const dim3 grid((W + LT - 1) / LT, (H + LT - 1) / LT, C);
     hipLaunchKernelGGL(ssim_grad_kernel, grid, dim3(LOSS_THREADS), 0, s, img, gt, H, W, win, (const float*)scratch, lambda,
                        (float)(1.0 / ((double)C * (double)H * (double)W)), upstream, dL_dimg);

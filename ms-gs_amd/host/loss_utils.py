@@ -34,13 +34,13 @@ def _as_planes(t, what):
 
 class _L1SsimLoss(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, image, gt, lambda_dssim):
+    def forward(ctx, image, gt, lambda_dssim, keep_maps):
         x, planes, H, W = _as_planes(image, "image")
         y, p2, H2, W2 = _as_planes(gt, "gt")
         if (planes, H, W) != (p2, H2, W2):
             raise ValueError(f"image {tuple(image.shape)} and gt {tuple(gt.shape)} differ in shape")
         lib = _C.lib
-        need_grad = image.requires_grad
+        need_grad = bool(keep_maps)
         with torch.cuda.device(x.device):
             stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
             scratch = torch.empty(int(lib.msgs_loss_scratch_bytes(planes, H, W)), dtype=torch.uint8, device=x.device)
@@ -62,12 +62,19 @@ class _L1SsimLoss(torch.autograd.Function):
             stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
             _C.check(_C.lib.msgs_loss_backward(_ptr(x), _ptr(y), planes, H, W, lam, _ptr(up), _ptr(scratch),
                                                scratch.numel(), _ptr(grad), stream), "msgs_loss_backward")
-        return grad.view(shape).to(dtype), None, None
+        return grad.view(shape).to(dtype), None, None, None
+
+
+def _loss(image, gt, lambda_dssim):
+    """(loss, [loss, l1, ssim]).  The three derivative maps are written only when a backward can follow: grad mode is
+    always off inside Function.forward and image.requires_grad is True under torch.no_grad() as well, so the decision
+    is taken here, outside"""
+    return _L1SsimLoss.apply(image, gt, lambda_dssim, torch.is_grad_enabled() and image.requires_grad)
 
 
 def l1_ssim_loss(image, gt, lambda_dssim=0.2):
     """(1 - lambda_dssim) * l1_loss + lambda_dssim * (1 - ssim)  ->  (loss, Ll1).  train.py:209-211."""
-    loss, out3 = _L1SsimLoss.apply(image, gt, lambda_dssim)
+    loss, out3 = _loss(image, gt, lambda_dssim)
     return loss, out3[1]
 
 
@@ -75,11 +82,11 @@ def ssim(img1, img2, window_size=11, size_average=True):
     """loss_utils.py:32-63.  Only the configuration the reference uses (window 11, size_average) is implemented."""
     if window_size != 11 or not size_average:
         raise NotImplementedError("ssim: only window_size=11, size_average=True (the values every MS-GS caller uses)")
-    loss, _ = _L1SsimLoss.apply(img1, img2, 1.0)          # lambda = 1: loss = 1 - ssim
+    loss, _ = _loss(img1, img2, 1.0)                      # lambda = 1: loss = 1 - ssim
     return 1.0 - loss
 
 
 def l1_loss(network_output, gt):
     """loss_utils.py:17-18."""
-    loss, _ = _L1SsimLoss.apply(network_output, gt, 0.0)  # lambda = 0: loss = L1 mean
+    loss, _ = _loss(network_output, gt, 0.0)              # lambda = 0: loss = L1 mean
     return loss

@@ -1,6 +1,6 @@
 """The composed GPU training iteration (render_fused -> l1_ssim_loss -> backward -> statistics -> FusedAdam) against
-the same iteration composed the reference's way (render + torch loss formulation + torch.optim.Adam + masked-index
-statistics), and a short optimisation run as the train-step harness of SURVEY §8(d)."""
+the same iteration composed the reference's way (render + torch loss formulation, evaluated in float64 + torch.optim.Adam +
+masked-index statistics), and a short optimisation run as the train-step harness of SURVEY §8(d)."""
 import pytest
 import torch
 import torch.nn.functional as F
@@ -13,7 +13,7 @@ pytestmark = pytest.mark.gpu
 
 
 def _torch_loss(x, gt, lam):
-    w = torch.from_numpy(lo.window_2d()).to(x.device).expand(3, 1, 11, 11).contiguous()
+    w = torch.from_numpy(lo.window_2d()).to(x.device, x.dtype).expand(3, 1, 11, 11).contiguous()
     conv = lambda t: F.conv2d(t, w, padding=5, groups=3)
     m1, m2 = conv(x), conv(gt)
     s1, s2, s12 = conv(x * x) - m1 * m1, conv(gt * gt) - m2 * m2, conv(x * gt) - m1 * m2
@@ -24,7 +24,13 @@ def _torch_loss(x, gt, lam):
 def _reference_style_iteration(model, opt, cam, gt, bg, lvl, st):
     from gaussian_renderer import render
     pkg = render(cam, model, PIPE, bg, **st)
-    loss = _torch_loss(pkg["render"], gt, 0.2)
+    # the loss formula in float64.  On _scaling / _rotation the distance below is that of ONE Gaussian of this scene (index 1080,
+    # radius 39 px), whose gradient responds to the pixel gradient in steps, as float32 accumulation of cancelling terms does: it moves
+    # in steps of ~3e-5 of the largest entry and not at all in between (two pixel gradients 7e-7 apart give the same bits, 1000 x
+    # their difference fed alone moves it by 1.6e-7).  Fed the float64 oracle's pixel gradient, it lands 2.0e-5 / 4.1e-5 from
+    # where the float32 formulation puts it, as much as the tolerance; every other Gaussian agrees to 2.5e-6 either way
+    # (profiles/loss_notes.md).  The truth is the reference that does not add a step of its own.
+    loss = _torch_loss(pkg["render"].double(), gt.double(), 0.2)
     loss.backward()
     with torch.no_grad():
         vis, radii, ps = pkg["visibility_filter"], pkg["radii"], pkg["pixel_sizes"]
@@ -76,7 +82,7 @@ def test_first_iteration_matches_the_reference_composition():
         ma, mb = oa.state[p]["exp_avg"], ob.state[q]["exp_avg"]
         e = (ma - mb).abs().max().item() / mb.abs().max().item()
         print(f"[parity] train step exp_avg {n}: {e:.3e}")
-        assert e <= (5e-5 if n in ("_scaling", "_rotation") else 5e-6), n      # measured 4.5e-6 / 2.3e-6 / <= 4.1e-7
+        assert e <= (5e-5 if n in ("_scaling", "_rotation") else 5e-6), n      # measured 1.8e-5 / 2.7e-5 / <= 4.0e-7
         sure = mb.abs() > 1e-3 * mb.abs().max()
         assert sure.any()
         step_a, step_b = (p - before[n])[sure], (q - before[n])[sure]
