@@ -1011,6 +1011,72 @@ int msgs_bilagrid_tv_forward(int64_t N, int32_t GX, int32_t GY, int32_t GL, cons
 int msgs_bilagrid_tv_backward(int64_t N, int32_t GX, int32_t GY, int32_t GL, const float* grids, const float* upstream,
                               float* dL_dgrids, void* stream);
 
+/* ---- TSDF fusion of depth maps and mesh extraction (DESIGN.md SPEC M20, 4.22) -------------------------------------------------
+ * A block-sparse volume over the lattice p(i,j,k) = origin + voxel_size (i,j,k), 0 <= i,j,k < 8 nb: `table` [nb z, nb y, nb x] int32
+ * holds the pool slot of every block of 8x8x8 lattice points (x fastest) or -1, `slot_block` [n_slots] int32 the linear table
+ * index of every slot.  Per slot tsdf_sum [512] and weight_sum [512] float32, and colour_sum [3][512] (channel planes, so that a
+ * wave reads and writes 256 contiguous bytes per plane) or NULL.  1 <= nb <= MSGS_TSDF_MAX_BLOCKS_PER_AXIS, n_slots <=
+ * MSGS_TSDF_MAX_SLOTS; anything else returns MSGS_ERR_INVALID_ARG and launches nothing.
+ * Frames: n rows of the camera table of msgs_filter3d_sweep (all of width W and height H), depth [n,H,W], colour [n,3,H,W] or
+ * NULL, weight [n,H,W] or NULL (1), float32.  A pixel is a surface sample iff 0 < d <= depth_trunc and d is finite.
+ *   msgs_tsdf_mark_blocks  writes 1 into marks [nb z nb y nb x] (bytes, cleared by the caller) for every block that holds one of
+ *                          the points of a surface sample's ray at the view depths (d - r) + k (2 r / steps), k = 0..steps,
+ *                          r = sdf_trunc + 2 voxel_size (depths <= 0 are left out); the view matrices must be rigid.
+ *   msgs_tsdf_integrate    lattice point p, camera row M: t = p M, pixel (floor(t.x / t.z fx + W/2), floor(t.y / t.z fy + H/2));
+ *                          skipped iff t.z <= 0, the pixel is outside, it is no surface sample, its weight is not positive and
+ *                          finite, or d - t.z < -sdf_trunc; otherwise tsdf_sum += w min(1, (d - t.z) / sdf_trunc), weight_sum += w,
+ *                          colour_sum += w c, in camera order from the stored values.  One read and one write of the pool.
+ *   msgs_tsdf_count        a lattice point is observed iff weight_sum > 0 and inside iff it is observed and tsdf_sum < 0.  Per
+ *                          lattice point: edge_mask (bit d - 1: the edge to the lattice point at +d, d = dx + 2 dy + 4 dz in 1..7,
+ *                          has both ends observed and exactly one inside) and vertex_count = its bit count; per cube (stored at its
+ *                          lowest corner; meshed iff all 8 corners are observed) triangle_count of its six Kuhn tetrahedra.
+ *   msgs_tsdf_emit         with the exclusive scans of both counts: vertices / colours [n_vertices,3] float32 (colours NULL
+ *                          without colour_sum), faces [n_faces,3] int32, normals towards positive TSDF; nothing is written past
+ *                          n_vertices / n_faces.
+ * All arrays per lattice point are [n_slots, 512].  No atomics: the same bits on every run.  Everything on `stream`, no
+ * synchronisation; n_slots == 0 or n == 0 launches nothing. */
+#define MSGS_TSDF_CAMERA_CHUNK 64          /* camera rows staged per pass of the integration (tests straddle it) */
+#define MSGS_TSDF_MAX_BLOCKS_PER_AXIS 256
+#define MSGS_TSDF_MAX_SLOTS (1 << 22)
+typedef struct msgs_tsdf_volume {
+    float origin[3];
+    float voxel_size;
+    int32_t nb[3];                   /* blocks along x, y, z */
+    int32_t n_slots;
+    const int32_t* table;
+    const int32_t* slot_block;
+    float* tsdf_sum;
+    float* weight_sum;
+    float* colour_sum;               /* or NULL */
+} msgs_tsdf_volume_t;
+typedef struct msgs_tsdf_frames {
+    int32_t n;
+    int32_t W;
+    int32_t H;
+    int32_t reserved;
+    const float* cameras;            /* [n, MSGS_FILTER3D_CAMERA_FLOATS] */
+    const float* depth;
+    const float* colour;             /* or NULL */
+    const float* weight;             /* or NULL */
+    float sdf_trunc;
+    float depth_trunc;
+} msgs_tsdf_frames_t;
+typedef struct msgs_tsdf_mesh {
+    const uint8_t* edge_mask;
+    const int32_t* vertex_offset;
+    const int32_t* triangle_offset;
+    int32_t n_vertices;
+    int32_t n_faces;
+    float* vertices;
+    float* colours;                  /* or NULL */
+    int32_t* faces;
+} msgs_tsdf_mesh_t;
+int msgs_tsdf_mark_blocks(const msgs_tsdf_volume_t* v, const msgs_tsdf_frames_t* f, int32_t steps, uint8_t* marks, void* stream);
+int msgs_tsdf_integrate(const msgs_tsdf_volume_t* v, const msgs_tsdf_frames_t* f, void* stream);
+int msgs_tsdf_count(const msgs_tsdf_volume_t* v, uint8_t* edge_mask, int32_t* vertex_count, int32_t* triangle_count,
+                    void* stream);
+int msgs_tsdf_emit(const msgs_tsdf_volume_t* v, const msgs_tsdf_mesh_t* m, void* stream);
+
 /* ---- fused photometric loss ----------------------------------------------------------------
  * loss = (1 - lambda_dssim) * l1_loss(img, gt) + lambda_dssim * (1 - ssim(img, gt))   (/root/reference/train.py:209-211)
  * with l1_loss / ssim of /root/reference/utils/loss_utils.py:17-18,32-63 (window 11, sigma 1.5, zero padding, mean).

@@ -1558,6 +1558,60 @@ int msgs_bilagrid_tv_backward(int64_t N, int32_t GX, int32_t GY, int32_t GL, con
     return MSGS_OK;
 }
 
+// ---- TSDF fusion and mesh extraction (SPEC M20) ----
+static int tsdf_geometry_ok(const msgs_tsdf_volume_t* v) {
+    if (!v || !(v->voxel_size > 0.f) || !(v->voxel_size < INFINITY)) return 0;
+    for (int a = 0; a < 3; ++a)
+        if (v->nb[a] < 1 || v->nb[a] > MSGS_TSDF_MAX_BLOCKS_PER_AXIS || !(fabsf(v->origin[a]) < INFINITY)) return 0;
+    return 1;
+}
+
+static int tsdf_pool_ok(const msgs_tsdf_volume_t* v) {
+    if (!tsdf_geometry_ok(v) || v->n_slots < 0 || v->n_slots > MSGS_TSDF_MAX_SLOTS) return 0;
+    return v->n_slots == 0 || (v->table && v->slot_block && v->tsdf_sum && v->weight_sum);
+}
+
+static int tsdf_frames_ok(const msgs_tsdf_frames_t* f) {
+    if (!f || f->n < 0 || f->n > 65535 || f->W < 1 || f->H < 1 || (int64_t)f->W * f->H >= ((int64_t)1 << 29)) return 0;
+    if (!(f->sdf_trunc > 0.f) || !(f->sdf_trunc < INFINITY) || !(f->depth_trunc > 0.f)) return 0;
+    return f->n == 0 || (f->cameras && f->depth);
+}
+
+int msgs_tsdf_mark_blocks(const msgs_tsdf_volume_t* v, const msgs_tsdf_frames_t* f, int32_t steps, uint8_t* marks, void* stream) {
+    if (!tsdf_geometry_ok(v) || !tsdf_frames_ok(f) || steps < 1 || steps > (1 << 16) || !marks) return MSGS_ERR_INVALID_ARG;
+    if (f->n == 0) return MSGS_OK;
+    HIP_TRY(launch_tsdf_mark_blocks(*v, *f, steps, marks, (hipStream_t)stream));
+    return MSGS_OK;
+}
+
+int msgs_tsdf_integrate(const msgs_tsdf_volume_t* v, const msgs_tsdf_frames_t* f, void* stream) {
+    if (!tsdf_pool_ok(v) || !tsdf_frames_ok(f)) return MSGS_ERR_INVALID_ARG;
+    if (f->n > 0 && f->colour && !v->colour_sum) return MSGS_ERR_INVALID_ARG;      // colours with nowhere to go
+    if (f->n > 0 && v->n_slots > 0 && v->colour_sum && !f->colour) return MSGS_ERR_INVALID_ARG;
+    if (v->n_slots == 0 || f->n == 0) return MSGS_OK;
+    HIP_TRY(launch_tsdf_integrate(*v, *f, (hipStream_t)stream));
+    return MSGS_OK;
+}
+
+int msgs_tsdf_count(const msgs_tsdf_volume_t* v, uint8_t* edge_mask, int32_t* vertex_count, int32_t* triangle_count,
+                    void* stream) {
+    if (!tsdf_pool_ok(v)) return MSGS_ERR_INVALID_ARG;
+    if (v->n_slots == 0) return MSGS_OK;
+    if (!edge_mask || !vertex_count || !triangle_count) return MSGS_ERR_INVALID_ARG;
+    HIP_TRY(launch_tsdf_count(*v, edge_mask, vertex_count, triangle_count, (hipStream_t)stream));
+    return MSGS_OK;
+}
+
+int msgs_tsdf_emit(const msgs_tsdf_volume_t* v, const msgs_tsdf_mesh_t* m, void* stream) {
+    if (!tsdf_pool_ok(v) || !m || m->n_vertices < 0 || m->n_faces < 0) return MSGS_ERR_INVALID_ARG;
+    if (v->n_slots == 0 || (m->n_vertices == 0 && m->n_faces == 0)) return MSGS_OK;
+    if (!m->edge_mask || !m->vertex_offset || !m->triangle_offset) return MSGS_ERR_INVALID_ARG;
+    if ((m->n_vertices > 0 && (!m->vertices || (v->colour_sum && !m->colours))) || (m->n_faces > 0 && !m->faces))
+        return MSGS_ERR_INVALID_ARG;
+    HIP_TRY(launch_tsdf_emit(*v, *m, (hipStream_t)stream));
+    return MSGS_OK;
+}
+
 static int loss_args_ok(const float* img, const float* gt, int32_t C, int32_t H, int32_t W, float lambda) {
     if (!img || !gt || C < 1 || H < 1 || W < 1 || !(lambda >= 0.f && lambda <= 1.f)) return MSGS_ERR_INVALID_ARG;
     if ((int64_t)C * H * W > (int64_t)1 << 31 || C > 65535) return MSGS_ERR_TOO_MANY;

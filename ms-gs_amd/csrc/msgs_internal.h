@@ -932,6 +932,14 @@ hipError_t launch_depth_normal_backward(int W, int H, float tanfovx, float tanfo
 hipError_t launch_blend_median_depth_forward(const ReplayInputs& in, float* out_depth, int32_t* out_id, hipStream_t s);
 hipError_t launch_median_depth_backward(const ViewParams& vp, int P, const int32_t* median_id, const float* dL_dmedian,
                                         grad_acc_t* grad_rec, hipStream_t s);
+// tsdf.hip — msgs_tsdf_* (SPEC M20): block activation, projective TSDF integration, and the count and emit passes of the
+// marching-tetrahedra extraction (the arguments are checked in api.hip)
+hipError_t launch_tsdf_mark_blocks(const msgs_tsdf_volume_t& v, const msgs_tsdf_frames_t& f, int steps, uint8_t* marks,
+                                   hipStream_t s);
+hipError_t launch_tsdf_integrate(const msgs_tsdf_volume_t& v, const msgs_tsdf_frames_t& f, hipStream_t s);
+hipError_t launch_tsdf_count(const msgs_tsdf_volume_t& v, uint8_t* edge_mask, int32_t* vertex_count, int32_t* triangle_count,
+                             hipStream_t s);
+hipError_t launch_tsdf_emit(const msgs_tsdf_volume_t& v, const msgs_tsdf_mesh_t& m, hipStream_t s);
 // heaviest-first launch order of the one-wave-per-tile backward from the forward's per-tile traversal lengths
 hipError_t launch_tile_order(const ViewParams& vp, const uint32_t* tile_last, uint32_t* tile_order, hipStream_t s);
 hipError_t launch_blend_lane_stats(const ViewParams& vp, const char* geom, const uint32_t* ids, const uint2* ranges,

@@ -31,7 +31,9 @@ __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gau
            "deferred_forward", "GradAccumulator", "set_grad_accumulator", "ContributionScores", "ContributionAccumulator",
            "screen_compensation", "compute_3d_filter", "smoothing_filter", "FILTER3D_CAMERA_CHUNK",
            "gaussian_normals", "depth_to_normal", "DEPTH_NORMAL_TILE_W", "DEPTH_NORMAL_TILE_H",
-           "bilateral_slice", "total_variation_loss", "BILAGRID_TILE_W", "BILAGRID_TILE_H", "BILAGRID_WINDOW_CELLS"]
+           "bilateral_slice", "total_variation_loss", "BILAGRID_TILE_W", "BILAGRID_TILE_H", "BILAGRID_WINDOW_CELLS",
+           "tsdf_allocate", "tsdf_integrate", "tsdf_extract", "tsdf_mark_steps", "TSDF_CAMERA_CHUNK", "TSDF_MAX_BLOCKS_PER_AXIS",
+           "TSDF_MAX_SLOTS"]
 
 
 class GaussianRasterizationSettings(NamedTuple):
@@ -2160,6 +2162,208 @@ def total_variation_loss(grids):
         raise ValueError(f"total_variation_loss: grids must be [N,12,GL,GY,GX], got {tuple(grids.shape)}")
     _bilagrid_sizes(grids[0] if grids.shape[0] else grids.new_zeros((12,) + tuple(grids.shape[2:])), "total_variation_loss")
     return _TotalVariation.apply(grids)
+
+
+# TSDF fusion and mesh extraction (4.22): depth maps (median depth, by preference) fused into a block-sparse
+# volume of TSDF and weight SUMS, and the zero level set extracted by marching tetrahedra.  `volume` is any object with the
+# attributes of host/tsdf.py's TSDFVolume: origin (3 floats), voxel_size, blocks (NBx, NBy, NBz), table int32 [NBz,NBy,NBx],
+# slot_block int32 [S], tsdf_sum / weight_sum float32 [S,512], colour_sum float32 [S,3,512] or None.  Nothing here is
+# differentiable.
+TSDF_CAMERA_CHUNK = _C.TSDF_CAMERA_CHUNK
+TSDF_MAX_BLOCKS_PER_AXIS, TSDF_MAX_SLOTS = _C.TSDF_MAX_BLOCKS_PER_AXIS, _C.TSDF_MAX_SLOTS
+_tsdf_probe = None                 # tests: a callable (name) run in front of every msgs_tsdf_* call
+
+
+def tsdf_mark_steps(voxel_size, sdf_trunc, table):
+    """steps of the activation walk: the smallest count for which a step of 2 r / steps in view depth, r = sdf_trunc + 2 voxels,
+    is at most one voxel along every ray of the host camera table [n,20] — ceil(2 r L / voxel) with L = max over the rows of
+    sqrt(1 + tanfovx^2 + tanfovy^2), formed in double from the float32 values the kernels read"""
+    import math
+    import numpy as np
+    v, t = float(np.float32(voxel_size)), float(np.float32(sdf_trunc))
+    tab = table.detach().cpu().double()
+    L = torch.sqrt(1.0 + (tab[:, 18] / (2.0 * tab[:, 16])) ** 2 + (tab[:, 19] / (2.0 * tab[:, 17])) ** 2).max().item()
+    return max(1, int(math.ceil(2.0 * (t + 2.0 * v) * L / v)))
+
+
+def _tsdf_geometry(volume, who):
+    blocks = tuple(int(b) for b in volume.blocks)
+    if len(blocks) != 3 or any(b < 1 or b > TSDF_MAX_BLOCKS_PER_AXIS for b in blocks):
+        raise ValueError(f"{who}: the volume has {blocks} blocks, 1 .. {TSDF_MAX_BLOCKS_PER_AXIS} per axis are supported")
+    if not float(volume.voxel_size) > 0.0:
+        raise ValueError(f"{who}: voxel_size must be positive")
+    table = volume.table
+    if table.dtype != torch.int32 or tuple(table.shape) != blocks[::-1] or not table.is_contiguous():
+        raise ValueError(f"{who}: table must be a contiguous int32 tensor {blocks[::-1]}")
+    v = _C.TsdfVolume()
+    v.origin[:] = [float(o) for o in volume.origin]
+    v.voxel_size = float(volume.voxel_size)
+    v.nb[:] = blocks
+    v.table = table.data_ptr()
+    return v
+
+
+def _tsdf_pool(volume, who):
+    v = _tsdf_geometry(volume, who)
+    dev = volume.table.device
+    S = int(volume.slot_block.shape[0])
+    if S > TSDF_MAX_SLOTS:
+        raise ValueError(f"{who}: {S} pool slots, at most {TSDF_MAX_SLOTS} are supported")
+    want = [("slot_block", volume.slot_block, torch.int32, (S,)), ("tsdf_sum", volume.tsdf_sum, torch.float32, (S, 512)),
+            ("weight_sum", volume.weight_sum, torch.float32, (S, 512))]
+    if volume.colour_sum is not None:
+        want.append(("colour_sum", volume.colour_sum, torch.float32, (S, 3, 512)))
+    for name, t, dtype, shape in want:
+        if t.device != dev or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f"{who}: {name} must be a contiguous {dtype} tensor {shape} on {dev}")
+    v.n_slots = S
+    v.slot_block, v.tsdf_sum, v.weight_sum = volume.slot_block.data_ptr(), volume.tsdf_sum.data_ptr(), volume.weight_sum.data_ptr()
+    v.colour_sum = None if volume.colour_sum is None else volume.colour_sum.data_ptr()
+    return v
+
+
+def _tsdf_on_device(who, dev, **tensors):
+    """the last check in front of a launch: the volume and every map live on one HIP device"""
+    if dev.type != "cuda":
+        raise RuntimeError(f"{who}: the volume must live on a HIP device ('cuda'); there is no CPU path")
+    for name, t in tensors.items():
+        if t is not None and t.device.type != "cuda":
+            raise RuntimeError(f"{who}: {name} must live on a HIP device ('cuda'); there is no CPU path")
+        if t is not None and t.device != dev:
+            raise ValueError(f"{who}: {name} is on {t.device}, the volume on {dev}")
+
+
+def _tsdf_frames(who, dev, depth, cameras, sdf_trunc, depth_trunc, colour=None, weight=None):
+    """(msgs_tsdf_frames_t, the host camera table, the tensors it points to) — everything is checked before any launch"""
+    for name, t in (("depth", depth), ("colour", colour), ("weight", weight)):
+        if t is None:
+            continue
+        if not torch.is_tensor(t):
+            raise ValueError(f"{who}: {name} must be a tensor")
+        if t.dtype != torch.float32:
+            raise ValueError(f"{who}: {name} must be float32, not {t.dtype}")
+        if t.requires_grad:
+            raise ValueError(f"{who}: {name} requires grad — TSDF fusion is not differentiable: pass {name}.detach()")
+    if depth.dim() != 3:
+        raise ValueError(f"{who}: depth must be [n,H,W], got {tuple(depth.shape)}")
+    n, H, W = (int(x) for x in depth.shape)
+    if H < 1 or W < 1 or W * H >= 1 << 29 or n > 65535:
+        raise ValueError(f"{who}: depth [n,H,W] = {tuple(depth.shape)} is outside the supported sizes")
+    if colour is not None and tuple(colour.shape) != (n, 3, H, W):
+        raise ValueError(f"{who}: colour must be [n,3,H,W] = {(n, 3, H, W)}, got {tuple(colour.shape)}")
+    if weight is not None and tuple(weight.shape) != (n, H, W):
+        raise ValueError(f"{who}: weight must be [n,H,W] = {(n, H, W)}, got {tuple(weight.shape)}")
+    if not (float(sdf_trunc) > 0.0 and float(sdf_trunc) < float("inf")):
+        raise ValueError(f"{who}: sdf_trunc must be positive and finite")
+    if not float(depth_trunc) > 0.0:
+        raise ValueError(f"{who}: depth_trunc must be positive")
+    if torch.is_tensor(cameras):
+        table = cameras.detach().float().cpu().contiguous()
+        if table.dim() != 2 or table.shape[1] != _C.FILTER3D_CAMERA_FLOATS:
+            raise ValueError(f"{who}: a camera table must be [n,{_C.FILTER3D_CAMERA_FLOATS}]")
+    else:
+        cameras = list(cameras)
+        table = _camera_table(cameras) if cameras else torch.zeros(0, _C.FILTER3D_CAMERA_FLOATS)
+    if table.shape[0] != n:
+        raise ValueError(f"{who}: {table.shape[0]} cameras for {n} depth maps")
+    if n and not bool(((table[:, 18] == W) & (table[:, 19] == H)).all()):
+        raise ValueError(f"{who}: every camera of a call must have the size of the depth maps, {W}x{H}")
+    _tsdf_on_device(who, dev, depth=depth, colour=colour, weight=weight)
+    f = _C.TsdfFrames()
+    f.n, f.W, f.H = n, W, H
+    f.sdf_trunc, f.depth_trunc = float(sdf_trunc), float(depth_trunc)
+    return f, table, [t if t is None or t.is_contiguous() else t.contiguous() for t in (depth, colour, weight)]
+
+
+@torch.no_grad()
+def tsdf_allocate(volume, depth, cameras, sdf_trunc, depth_trunc):
+    """uint8 [NBz,NBy,NBx]: 1 for every block of the volume's table that holds a sample of the activation walk of SPEC M20 — for
+    every pixel with 0 < d <= depth_trunc the points of its ray (through the pixel centre, a_x = ((2x+1)/W - 1) tanfovx) at the
+    view depths (d - r) + k 2 r / steps, k = 0 .. steps, r = sdf_trunc + 2 voxels, steps = tsdf_mark_steps(...).  Free space in
+    front of the surface is not marked.  One kernel, one lane per pixel; the volume is not changed and nothing is read back."""
+    v = _tsdf_geometry(volume, "tsdf_allocate")
+    dev = volume.table.device
+    f, table, (depth, _, _) = _tsdf_frames("tsdf_allocate", dev, depth, cameras, sdf_trunc, depth_trunc)
+    marks = torch.zeros(volume.table.shape, dtype=torch.uint8, device=dev)
+    if f.n == 0:
+        return marks
+    steps = tsdf_mark_steps(volume.voxel_size, sdf_trunc, table)
+    with _on_device(dev):
+        cams = table.to(dev)
+        f.cameras, f.depth = cams.data_ptr(), depth.data_ptr()
+        if _tsdf_probe is not None:
+            _tsdf_probe("msgs_tsdf_mark_blocks")
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _C.check(_C.lib.msgs_tsdf_mark_blocks(C.byref(v), C.byref(f), steps, _ptr(marks), stream), "msgs_tsdf_mark_blocks")
+    return marks
+
+
+@torch.no_grad()
+def tsdf_integrate(volume, depth, cameras, sdf_trunc, depth_trunc, colour=None, weight=None):
+    """Adds the views (depth [n,H,W], cameras: n camera objects or a [n,20] table, colour [n,3,H,W] iff the volume stores colour,
+    weight [n,H,W] or 1) to the sums of every pool slot of `volume`, in place: projective TSDF with nearest-pixel lookup,
+    tsdf_sum += w min(1, (d - t.z) / sdf_trunc), weight_sum += w, colour_sum += w c, in camera order (SPEC M20).  One kernel,
+    one workgroup per slot; the pool is read and written once whatever n is.  Returns None."""
+    v = _tsdf_pool(volume, "tsdf_integrate")
+    dev = volume.table.device
+    f, table, (depth, colour, weight) = _tsdf_frames("tsdf_integrate", dev, depth, cameras, sdf_trunc, depth_trunc, colour, weight)
+    if (colour is None) != (volume.colour_sum is None) and f.n:
+        raise ValueError("tsdf_integrate: colour maps are needed exactly when the volume stores colour")
+    if v.n_slots == 0 or f.n == 0:
+        return
+    with _on_device(dev):
+        cams = table.to(dev)
+        f.cameras, f.depth = cams.data_ptr(), depth.data_ptr()
+        f.colour = None if colour is None else colour.data_ptr()
+        f.weight = None if weight is None else weight.data_ptr()
+        if _tsdf_probe is not None:
+            _tsdf_probe("msgs_tsdf_integrate")
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _C.check(_C.lib.msgs_tsdf_integrate(C.byref(v), C.byref(f), stream), "msgs_tsdf_integrate")
+
+
+@torch.no_grad()
+def tsdf_extract(volume):
+    """(vertices [V,3] float32, colours [V,3] float32 or None, faces [F,3] int32): the zero level set of T = tsdf_sum / weight_sum
+    over the observed lattice points by marching tetrahedra (six Kuhn tetrahedra per cube, SPEC M20) — indexed and welded by
+    construction, normals towards positive TSDF, in a fixed order.  A count kernel, two torch.cumsum, one host read of the two
+    totals, an emit kernel.  Vertices no face uses (on edges without a fully observed cube) are kept; see
+    TSDFVolume.extract_mesh(drop_unreferenced=True)."""
+    v = _tsdf_pool(volume, "tsdf_extract")
+    dev = volume.table.device
+    _tsdf_on_device("tsdf_extract", dev)
+    S = v.n_slots
+    has_colour = volume.colour_sum is not None
+    empty = (torch.zeros(0, 3, device=dev), torch.zeros(0, 3, device=dev) if has_colour else None,
+             torch.zeros(0, 3, dtype=torch.int32, device=dev))
+    if S == 0:
+        return empty
+    with _on_device(dev):
+        mask = torch.empty(S * 512, dtype=torch.uint8, device=dev)
+        vcount = torch.empty(S * 512, dtype=torch.int32, device=dev)
+        tcount = torch.empty(S * 512, dtype=torch.int32, device=dev)
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        if _tsdf_probe is not None:
+            _tsdf_probe("msgs_tsdf_count")
+        _C.check(_C.lib.msgs_tsdf_count(C.byref(v), _ptr(mask), _ptr(vcount), _ptr(tcount), stream), "msgs_tsdf_count")
+        vend, tend = torch.cumsum(vcount, 0, dtype=torch.int64), torch.cumsum(tcount, 0, dtype=torch.int64)
+        V, F = (int(x) for x in torch.stack((vend[-1], tend[-1])).tolist())
+        if V >= 1 << 31 or F >= 1 << 31:
+            raise ValueError(f"tsdf_extract: {V} vertices and {F} faces do not fit int32 indices")
+        if V == 0 and F == 0:
+            return empty
+        m = _C.TsdfMesh()
+        voff, toff = (vend - vcount).to(torch.int32), (tend - tcount).to(torch.int32)
+        vertices = torch.empty(V, 3, dtype=torch.float32, device=dev)
+        colours = torch.empty(V, 3, dtype=torch.float32, device=dev) if has_colour else None
+        faces = torch.empty(F, 3, dtype=torch.int32, device=dev)
+        m.edge_mask, m.vertex_offset, m.triangle_offset = mask.data_ptr(), voff.data_ptr(), toff.data_ptr()
+        m.n_vertices, m.n_faces = V, F
+        m.vertices, m.colours, m.faces = vertices.data_ptr(), None if colours is None else colours.data_ptr(), faces.data_ptr()
+        if _tsdf_probe is not None:
+            _tsdf_probe("msgs_tsdf_emit")
+        _C.check(_C.lib.msgs_tsdf_emit(C.byref(v), C.byref(m), stream), "msgs_tsdf_emit")
+    return vertices, colours, faces
 
 
 # Contribution scores (DESIGN.md 2, M11; 4.11): what every Gaussian did to the images of one or many views, the criterion of

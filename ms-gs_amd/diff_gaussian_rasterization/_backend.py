@@ -135,6 +135,28 @@ class McmcRelocate(C.Structure):         # msgs_mcmc_relocate_t
                 ("u", C.c_void_p), ("tensors", C.POINTER(McmcTensor))]
 
 
+# msgs_tsdf_* (include/msgs.h): camera rows staged per pass of the integration, the limits of the block table and the pool
+TSDF_CAMERA_CHUNK, TSDF_MAX_BLOCKS_PER_AXIS, TSDF_MAX_SLOTS = 64, 256, 1 << 22
+
+
+class TsdfVolume(C.Structure):           # msgs_tsdf_volume_t
+    _fields_ = [("origin", C.c_float * 3), ("voxel_size", C.c_float), ("nb", C.c_int32 * 3), ("n_slots", C.c_int32),
+                ("table", C.c_void_p), ("slot_block", C.c_void_p), ("tsdf_sum", C.c_void_p), ("weight_sum", C.c_void_p),
+                ("colour_sum", C.c_void_p)]
+
+
+class TsdfFrames(C.Structure):           # msgs_tsdf_frames_t
+    _fields_ = [("n", C.c_int32), ("W", C.c_int32), ("H", C.c_int32), ("reserved", C.c_int32),
+                ("cameras", C.c_void_p), ("depth", C.c_void_p), ("colour", C.c_void_p), ("weight", C.c_void_p),
+                ("sdf_trunc", C.c_float), ("depth_trunc", C.c_float)]
+
+
+class TsdfMesh(C.Structure):             # msgs_tsdf_mesh_t
+    _fields_ = [("edge_mask", C.c_void_p), ("vertex_offset", C.c_void_p), ("triangle_offset", C.c_void_p),
+                ("n_vertices", C.c_int32), ("n_faces", C.c_int32),
+                ("vertices", C.c_void_p), ("colours", C.c_void_p), ("faces", C.c_void_p)]
+
+
 class Timing(C.Structure):
     _fields_ = [("ev", C.c_void_p * (2 * K_COUNT))]
 
@@ -322,6 +344,14 @@ def _load():
     lib.msgs_mcmc_relocate.argtypes = [C.POINTER(McmcRelocate), vp, sz, vp]
     lib.msgs_mcmc_noise.restype = C.c_int
     lib.msgs_mcmc_noise.argtypes = [C.c_int64, vp, vp, vp, vp, vp, C.c_float, vp]
+    lib.msgs_tsdf_mark_blocks.restype = C.c_int
+    lib.msgs_tsdf_mark_blocks.argtypes = [C.POINTER(TsdfVolume), C.POINTER(TsdfFrames), C.c_int32, vp, vp]
+    lib.msgs_tsdf_integrate.restype = C.c_int
+    lib.msgs_tsdf_integrate.argtypes = [C.POINTER(TsdfVolume), C.POINTER(TsdfFrames), vp]
+    lib.msgs_tsdf_count.restype = C.c_int
+    lib.msgs_tsdf_count.argtypes = [C.POINTER(TsdfVolume), vp, vp, vp, vp]
+    lib.msgs_tsdf_emit.restype = C.c_int
+    lib.msgs_tsdf_emit.argtypes = [C.POINTER(TsdfVolume), C.POINTER(TsdfMesh), vp]
     lib.msgs_loss_scratch_bytes.restype = sz
     lib.msgs_loss_scratch_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
     lib.msgs_loss_forward.restype = C.c_int
@@ -378,6 +408,7 @@ EXPORTS = ("msgs_abi_version", "msgs_error_string", "msgs_geom_bytes", "msgs_sta
            "msgs_bilagrid_scratch_bytes", "msgs_bilagrid_slice_forward", "msgs_bilagrid_slice_backward",
            "msgs_bilagrid_tv_scratch_bytes", "msgs_bilagrid_tv_forward", "msgs_bilagrid_tv_backward",
            "msgs_mcmc_scratch_bytes", "msgs_mcmc_prepare", "msgs_mcmc_sample", "msgs_mcmc_relocate", "msgs_mcmc_noise",
+           "msgs_tsdf_mark_blocks", "msgs_tsdf_integrate", "msgs_tsdf_count", "msgs_tsdf_emit",
            "msgs_set_depth_sort", "msgs_depth_sort_stats")
 
 

@@ -52,6 +52,34 @@ def write_ply(path, columns):
         f.write(rec.tobytes())
 
 
+def write_mesh_ply(path, vertices, faces, colours=None):
+    """A triangle mesh as binary_little_endian PLY: element vertex (float x y z, and uchar red green blue when `colours` [V,3]
+    in [0,1] is given: clamped, times 255, rounded) and element face (property list uchar int vertex_indices, 3 per face).
+    vertices [V,3] and faces [F,3] are tensors or arrays (TSDFVolume.extract_mesh).  read_ply reads the vertex element back."""
+    arr = lambda t: t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+    v, f = arr(vertices).astype("<f4").reshape(-1, 3), arr(faces).astype("<i4").reshape(-1, 3)
+    fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+    if colours is not None:
+        fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
+    vrec = np.empty(len(v), dtype=np.dtype(fields))
+    vrec["x"], vrec["y"], vrec["z"] = v[:, 0], v[:, 1], v[:, 2]
+    if colours is not None:
+        c = np.rint(np.clip(arr(colours).astype(np.float64).reshape(-1, 3), 0.0, 1.0) * 255.0).astype(np.uint8)
+        if len(c) != len(v):
+            raise ValueError(f"write_mesh_ply: {len(c)} colours for {len(v)} vertices")
+        vrec["red"], vrec["green"], vrec["blue"] = c[:, 0], c[:, 1], c[:, 2]
+    frec = np.empty(len(f), dtype=np.dtype([("n", "u1"), ("v", "<i4", (3,))]))
+    frec["n"], frec["v"] = 3, f
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    header = ["ply", "format binary_little_endian 1.0", f"element vertex {len(v)}"]
+    header += [f"property {'uchar' if t == 'u1' else 'float'} {k}" for k, t in fields]
+    header += [f"element face {len(f)}", "property list uchar int vertex_indices", "end_header"]
+    with open(path, "wb") as out:
+        out.write(("\n".join(header) + "\n").encode("ascii"))
+        out.write(vrec.tobytes())
+        out.write(frec.tobytes())
+
+
 def read_ply(path):
     """First element of a binary_little_endian (or ascii) PLY as a numpy structured array."""
     with open(path, "rb") as f:
