@@ -15,8 +15,14 @@ open3d is third-party and not vendored by the reference; its documented behaviou
 floor(p / voxel_size) per axis; 'average' = arithmetic mean; 'center' = voxel centre).  The ORDER of the pooled rows is
 unspecified in open3d; here it is ascending (z, y, x) voxel index.  All eleven tensors share one grouping, so rows
 stay aligned exactly as the reference requires.
+
+The voxel rule AS BUILT (csrc/voxel_pool.hip) is the float32 product floor(fl32(p * fl32(1 / voxel_size))), clamped in
+float to [-2^20, 2^20 - 1]: on an exact multiple k * voxel_size it can name the voxel below the quotient's (about one k
+in ten at the call site's voxel sizes); +-inf and out-of-range coordinates fall into the outermost cell of their side.
+Means are float32 sums in ascending point id, divided by float32(count): reproducible bit for bit.
 """
 import ctypes as C
+import weakref
 from types import SimpleNamespace
 
 import torch
@@ -90,13 +96,16 @@ class VoxelPooling:
             raise NotImplementedError(f"VoxelPooling(position_fn={position_fn!r}, feature_fn={feature_fn!r}): only "
                                       "position_fn in ('center', 'average') with feature_fn='average' is provided")
         self.position_fn = position_fn
-        self._cache = None      # (key, grouping): the reference calls with the same positions eleven times
+        self._cache = None      # (weakref, key, grouping): the reference calls with the same positions eleven times
 
     def __call__(self, positions, features, voxel_size):
+        # A hit needs the SAME tensor object, unmodified: an address says nothing (the allocator hands a freed tensor's
+        # address, at version 0 again, to the next tensor of that shape).  The reference is weak, so the cache keeps no
+        # caller's tensor alive; a dead one never compares identical to a live tensor.
         key = (positions.data_ptr(), tuple(positions.shape), positions._version, float(voxel_size), str(positions.device))
-        if self._cache is None or self._cache[0] != key:
-            self._cache = (key, VoxelGrouping(positions, voxel_size))
-        g = self._cache[1]
+        if self._cache is None or self._cache[0]() is not positions or self._cache[1] != key:
+            self._cache = (weakref.ref(positions), key, VoxelGrouping(positions, voxel_size))
+        g = self._cache[2]
         pooled_pos = g.centers if self.position_fn == "center" else g.mean_positions()
         return SimpleNamespace(pooled_positions=pooled_pos, pooled_features=g.average(features))
 
