@@ -105,13 +105,26 @@ def depth_key_f32(means3D, viewmatrix):
 
 def preprocess(means3D, opacities, view, *, scales=None, rotations=None, cov3D_precomp=None,
                shs=None, colors_precomp=None, max_pixel_sizes=None, min_pixel_sizes=None,
-               base_mask=None, dtype=torch.float64):
+               base_mask=None, dtype=torch.float64, _decisions=None):
     """Per-Gaussian stage.  `view` is a dict with image_width/height, tanfovx/y, viewmatrix [4,4],
     projmatrix [4,4], campos [3], sh_degree, scale_modifier, filter_small, filter_large, fade_size.
     Returns a dict of per-Gaussian tensors (float64; differentiable where meaningful).  `dtype`:
     torch.float32 evaluates the same expressions in float32 (tests/replay_truth.py: the reference's
-    own float32 distance from its float64 result)."""
+    own float32 distance from its float64 result).
+
+    The discrete decisions the SPEC words on float32 arithmetic — the Q2 clamp masks (limit 1.3f * tanfov), Q3 (det == 0.0f),
+    Q5 (the tile rect: an int() of float32 quotients) and the 255f * o > 1.0f gate of M1 — are taken on the float32 evaluation
+    in every dtype, as Q1 and Q10 always were: at an exact float32 tie (tests/preprocess_ties.py) the float64 values do not tie
+    (the +0.3 of Q3 and the 1e-7 of Q9 are no longer absorbed, 1.3 * tanfov is not 1.3f * tanfov), and away from a tie the two
+    agree."""
     dt = dtype
+    dec = _decisions
+    if dec is None and dt != torch.float32:
+        det_ = lambda t: None if t is None else t.detach()
+        with torch.no_grad():
+            dec = preprocess(det_(means3D), det_(opacities), view, scales=det_(scales), rotations=det_(rotations),
+                             cov3D_precomp=det_(cov3D_precomp), shs=det_(shs), colors_precomp=det_(colors_precomp),
+                             dtype=torch.float32)
     P = means3D.shape[0]
     W, H = int(view["image_width"]), int(view["image_height"])
     V = view["viewmatrix"].to(dt)
@@ -138,9 +151,12 @@ def preprocess(means3D, opacities, view, *, scales=None, rotations=None, cov3D_p
     tx, ty, tz = p_view[:, 0], p_view[:, 1], p_view[:, 2]
     tz_safe = torch.where(in_front, tz, torch.ones_like(tz))
     limx, limy = 1.3 * tanx, 1.3 * tany
+    if dt == torch.float32:               # the limit as the float32 implementations form it: 1.3f * tanfov, one rounding
+        f32 = lambda v: torch.tensor(v, dtype=torch.float32)
+        limx, limy = float(f32(1.3) * f32(tanx)), float(f32(1.3) * f32(tany))
     txtz, tytz = tx / tz_safe, ty / tz_safe
-    cx = (txtz < -limx) | (txtz > limx)
-    cy = (tytz < -limy) | (tytz > limy)
+    cx = ((txtz < -limx) | (txtz > limx)) if dec is None else dec["clamped_x"]           # Q2: strict
+    cy = ((tytz < -limy) | (tytz > limy)) if dec is None else dec["clamped_y"]
     tx_c = torch.where(cx, (txtz.clamp(-limx, limx) * tz_safe).detach(), tx)   # Q2
     ty_c = torch.where(cy, (tytz.clamp(-limy, limy) * tz_safe).detach(), ty)
     fx, fy = W / (2.0 * tanx), H / (2.0 * tany)
@@ -157,7 +173,8 @@ def preprocess(means3D, opacities, view, *, scales=None, rotations=None, cov3D_p
     b = cov2[:, 0, 1]
     c = cov2[:, 1, 1] + 0.3
     det = a * c - b * b
-    ok = in_front & (det != 0)
+    det_nonzero = (det != 0) if dec is None else dec["det_nonzero"]                      # Q3
+    ok = in_front & det_nonzero
     det_safe = torch.where(ok, det, torch.ones_like(det))
     conic = torch.stack([c / det_safe, -b / det_safe, a / det_safe], dim=1)
     mid = 0.5 * (a + c)
@@ -176,6 +193,8 @@ def preprocess(means3D, opacities, view, *, scales=None, rotations=None, cov3D_p
     rmin_y = tile_lo(pyd - radius, gy)
     rmax_x = tile_lo(pxd + radius + TILE - 1, gx)
     rmax_y = tile_lo(pyd + radius + TILE - 1, gy)
+    if dec is not None:                                                                  # Q5
+        rmin_x, rmin_y, rmax_x, rmax_y = (r.to(dt) for r in dec["rect"])
     area = (rmax_x - rmin_x) * (rmax_y - rmin_y)
 
     # --- MS-GS pixel size + filters ---
@@ -183,7 +202,8 @@ def preprocess(means3D, opacities, view, *, scales=None, rotations=None, cov3D_p
     ell = 2.0 * torch.log(torch.clamp_min(255.0 * o.detach(), 1e-300))
     qx = conic[:, 0].detach()
     qz = conic[:, 2].detach()
-    size = torch.where((ell > 0) & ok & (qx > 0) & (qz > 0),
+    gate = (255.0 * o.detach() > 1.0) if dec is None else dec["gate"]                    # M1
+    size = torch.where(gate & ok & (qx > 0) & (qz > 0),
                        torch.minimum(2.0 * torch.sqrt(ell.clamp_min(0) / qx.clamp_min(1e-300)),
                                      2.0 * torch.sqrt(ell.clamp_min(0) / qz.clamp_min(1e-300))),
                        torch.zeros_like(ell))
@@ -227,7 +247,8 @@ def preprocess(means3D, opacities, view, *, scales=None, rotations=None, cov3D_p
     return dict(visible=visible, depth32=depth32, depth=tz, px=px, py=py, conic=conic, opacity=o_eff,
                 rgb=rgb, clamped=clamped, radii=radii, pixel_sizes=pixel_sizes,
                 rect=(rmin_x.long(), rmin_y.long(), rmax_x.long(), rmax_y.long()),
-                cov3D=cov3D, cov2=(a, b, c))
+                cov3D=cov3D, cov2=(a, b, c), det_nonzero=det_nonzero, gate=gate,
+                clamped_x=cx, clamped_y=cy)
 
 
 def rasterize(means3D, opacities, view, bg, **kw):
