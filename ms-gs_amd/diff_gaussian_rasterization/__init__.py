@@ -260,12 +260,13 @@ def _alloc_grad_records(ctx, P, dev):
 def _take_backward_scratch(ctx, P, D, dev, depth=False):
     """(scratch, is_clear): the buffer the forward cleared, once; any later backward through the same graph
     (retain_graph) gets a fresh one that msgs_backward clears itself"""
-    if bool(_C.lib.msgs_get_deterministic()) != bool(getattr(ctx, "det", False)):
+    det = bool(_C.lib.msgs_get_deterministic())
+    if det != bool(getattr(ctx, "det", False)):
         raise RuntimeError("diff_gaussian_rasterization: set_deterministic() changed between this forward and its backward (the "
                            "verification mode's backward reads what its own forward left behind)")
     rec = getattr(ctx, "grad_rec", None)
     ctx.grad_rec = None
-    if rec is not None and not _C.lib.msgs_get_deterministic():
+    if rec is not None and not det:
         return rec, 1
     return _backward_scratch(P, D, dev, depth), 0
 
@@ -425,31 +426,31 @@ _MEDIAN = _MedianMarker()
 def _extra_inputs(rs, return_alpha=False, absgrad=False, means2D=None, features=None, model=None, return_distortion=False,
                   return_median_depth=False):
     """model: the call's means3D / xyz (its rows and device check `features`)"""
-    if absgrad and _C.lib.msgs_get_deterministic():
-        raise ValueError("absgrad=True is not offered in the verification mode (set_deterministic): that mode checks the "
-                         "gradients, it does not train")
-    if return_distortion and _C.lib.msgs_get_deterministic():
-        raise ValueError("return_distortion=True is not offered in the verification mode (set_deterministic): that mode "
-                         "checks the gradients of the reference's outputs")
-    if return_median_depth and _C.lib.msgs_get_deterministic():
-        raise ValueError("return_median_depth=True is not offered in the verification mode (set_deterministic): that mode "
-                         "checks the gradients of the reference's outputs")
+    if (absgrad or return_distortion or return_median_depth) and _C.lib.msgs_get_deterministic():
+        for flag, message in ((absgrad, "absgrad=True is not offered in the verification mode (set_deterministic): that mode "
+                                        "checks the gradients, it does not train"),
+                              (return_distortion, "return_distortion=True is not offered in the verification mode "
+                                                  "(set_deterministic): that mode checks the gradients of the reference's outputs"),
+                              (return_median_depth, "return_median_depth=True is not offered in the verification mode "
+                                                    "(set_deterministic): that mode checks the gradients of the reference's outputs")):
+            if flag:
+                raise ValueError(message)
     if features is not None:
         features = _check_features(features, int(model.shape[0]), model.device)
-    extra = _camera_inputs(rs)
+    extra = list(_camera_inputs(rs))
     if torch.is_grad_enabled() and torch.is_tensor(rs.bg) and rs.bg.requires_grad:
-        extra = tuple(extra) + (rs.bg,)
+        extra.append(rs.bg)
     if return_alpha:
-        extra = tuple(extra) + (_ALPHA,)
+        extra.append(_ALPHA)
     if absgrad:
-        extra = tuple(extra) + (_AbsgradMarker(means2D),)
+        extra.append(_AbsgradMarker(means2D))
     if return_distortion:
-        extra = tuple(extra) + (_DISTORTION,)
+        extra.append(_DISTORTION)
     if return_median_depth:
-        extra = tuple(extra) + (_MEDIAN,)
+        extra.append(_MEDIAN)
     if features is not None:
-        extra = tuple(extra) + (_FEATURES, features)
-    return extra
+        extra += (_FEATURES, features)
+    return tuple(extra)
 
 
 def _note_extra(ctx, extra):
@@ -487,6 +488,27 @@ def _note_extra(ctx, extra):
     return camera, alpha
 
 
+def _replay_args(call, P, geom, binning, image, D):
+    """the nine leading arguments of every replay of a forward's state (include/msgs.h: msgs_absgrad, msgs_features_*,
+    msgs_distortion_*, msgs_median_depth_forward, msgs_contrib_accumulate): the view, P, then geom, binning and image state with
+    their byte counts, the instance count D behind geom's"""
+    return (call.view_ref, P, _ptr(geom), geom.numel(), D, _ptr(binning), binning.numel() if binning is not None else 0,
+            _ptr(image), image.numel())
+
+
+def _replay_forward(name, probe, call, state, *tail):
+    """what the three *_forward replays share: the state resolved (a deferred forward first waits for its instance count: correct,
+    at the price of that view's overlap), the tests' probe, then lib.`name`(replay arguments, *tail, stream) on the current
+    stream of the call's device, behind the forward that left `state`"""
+    geom, binning, image, D = _resolve(state)
+    dev = call.device
+    if probe is not None:
+        probe(name)
+    with _on_device(dev):
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _C.check(getattr(_C.lib, name)(*_replay_args(call, call.P, geom, binning, image, D), *tail, stream), name)
+
+
 def _absgrad(ctx, call, geom, binning, image, D, dL, dLd, dLa, dev, stream):
     """backward of an absgrad=True call: msgs_absgrad on the backward's stream, the result assigned to means2D.absgrad"""
     m2 = ctx.absgrad.means2D()
@@ -495,9 +517,8 @@ def _absgrad(ctx, call, geom, binning, image, D, dL, dLd, dLa, dev, stream):
     P = call.P
     out = torch.empty(P, 3, dtype=torch.float32, device=dev)
     scratch = _bytes(_C.lib.msgs_absgrad_scratch_bytes(P), dev)
-    _C.check(_C.lib.msgs_absgrad(call.view_ref, P, _ptr(geom), geom.numel(), D, _ptr(binning), binning.numel(), _ptr(image),
-                                 image.numel(), _ptr(dL), _ptr(dLd), _ptr(dLa), _ptr(scratch), scratch.numel(), _ptr(out), stream),
-             "msgs_absgrad")
+    _C.check(_C.lib.msgs_absgrad(*_replay_args(call, P, geom, binning, image, D), _ptr(dL), _ptr(dLd), _ptr(dLa), _ptr(scratch),
+                                 scratch.numel(), _ptr(out), stream), "msgs_absgrad")
     m2.absgrad = out.view(m2.shape) if out.shape != m2.shape and out.numel() == m2.numel() else out
 
 
@@ -544,16 +565,9 @@ def _features_forward(ctx, call, state):
     """the feature map [C,H,W] of a call with features: msgs_features_forward on the current stream, behind the forward that
     left `state`.  A deferred forward is resolved first (the replay needs the instance count): correct, at the price of that
     view's overlap."""
-    geom, binning, image, D = _resolve(state)
-    dev, P, Cn = call.device, call.P, int(ctx.feat.shape[1])
-    if _features_probe is not None:
-        _features_probe("msgs_features_forward")
-    with _on_device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        out = torch.empty(Cn, call.H, call.W, dtype=torch.float32, device=dev)
-        _C.check(_C.lib.msgs_features_forward(call.view_ref, P, _ptr(geom), geom.numel(), D, _ptr(binning),
-                                              binning.numel() if binning is not None else 0, _ptr(image), image.numel(),
-                                              _ptr(ctx.feat), Cn, _ptr(out), stream), "msgs_features_forward")
+    Cn = int(ctx.feat.shape[1])
+    out = torch.empty(Cn, call.H, call.W, dtype=torch.float32, device=call.device)
+    _replay_forward("msgs_features_forward", _features_probe, call, state, _ptr(ctx.feat), Cn, _ptr(out))
     return out
 
 
@@ -572,11 +586,9 @@ def _features_backward(ctx, call, geom, binning, image, D, grad_features, scratc
     acc = _bytes(lib.msgs_features_scratch_bytes(P, Cn), dev)
     if _features_probe is not None:
         _features_probe("msgs_features_backward")
-    _C.check(lib.msgs_features_backward(call.view_ref, P, _ptr(geom), geom.numel(), D, _ptr(binning),
-                                        binning.numel() if binning is not None else 0, _ptr(image), image.numel(),
-                                        _ptr(ctx.feat), Cn, _ptr(G), _ptr(scratch) if geom_share else None,
-                                        scratch.numel() if geom_share else 0, _ptr(acc), acc.numel(), _ptr(out), stream),
-             "msgs_features_backward")
+    _C.check(lib.msgs_features_backward(*_replay_args(call, P, geom, binning, image, D), _ptr(ctx.feat), Cn, _ptr(G),
+                                        _ptr(scratch) if geom_share else None, scratch.numel() if geom_share else 0, _ptr(acc),
+                                        acc.numel(), _ptr(out), stream), "msgs_features_backward")
     ctx.g_features = out
     return 1 if geom_share else is_clear
 
@@ -588,17 +600,9 @@ def _distortion_forward(ctx, call, state):
     """the distortion map [H,W] of a return_distortion=True call: msgs_distortion_forward on the current stream, behind the
     forward that left `state`; the moment map the backward needs stays on ctx.  A deferred forward is resolved first (the replay
     needs the instance count): correct, at the price of that view's overlap."""
-    geom, binning, image, D = _resolve(state)
-    dev, P = call.device, call.P
-    if _distortion_probe is not None:
-        _distortion_probe("msgs_distortion_forward")
-    with _on_device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        out = torch.empty(call.H, call.W, dtype=torch.float32, device=dev)
-        ctx.dist_moment = torch.empty(call.H, call.W, dtype=torch.float32, device=dev)
-        _C.check(_C.lib.msgs_distortion_forward(call.view_ref, P, _ptr(geom), geom.numel(), D, _ptr(binning),
-                                                binning.numel() if binning is not None else 0, _ptr(image), image.numel(),
-                                                _ptr(out), _ptr(ctx.dist_moment), stream), "msgs_distortion_forward")
+    out = torch.empty(call.H, call.W, dtype=torch.float32, device=call.device)
+    ctx.dist_moment = torch.empty_like(out)
+    _replay_forward("msgs_distortion_forward", _distortion_probe, call, state, _ptr(out), _ptr(ctx.dist_moment))
     return out
 
 
@@ -611,10 +615,9 @@ def _distortion_backward(ctx, call, geom, binning, image, D, grad_distortion, dL
         scratch.zero_()
     if _distortion_probe is not None:
         _distortion_probe("msgs_distortion_backward")
-    _C.check(_C.lib.msgs_distortion_backward(call.view_ref, call.P, _ptr(geom), geom.numel(), D, _ptr(binning),
-                                             binning.numel() if binning is not None else 0, _ptr(image), image.numel(),
-                                             _ptr(ctx.dist_moment), _ptr(_f32c(grad_distortion)), _ptr(scratch), scratch.numel(),
-                                             stream), "msgs_distortion_backward")
+    _C.check(_C.lib.msgs_distortion_backward(*_replay_args(call, call.P, geom, binning, image, D), _ptr(ctx.dist_moment),
+                                             _ptr(_f32c(grad_distortion)), _ptr(scratch), scratch.numel(), stream),
+             "msgs_distortion_backward")
     if dLd is None:
         dLd = torch.zeros(call.H, call.W, dtype=torch.float32, device=dev)
     return dLd, 1
@@ -627,18 +630,9 @@ def _median_depth_forward(ctx, call, state):
     """(median_depth [H,W] float32, median_id [H,W] int32) of a return_median_depth=True call: msgs_median_depth_forward on the
     current stream, behind the forward that left `state`; the id map stays on ctx for the backward.  A deferred forward is
     resolved first (the replay needs the instance count): correct, at the price of that view's overlap."""
-    geom, binning, image, D = _resolve(state)
-    dev, P = call.device, call.P
-    if _median_probe is not None:
-        _median_probe("msgs_median_depth_forward")
-    with _on_device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        out = torch.empty(call.H, call.W, dtype=torch.float32, device=dev)
-        ids = torch.empty(call.H, call.W, dtype=torch.int32, device=dev)
-        _C.check(_C.lib.msgs_median_depth_forward(call.view_ref, P, _ptr(geom), geom.numel(), D, _ptr(binning),
-                                                  binning.numel() if binning is not None else 0, _ptr(image), image.numel(),
-                                                  _ptr(out), _ptr(ids), stream), "msgs_median_depth_forward")
-    ctx.median_id = ids
+    out = torch.empty(call.H, call.W, dtype=torch.float32, device=call.device)
+    ctx.median_id = ids = torch.empty(call.H, call.W, dtype=torch.int32, device=call.device)
+    _replay_forward("msgs_median_depth_forward", _median_probe, call, state, _ptr(out), _ptr(ids))
     return out, ids
 
 
@@ -1117,6 +1111,64 @@ def _forward_tail(ctx, call, state, outs, geometry=(0, 1, 4, 5, 6)):
     return tuple(outs)
 
 
+def _backward_body(ctx, grad_color, grad_depth, grad_tail, destinations, after_main=None):
+    """What every backward of the op runs, in the one order its launches take on the stream: the backward scratch, the entry's
+    `destinations(ctx, call, scratch_is_clear) -> (_C.Grads, dest)` (where the leaf gradients go: fresh tensors, sinks, the
+    accumulator or the Adam step; `dest` is whatever the entry wants back, kept alive across the launches), the camera outputs,
+    the pre-passes of the opt-in maps the loss used — features, distortion, median depth, each adding to the gradient records and
+    handing dL/ddepth and scratch_is_clear on — the main backward, the entry's `after_main(ctx, dest)`, dL/dbg, absgrad and the
+    gradients of the trailing inputs.  Returns (dest, those gradients).  A further opt-in map is added HERE, once.
+    (The two callbacks are plain functions, not closures made per call: this runs between the forward's host synchronisation
+    and the backward's first launch, where host time shows in the step.)"""
+    grad_alpha, grad_distortion, grad_median, grad_features = _split_grad_tail(ctx, grad_tail)
+    _check_saved(ctx)
+    call = ctx.call
+    if grad_color is None:
+        grad_color = torch.zeros(3, call.H, call.W, dtype=torch.float32, device=call.device)
+    geom, binning, image, D = _resolve(ctx.state)
+    dev, P = call.device, call.P
+    with _on_device(dev):
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        dL = _f32c(grad_color)
+        dLd = _f32c(grad_depth) if grad_depth is not None else None
+        dLa = _f32c(grad_alpha) if grad_alpha is not None else None
+        scratch, is_clear = _take_backward_scratch(ctx, P, D, dev, dLd is not None or grad_distortion is not None or
+                                                   grad_median is not None)
+        grads, dest = destinations(ctx, call, is_clear)
+        cam = _CameraGrads(ctx, P, dev) if ctx.camera else None
+        dLd_loss = dLd                                          # (what the loss itself sent to the depth map: absgrad's input)
+        if grad_features is not None:
+            grads.scratch_is_clear = _features_backward(ctx, call, geom, binning, image, D, grad_features, scratch, is_clear,
+                                                        dev, stream)
+        if grad_distortion is not None:
+            dLd, grads.scratch_is_clear = _distortion_backward(ctx, call, geom, binning, image, D, grad_distortion, dLd, scratch,
+                                                               grads.scratch_is_clear, dev, stream)
+        if grad_median is not None:
+            dLd, grads.scratch_is_clear = _median_depth_backward(ctx, call, D, grad_median, dLd, scratch,
+                                                                 grads.scratch_is_clear, dev, stream)
+        _run_backward(_C.lib, call, ctx, geom, binning, image, D, dL, dLd, dLa, scratch, grads, stream, cam)
+        if after_main is not None:
+            after_main(ctx, dest)
+        g_bg = _bg_grad(ctx, call.view_ref, image, dL, call.W, call.H, dev, stream) if ctx.bg is not None else None
+        if ctx.absgrad is not None:
+            _absgrad(ctx, call, geom, binning, image, D, dL, dLd_loss, dLa, dev, stream)
+    return dest, _extra_grads(ctx, cam.grads(ctx) if cam is not None else (), g_bg)
+
+
+def _fresh_destinations(ctx, call, is_clear):
+    """_RasterizeGaussians.backward: fresh tensors, in the order of msgs_grads_t — means3D, means2D, sh, colours, opacity, scales,
+    rotations, cov3D"""
+    P, dev, f32 = call.P, call.device, torch.float32
+    g = (torch.empty(P, 3, dtype=f32, device=dev), torch.empty(P, 3, dtype=f32, device=dev),
+         torch.empty(P, call.K, 3, dtype=f32, device=dev) if call.sh is not None else None,
+         torch.empty(P, 3, dtype=f32, device=dev) if call.colors is not None else None,
+         torch.empty(P, dtype=f32, device=dev),
+         torch.empty(P, 3, dtype=f32, device=dev) if call.scales is not None else None,
+         torch.empty(P, 4, dtype=f32, device=dev) if call.rot is not None else None,
+         torch.empty(P, 6, dtype=f32, device=dev) if call.cov is not None else None)
+    return _C.Grads(*map(_ptr, g), None, None, None, is_clear), g
+
+
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
@@ -1139,18 +1191,17 @@ class _RasterizeGaussians(torch.autograd.Function):
             outs = (color, torch.zeros(H, W, device=dev), torch.zeros(H, W, device=dev),
                     torch.zeros(0, dtype=torch.int32, device=dev), torch.zeros(0, device=dev))
             non_diff = (outs[1],) + outs[3:]                    # (depth stays differentiable: zero gradients)
-            if want_alpha:                                      # (nothing blended: alpha 0, zero gradients)
-                outs = outs + (torch.zeros(H, W, device=dev),)
-            if ctx.distortion:                                  # (nothing blended: no pair, zero gradients)
-                outs = outs + (torch.zeros(H, W, device=dev),)
-            if ctx.median:                                      # (nothing blended: depth 0, id -1, zero gradients)
-                outs = outs + (torch.zeros(H, W, device=dev), torch.full((H, W), -1, dtype=torch.int32, device=dev))
-                non_diff += (outs[-1],)
+            # nothing blended, in the order of _forward_tail: alpha 0, no distortion pair, median depth 0 — [H,W] zeros — then
+            # median id -1 and a zero feature map; zero gradients throughout
+            extra = [torch.zeros(H, W, device=dev) for _ in range(int(want_alpha) + int(ctx.distortion) + int(ctx.median))]
+            if ctx.median:
+                extra.append(torch.full((H, W), -1, dtype=torch.int32, device=dev))
+                non_diff += (extra[-1],)
+            if ctx.features is not None:
+                extra.append(torch.zeros(int(ctx.features.shape[1]), H, W, device=dev))
             ctx.mark_non_differentiable(*non_diff)
-            if ctx.features is not None:                        # (nothing blended: a zero map, zero gradients)
-                outs = outs + (torch.zeros(int(ctx.features.shape[1]), H, W, device=dev),)
             ctx.set_materialize_grads(False)
-            return outs
+            return outs + tuple(extra)
         ctx.empty = False
         call = _Call(raster_settings, means3D, _opt(sh), _opt(colors_precomp), opacities, _opt(scales),
                      _opt(rotations), _opt(cov3Ds_precomp), _opt(max_pixel_sizes), _opt(min_pixel_sizes),
@@ -1162,8 +1213,8 @@ class _RasterizeGaussians(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_color, grad_acc_ps, grad_depth, grad_radii, grad_pixel_sizes, *grad_tail):
-        grad_alpha, grad_distortion, grad_median, grad_features = _split_grad_tail(ctx, grad_tail)
         if ctx.empty:
+            grad_features = _split_grad_tail(ctx, grad_tail)[3]
             cam = tuple(None if m is None else torch.zeros(m[0], dtype=m[1], device=m[2]) for m in ctx.camera)
             g_bg = None
             if ctx.bg is not None:          # the image is the background: dL/dbg_c = sum_p dL/dC_{c,p} (final_T = 1)
@@ -1180,50 +1231,13 @@ class _RasterizeGaussians(torch.autograd.Function):
             if grad_features is not None:
                 ctx.g_features = torch.zeros(ctx.features.shape, dtype=torch.float32, device=ctx.dev)
             return tuple(torch.zeros(s, device=ctx.dev) for s in ctx.in_shapes) + (None,) * 6 + _extra_grads(ctx, cam, g_bg)
-        _check_saved(ctx)
-        call = ctx.call
-        if grad_color is None:
-            grad_color = torch.zeros(3, call.H, call.W, dtype=torch.float32, device=call.device)
-        geom, binning, image, D = _resolve(ctx.state)
-        dev, P, K = call.device, call.P, call.K
-        lib = _C.lib
-        with _on_device(dev):
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            dL = _f32c(grad_color)
-            g_means3D = torch.empty(P, 3, dtype=torch.float32, device=dev)
-            g_means2D = torch.empty(P, 3, dtype=torch.float32, device=dev)
-            g_opac = torch.empty(P, dtype=torch.float32, device=dev)
-            g_sh = torch.empty(P, K, 3, dtype=torch.float32, device=dev) if call.sh is not None else None
-            g_col = torch.empty(P, 3, dtype=torch.float32, device=dev) if call.colors is not None else None
-            g_scales = torch.empty(P, 3, dtype=torch.float32, device=dev) if call.scales is not None else None
-            g_rot = torch.empty(P, 4, dtype=torch.float32, device=dev) if call.rot is not None else None
-            g_cov = torch.empty(P, 6, dtype=torch.float32, device=dev) if call.cov is not None else None
-            dLd = _f32c(grad_depth) if grad_depth is not None else None
-            scratch, is_clear = _take_backward_scratch(ctx, P, D, dev, dLd is not None or grad_distortion is not None or
-                                                       grad_median is not None)
-            dLd_loss = dLd                                      # (what the loss itself sent to the depth map: absgrad's input)
-            grads = _C.Grads(_ptr(g_means3D), _ptr(g_means2D), _ptr(g_sh), _ptr(g_col), _ptr(g_opac),
-                             _ptr(g_scales), _ptr(g_rot), _ptr(g_cov), None, None, None, is_clear)
-            cam = _CameraGrads(ctx, P, dev) if ctx.camera else None
-            dLa = _f32c(grad_alpha) if grad_alpha is not None else None
-            if grad_features is not None:
-                grads.scratch_is_clear = _features_backward(ctx, call, geom, binning, image, D, grad_features, scratch, is_clear,
-                                                            dev, stream)
-            if grad_distortion is not None:
-                dLd, grads.scratch_is_clear = _distortion_backward(ctx, call, geom, binning, image, D, grad_distortion, dLd, scratch,
-                                                                   grads.scratch_is_clear, dev, stream)
-            if grad_median is not None:
-                dLd, grads.scratch_is_clear = _median_depth_backward(ctx, call, D, grad_median, dLd, scratch,
-                                                                     grads.scratch_is_clear, dev, stream)
-            _run_backward(lib, call, ctx, geom, binning, image, D, dL, dLd, dLa, scratch, grads, stream, cam)
-            g_bg = _bg_grad(ctx, call.view_ref, image, dL, call.W, call.H, dev, stream) if ctx.bg is not None else None
-            if ctx.absgrad is not None:
-                _absgrad(ctx, call, geom, binning, image, D, dL, dLd_loss, dLa, dev, stream)
+        g, g_extra = _backward_body(ctx, grad_color, grad_depth, grad_tail, _fresh_destinations)
+        g_means3D, g_means2D, g_sh, g_col, g_opac, g_scales, g_rot, g_cov = g
         m2_shape, op_shape = ctx.shapes
         # occ_multiplier / dc_delta / pixel-size inputs / masks receive no gradient (DESIGN.md SPEC M5)
         return (g_means3D, g_means2D.view(m2_shape) if g_means2D.shape == m2_shape else g_means2D,
                 g_sh, g_col, g_opac.view(op_shape), g_scales, g_rot, g_cov,
-                None, None, None, None, None, None) + _extra_grads(ctx, cam.grads(ctx) if cam is not None else (), g_bg)
+                None, None, None, None, None, None) + g_extra
 
 
 # Gradient sinks (view-parallel training): a trainer that exchanges gradients through one flat bucket registers, per leaf
@@ -1404,6 +1418,54 @@ def _grad_out(hit, shape, dev):
     return torch.empty(shape, dtype=torch.float32, device=dev)
 
 
+def _leaf_destinations(ctx, call, is_clear):
+    """_RasterizeGaussiansRaw.backward: where the six leaf gradients go — consumed by the Adam step, into the accumulator, or
+    into sinks / fresh tensors.  dest = (dL/dmeans2D, the six gradients autograd is handed (None where they live in the
+    accumulator or were consumed by the step), the Adam table or None)"""
+    dev, P = call.device, call.P
+    dc_shape, rest_shape, op_shape = ctx.shapes[1:]
+    g_m2 = torch.empty(P, 3, dtype=torch.float32, device=dev)
+    factor, ready = ctx.sh_factor
+    if factor is not None and (factor.device != dev or factor.shape[0] != P):
+        raise ValueError("sh_factor sink does not match this model (device / number of Gaussians)")
+    accum = getattr(ctx, "accum", None)
+    step_opt = getattr(ctx, "step_opt", None)
+    acc_flag, ev_wait, ev_rec = 0, None, None
+    adam = g_xyz = g_dc = g_rest = g_opac = g_scal = g_rot = None
+    if step_opt is not None:
+        if accum is not None or factor is not None:
+            raise ValueError("set_optimizer_in_backward cannot be combined with a GradAccumulator or the factored SH gradient")
+        if call.view.sh_coeffs != 16:
+            raise ValueError("set_optimizer_in_backward needs 16 SH coefficients per Gaussian")
+        adam = step_opt.take_step_in_backward(ctx.leaves)        # (a _C.AdamInBackward; keeps its tensors alive itself)
+    elif accum is not None:
+        if factor is not None:
+            raise ValueError("GradAccumulator and the factored SH gradient cannot be combined")
+        (g_xyz, g_dc, g_rest, g_opac, g_scal, g_rot), acc, wait, rec = accum._take(ctx.leaves)
+        acc_flag = 1 if acc else 0
+        ev_wait = C.c_void_p(wait.cuda_event) if wait is not None else None
+        ev_rec = C.c_void_p(rec.cuda_event)
+    else:
+        kx, kdc, krest, kop, ksc, krot = ctx.sinks
+        g_xyz = _grad_out(kx, (P, 3), dev)
+        if factor is None:
+            g_dc, g_rest = _grad_out(kdc, dc_shape, dev), _grad_out(krest, rest_shape, dev)
+        g_opac, g_scal, g_rot = _grad_out(kop, op_shape, dev), _grad_out(ksc, (P, 3), dev), _grad_out(krot, (P, 4), dev)
+    grads = _C.Grads(_ptr(g_xyz), _ptr(g_m2), None, _ptr(factor), _ptr(g_opac), _ptr(g_scal), _ptr(g_rot), None,
+                     _ptr(g_dc), _ptr(g_rest),
+                     C.c_void_p(ready.cuda_event) if (factor is not None and ready is not None) else None,
+                     is_clear, acc_flag, ev_wait, ev_rec, C.addressof(adam) if adam is not None else None)
+    if accum is not None or adam is not None:
+        return grads, (g_m2, (None,) * 6, adam)
+    return grads, (g_m2, (g_xyz, g_dc, g_rest, g_opac, g_scal, g_rot), None)
+
+
+def _commit_step(ctx, dest):
+    """behind the main backward of the raw entry: the kernel that takes the Adam step has been launched"""
+    if dest[2] is not None:
+        ctx.step_opt.commit_step_in_backward(ctx.leaves)
+
+
 class _RasterizeGaussiansRaw(torch.autograd.Function):
     """Opt-in fused entry: takes the RAW GaussianModel parameters
     (/root/reference/scene/gaussian_model.py:53-58: _xyz, _features_dc, _features_rest, _opacity, _scaling, _rotation);
@@ -1428,76 +1490,8 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_color, grad_acc_ps, grad_depth, grad_radii, grad_pixel_sizes, *grad_tail):
-        grad_alpha, grad_distortion, grad_median, grad_features = _split_grad_tail(ctx, grad_tail)
-        _check_saved(ctx)
-        call = ctx.call
-        if grad_color is None:
-            grad_color = torch.zeros(3, call.H, call.W, dtype=torch.float32, device=call.device)
-        geom, binning, image, D = _resolve(ctx.state)
-        dev, P = call.device, call.P
-        lib = _C.lib
-        m2_shape, dc_shape, rest_shape, op_shape = ctx.shapes
-        with _on_device(dev):
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            dL = _f32c(grad_color)
-            kx, kdc, krest, kop, ksc, krot = ctx.sinks
-            g_m2 = torch.empty(P, 3, dtype=torch.float32, device=dev)
-            factor, ready = ctx.sh_factor
-            if factor is not None and (factor.device != dev or factor.shape[0] != P):
-                raise ValueError("sh_factor sink does not match this model (device / number of Gaussians)")
-            accum = getattr(ctx, "accum", None)
-            step_opt = getattr(ctx, "step_opt", None)
-            acc_flag, ev_wait, ev_rec = 0, None, None
-            adam = None
-            if step_opt is not None:
-                if accum is not None or factor is not None:
-                    raise ValueError("set_optimizer_in_backward cannot be combined with a GradAccumulator or the factored SH gradient")
-                if call.view.sh_coeffs != 16:
-                    raise ValueError("set_optimizer_in_backward needs 16 SH coefficients per Gaussian")
-                adam = step_opt.take_step_in_backward(ctx.leaves)        # (a _C.AdamInBackward; keeps its tensors alive itself)
-                g_xyz = g_dc = g_rest = g_opac = g_scal = g_rot = None
-            elif accum is not None:
-                if factor is not None:
-                    raise ValueError("GradAccumulator and the factored SH gradient cannot be combined")
-                (g_xyz, g_dc, g_rest, g_opac, g_scal, g_rot), acc, wait, rec = accum._take(ctx.leaves)
-                acc_flag = 1 if acc else 0
-                ev_wait = C.c_void_p(wait.cuda_event) if wait is not None else None
-                ev_rec = C.c_void_p(rec.cuda_event)
-            else:
-                g_xyz = _grad_out(kx, (P, 3), dev)
-                g_dc = g_rest = None
-                if factor is None:
-                    g_dc, g_rest = _grad_out(kdc, dc_shape, dev), _grad_out(krest, rest_shape, dev)
-                g_opac, g_scal, g_rot = _grad_out(kop, op_shape, dev), _grad_out(ksc, (P, 3), dev), _grad_out(krot, (P, 4), dev)
-            dLd = _f32c(grad_depth) if grad_depth is not None else None
-            scratch, is_clear = _take_backward_scratch(ctx, P, D, dev, dLd is not None or grad_distortion is not None or
-                                                       grad_median is not None)
-            dLd_loss = dLd                                      # (what the loss itself sent to the depth map: absgrad's input)
-            grads = _C.Grads(_ptr(g_xyz), _ptr(g_m2), None, _ptr(factor), _ptr(g_opac), _ptr(g_scal), _ptr(g_rot), None,
-                             _ptr(g_dc), _ptr(g_rest),
-                             C.c_void_p(ready.cuda_event) if (factor is not None and ready is not None) else None,
-                             is_clear, acc_flag, ev_wait, ev_rec, C.addressof(adam) if adam is not None else None)
-            cam = _CameraGrads(ctx, P, dev) if ctx.camera else None
-            dLa = _f32c(grad_alpha) if grad_alpha is not None else None
-            if grad_features is not None:
-                grads.scratch_is_clear = _features_backward(ctx, call, geom, binning, image, D, grad_features, scratch, is_clear,
-                                                            dev, stream)
-            if grad_distortion is not None:
-                dLd, grads.scratch_is_clear = _distortion_backward(ctx, call, geom, binning, image, D, grad_distortion, dLd, scratch,
-                                                                   grads.scratch_is_clear, dev, stream)
-            if grad_median is not None:
-                dLd, grads.scratch_is_clear = _median_depth_backward(ctx, call, D, grad_median, dLd, scratch,
-                                                                     grads.scratch_is_clear, dev, stream)
-            _run_backward(lib, call, ctx, geom, binning, image, D, dL, dLd, dLa, scratch, grads, stream, cam)
-            if adam is not None:
-                step_opt.commit_step_in_backward(ctx.leaves)
-            g_bg = _bg_grad(ctx, call.view_ref, image, dL, call.W, call.H, dev, stream) if ctx.bg is not None else None
-            if ctx.absgrad is not None:
-                _absgrad(ctx, call, geom, binning, image, D, dL, dLd_loss, dLa, dev, stream)
-        g_cam = _extra_grads(ctx, cam.grads(ctx) if cam is not None else (), g_bg)
-        if accum is not None or adam is not None:   # the leaf gradients live in the accumulator / were consumed by the step
-            return (None, g_m2.view(m2_shape), None, None, None, None, None, None, None, None, None, None, None) + g_cam
-        return (g_xyz, g_m2.view(m2_shape), g_dc, g_rest, g_opac, g_scal, g_rot, None, None, None, None, None, None) + g_cam
+        (g_m2, leaf, _), g_extra = _backward_body(ctx, grad_color, grad_depth, grad_tail, _leaf_destinations, _commit_step)
+        return (leaf[0], g_m2.view(ctx.shapes[0])) + leaf[1:] + (None, None, None, None, None, None) + g_extra
 
 
 class _RasterizeGaussiansChained(torch.autograd.Function):
@@ -1637,14 +1631,6 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
                         max_pixel_sizes, min_pixel_sizes, occ_multiplier, dc_delta, base_mask, raster_settings,
                         features=None, return_median_depth=False, return_distortion=False, absgrad=False,
                         return_alpha=False):
-    """return_alpha=True: a sixth output, the alpha map [H,W] (1 - final transmittance), differentiable
-    absgrad=True: every backward also assigns means2D.absgrad.
-    features [P,C]: one more output at the END, the feature map [C,H,W], differentiable.
-    return_distortion=True: one more output behind alpha and in front of the feature map, the depth-distortion map [H,W],
-    differentiable.
-    return_median_depth=True: two more outputs behind the distortion map and in front of the feature map, median_depth [H,W]
-    float32 (differentiable w.r.t. the means and the camera) and median_id [H,W] int32.  All five by
-    keyword."""
     extra = _extra_inputs(raster_settings, return_alpha, absgrad, means2D, features, means3D, return_distortion,
                           return_median_depth)
     _note_grad_mode()
@@ -1652,6 +1638,9 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
                                      cov3Ds_precomp, max_pixel_sizes, min_pixel_sizes, occ_multiplier, dc_delta,
                                      base_mask, raster_settings,
                                      *extra)
+
+
+rasterize_gaussians.__doc__ = rasterize_gaussians_raw.__doc__         # the same five keywords, the same outputs
 
 
 # Antialiasing (4.14): the opacity compensation of Mip-Splatting's 2-D screen filter as a pre-pass.  An
@@ -2413,10 +2402,9 @@ class ContributionAccumulator:
         dev = self.device
         with _on_device(dev):
             stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            _C.check(_C.lib.msgs_contrib_accumulate(
-                call.view_ref, self.P, _ptr(geom), geom.numel(), D, _ptr(binning), binning.numel() if binning is not None else 0,
-                _ptr(image), image.numel(), _ptr(pixel_weights), _ptr(self.buf), self.nbytes, int(self.views == 0), stream),
-                "msgs_contrib_accumulate")
+            _C.check(_C.lib.msgs_contrib_accumulate(*_replay_args(call, self.P, geom, binning, image, D), _ptr(pixel_weights),
+                                                    _ptr(self.buf), self.nbytes, int(self.views == 0), stream),
+                     "msgs_contrib_accumulate")
         self.views += 1
 
     def scores(self):
@@ -2463,6 +2451,14 @@ class GaussianRasterizer(nn.Module):
         self.return_median_depth = False
         self.antialiasing = False
 
+    def _with(self, **flags):
+        """a new module like this one — the settings, return_alpha, absgrad and every flag that travels on the module — with
+        `flags` replaced: what the with_*() methods return"""
+        r = GaussianRasterizer(self.raster_settings, self.return_alpha, self.absgrad)
+        for name in ("features", "return_distortion", "return_median_depth", "antialiasing"):
+            setattr(r, name, flags.get(name, getattr(self, name)))
+        return r
+
     def with_antialiasing(self, on=True):
         """A rasterizer like this one whose forward / contributions / preprocess_only render ANTIALIASED: the opacity of every
         Gaussian is first multiplied by rho = sqrt(max(0.000025, det0 / det1)), the compensation of Mip-Splatting's 2-D screen
@@ -2475,12 +2471,7 @@ class GaussianRasterizer(nn.Module):
         backward of the reference's getters does not apply to o rho, their backward runs in autograd.  forward_raw() raises
         ValueError: the raw entry applies the sigmoid inside its kernels.
         (__init__ keeps its pinned parameters, so the flag travels on the module, as with_distortion() does.)"""
-        r = GaussianRasterizer(self.raster_settings, self.return_alpha, self.absgrad)
-        r.features = self.features
-        r.return_distortion = self.return_distortion
-        r.return_median_depth = self.return_median_depth
-        r.antialiasing = bool(on)
-        return r
+        return self._with(antialiasing=bool(on))
 
     def _opacities(self, means3D, opacities, scales, rotations, cov3D_precomp):
         """the opacities the rasterizer is fed: o rho under with_antialiasing(), else the caller's"""
@@ -2501,12 +2492,7 @@ class GaussianRasterizer(nn.Module):
         a call resolves its own view before the replay: correct, but that view's overlap is lost.  Not offered in the
         verification mode (set_deterministic): ValueError before any launch.
         (__init__ keeps its pinned parameters, so the flag travels on the module, as with_features() does.)"""
-        r = GaussianRasterizer(self.raster_settings, self.return_alpha, self.absgrad)
-        r.features = self.features
-        r.return_distortion = bool(return_distortion)
-        r.return_median_depth = self.return_median_depth
-        r.antialiasing = self.antialiasing
-        return r
+        return self._with(return_distortion=bool(return_distortion))
 
     def with_median_depth(self, on=True):
         """A rasterizer like this one whose forward / forward_raw also return two maps, behind alpha and the distortion map and
@@ -2527,12 +2513,7 @@ class GaussianRasterizer(nn.Module):
         view's overlap is lost.  Not offered in the verification mode (set_deterministic): ValueError before any launch
         (DESIGN.md 2, M15).
         (__init__ keeps its pinned parameters, so the flag travels on the module, as with_distortion() does.)"""
-        r = GaussianRasterizer(self.raster_settings, self.return_alpha, self.absgrad)
-        r.features = self.features
-        r.return_distortion = self.return_distortion
-        r.return_median_depth = bool(on)
-        r.antialiasing = self.antialiasing
-        return r
+        return self._with(return_median_depth=bool(on))
 
     def with_features(self, features):
         """A rasterizer like this one whose forward / forward_raw also splat `features` [P,C] (float32 device tensor, C >= 1;
@@ -2545,12 +2526,7 @@ class GaussianRasterizer(nn.Module):
         deferred_forward a call with features resolves its own view before the replay: correct, but that view's overlap is
         lost.  Not offered in the verification mode (set_deterministic): ValueError before any launch.
         (forward() keeps the reference's 13 parameters, so the tensor travels on the module.)"""
-        r = GaussianRasterizer(self.raster_settings, self.return_alpha, self.absgrad)
-        r.features = features
-        r.return_distortion = self.return_distortion
-        r.return_median_depth = self.return_median_depth
-        r.antialiasing = self.antialiasing
-        return r
+        return self._with(features=features)
 
     def markVisible(self, positions):
         """Boolean mask of points in front of the near plane (upstream markVisible; unused by the
