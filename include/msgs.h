@@ -1077,6 +1077,34 @@ int msgs_tsdf_count(const msgs_tsdf_volume_t* v, uint8_t* edge_mask, int32_t* ve
                     void* stream);
 int msgs_tsdf_emit(const msgs_tsdf_volume_t* v, const msgs_tsdf_mesh_t* m, void* stream);
 
+/* ---- k-means vector quantisation (DESIGN.md SPEC M21, 4.23) --------------------------------------------------------------------
+ * x [P,D] and codebook [K,D] float32, contiguous rows; 1 <= D <= MSGS_VQ_MAX_DIM, 1 <= K <= MSGS_VQ_MAX_CODES, 0 <= P < 2^31;
+ * anything else returns MSGS_ERR_INVALID_ARG and launches nothing.  Inputs are assumed finite and are not checked on the device.
+ *   msgs_vq_assign   n_k = float32(1/2 sum_d double(c_kd)^2) (double, ascending d, rounded once); s(i,k) the float32 chain
+ *                    s = n_k; for d = 0 .. D-1: s = fmaf(-x_id, c_kd, s) — what the f32 MFMA leaves in an accumulator preloaded
+ *                    with n_k; idx [P] int32: the smallest k of minimal score under strict < from (best = +inf, idx = 0), a NaN
+ *                    score never wins (a row whose every score is NaN or +inf gets 0); err [P] float32 or NULL: e = 0;
+ *                    for d: t = x_id - c_{idx,d}; e = fmaf(t, t, e), from the two rows, not from the score.
+ *   msgs_vq_update   the members of code k are the rows order[offsets[k] .. offsets[k+1]) (order [P] int64: the rows sorted by
+ *                    code, stable, so ascending within a code; offsets [K+1] int32, offsets[K] = P); chunk_offsets [K+1] int32 is
+ *                    the exclusive scan of ceil(members / MSGS_VQ_UPDATE_CHUNK).  Per code and column the double sums of
+ *                    double(w_i) double(x_id) and of double(w_i) (w [P] float32 >= 0, or NULL: 1) are taken in member order within
+ *                    chunks of MSGS_VQ_UPDATE_CHUNK consecutive members, the chunk partials are added in chunk order, and
+ *                    new_codebook[k] = float32(sum / mass), mass [K] double, count [K] int32.  A code of mass 0 copies its row
+ *                    of `codebook`; new_codebook may be codebook.  No atomics: the same bits whatever the launch geometry.
+ * scratch: msgs_vq_scratch_bytes(P, D, K) bytes (0 for unsupported sizes), 16-byte aligned, no clearing needed, for either call.
+ * Everything on `stream`, no synchronisation; P == 0 launches nothing in msgs_vq_assign. */
+#define MSGS_VQ_MAX_DIM 64
+#define MSGS_VQ_MAX_CODES 65536
+#define MSGS_VQ_CODE_CHUNK 64              /* codes per LDS chunk of the search (tests straddle it) */
+#define MSGS_VQ_UPDATE_CHUNK 256           /* members per partial sum of the update: part of the result's definition */
+size_t msgs_vq_scratch_bytes(int64_t P, int32_t D, int32_t K);
+int msgs_vq_assign(int64_t P, int32_t D, int32_t K, const float* x, const float* codebook, int32_t* idx, float* err,
+                   void* scratch, size_t scratch_bytes, void* stream);
+int msgs_vq_update(int64_t P, int32_t D, int32_t K, const float* x, const float* w, const int64_t* order, const int32_t* offsets,
+                   const int32_t* chunk_offsets, const float* codebook, float* new_codebook, double* mass, int32_t* count,
+                   void* scratch, size_t scratch_bytes, void* stream);
+
 /* ---- fused photometric loss ----------------------------------------------------------------
  * loss = (1 - lambda_dssim) * l1_loss(img, gt) + lambda_dssim * (1 - ssim(img, gt))   (/root/reference/train.py:209-211)
  * with l1_loss / ssim of /root/reference/utils/loss_utils.py:17-18,32-63 (window 11, sigma 1.5, zero padding, mean).

@@ -1612,6 +1612,39 @@ int msgs_tsdf_emit(const msgs_tsdf_volume_t* v, const msgs_tsdf_mesh_t* m, void*
     return MSGS_OK;
 }
 
+// ---- k-means vector quantisation (SPEC M21) ----
+static int vq_shape_ok(int64_t P, int32_t D, int32_t K) {
+    return P >= 0 && P < ((int64_t)1 << 31) && D >= 1 && D <= MSGS_VQ_MAX_DIM && K >= 1 && K <= MSGS_VQ_MAX_CODES;
+}
+
+size_t msgs_vq_scratch_bytes(int64_t P, int32_t D, int32_t K) {
+    if (!vq_shape_ok(P, D, K)) return 0;
+    const size_t a = vq_assign_scratch_bytes(D, K), u = vq_update_scratch_bytes(P, D, K);
+    return a > u ? a : u;
+}
+
+int msgs_vq_assign(int64_t P, int32_t D, int32_t K, const float* x, const float* codebook, int32_t* idx, float* err,
+                   void* scratch, size_t scratch_bytes, void* stream) {
+    if (!vq_shape_ok(P, D, K) || !codebook) return MSGS_ERR_INVALID_ARG;
+    if (P == 0) return MSGS_OK;
+    if (!x || !idx || !scratch || ((uintptr_t)scratch & 15)) return MSGS_ERR_INVALID_ARG;
+    if (scratch_bytes < vq_assign_scratch_bytes(D, K)) return MSGS_ERR_CAPACITY;
+    HIP_TRY(launch_vq_assign(P, D, K, x, codebook, idx, err, (char*)scratch, (hipStream_t)stream));
+    return MSGS_OK;
+}
+
+int msgs_vq_update(int64_t P, int32_t D, int32_t K, const float* x, const float* w, const int64_t* order, const int32_t* offsets,
+                   const int32_t* chunk_offsets, const float* codebook, float* new_codebook, double* mass, int32_t* count,
+                   void* scratch, size_t scratch_bytes, void* stream) {
+    if (!vq_shape_ok(P, D, K) || !offsets || !chunk_offsets || !codebook || !new_codebook || !mass || !count)
+        return MSGS_ERR_INVALID_ARG;
+    if ((P > 0 && (!x || !order)) || !scratch || ((uintptr_t)scratch & 15)) return MSGS_ERR_INVALID_ARG;
+    if (scratch_bytes < vq_update_scratch_bytes(P, D, K)) return MSGS_ERR_CAPACITY;
+    HIP_TRY(launch_vq_update(P, D, K, x, w, order, offsets, chunk_offsets, codebook, new_codebook, mass, count, (char*)scratch,
+                             (hipStream_t)stream));
+    return MSGS_OK;
+}
+
 static int loss_args_ok(const float* img, const float* gt, int32_t C, int32_t H, int32_t W, float lambda) {
     if (!img || !gt || C < 1 || H < 1 || W < 1 || !(lambda >= 0.f && lambda <= 1.f)) return MSGS_ERR_INVALID_ARG;
     if ((int64_t)C * H * W > (int64_t)1 << 31 || C > 65535) return MSGS_ERR_TOO_MANY;

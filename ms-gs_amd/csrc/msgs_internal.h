@@ -940,6 +940,15 @@ hipError_t launch_tsdf_integrate(const msgs_tsdf_volume_t& v, const msgs_tsdf_fr
 hipError_t launch_tsdf_count(const msgs_tsdf_volume_t& v, uint8_t* edge_mask, int32_t* vertex_count, int32_t* triangle_count,
                              hipStream_t s);
 hipError_t launch_tsdf_emit(const msgs_tsdf_volume_t& v, const msgs_tsdf_mesh_t& m, hipStream_t s);
+// vq.hip — msgs_vq_* (SPEC M21): the nearest-code search on the f32 MFMA (norms and chunk records, then the fused argmin) and the
+// chunk-ordered centroid update (the arguments are checked in api.hip)
+size_t vq_assign_scratch_bytes(int D, int K);
+size_t vq_update_scratch_bytes(int64_t P, int D, int K);
+hipError_t launch_vq_assign(int64_t P, int D, int K, const float* x, const float* codebook, int32_t* idx, float* err, char* scratch,
+                            hipStream_t s);
+hipError_t launch_vq_update(int64_t P, int D, int K, const float* x, const float* w, const int64_t* order, const int32_t* offsets,
+                            const int32_t* chunk_offsets, const float* codebook, float* new_codebook, double* mass, int32_t* count,
+                            char* scratch, hipStream_t s);
 // heaviest-first launch order of the one-wave-per-tile backward from the forward's per-tile traversal lengths
 hipError_t launch_tile_order(const ViewParams& vp, const uint32_t* tile_last, uint32_t* tile_order, hipStream_t s);
 hipError_t launch_blend_lane_stats(const ViewParams& vp, const char* geom, const uint32_t* ids, const uint2* ranges,

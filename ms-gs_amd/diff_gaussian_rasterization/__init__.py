@@ -33,7 +33,7 @@ __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gau
            "gaussian_normals", "depth_to_normal", "DEPTH_NORMAL_TILE_W", "DEPTH_NORMAL_TILE_H",
            "bilateral_slice", "total_variation_loss", "BILAGRID_TILE_W", "BILAGRID_TILE_H", "BILAGRID_WINDOW_CELLS",
            "tsdf_allocate", "tsdf_integrate", "tsdf_extract", "tsdf_mark_steps", "TSDF_CAMERA_CHUNK", "TSDF_MAX_BLOCKS_PER_AXIS",
-           "TSDF_MAX_SLOTS"]
+           "TSDF_MAX_SLOTS", "vq_assign", "vq_update", "VQ_MAX_DIM", "VQ_MAX_CODES", "VQ_CODE_CHUNK", "VQ_UPDATE_CHUNK"]
 
 
 class GaussianRasterizationSettings(NamedTuple):
@@ -2353,6 +2353,117 @@ def tsdf_extract(volume):
             _tsdf_probe("msgs_tsdf_emit")
         _C.check(_C.lib.msgs_tsdf_emit(C.byref(v), C.byref(m), stream), "msgs_tsdf_emit")
     return vertices, colours, faces
+
+
+# k-means vector quantisation (SPEC M21; 4.23): the two device steps of a k-means iteration on any [P,D] float32
+# tensor, D <= VQ_MAX_DIM, K <= VQ_MAX_CODES — the nearest-code search on the f32 MFMA, fused with the argmin so that no [P,K] score
+# ever reaches memory, and a centroid update without float atomics whose bits do not depend on the launch.  host/compress.py builds
+# k-means and the compressed model file on them.  Not differentiable.
+VQ_MAX_DIM, VQ_MAX_CODES = _C.VQ_MAX_DIM, _C.VQ_MAX_CODES
+VQ_CODE_CHUNK, VQ_UPDATE_CHUNK = _C.VQ_CODE_CHUNK, _C.VQ_UPDATE_CHUNK
+_vq_probe = None                   # tests: a callable (name) run in front of every msgs_vq_* call
+
+
+def _vq_rows(who, x, codebook, **more):
+    """(P, D, K) of x [P,D] and codebook [K,D] — everything is checked before any launch; `more`: further float32 tensors"""
+    for name, t in (("x", x), ("codebook", codebook)) + tuple(more.items()):
+        if t is None:
+            continue
+        if not torch.is_tensor(t):
+            raise ValueError(f"{who}: {name} must be a tensor")
+        if t.dtype != torch.float32:
+            raise ValueError(f"{who}: {name} must be float32, not {t.dtype}")
+        if t.requires_grad:
+            raise ValueError(f"{who}: {name} requires grad — vector quantisation is not differentiable: pass {name}.detach()")
+    if x.dim() != 2 or codebook.dim() != 2:
+        raise ValueError(f"{who}: x must be [P,D] and codebook [K,D], got {tuple(x.shape)} and {tuple(codebook.shape)}")
+    (P, D), (K, Dc) = (int(n) for n in x.shape), (int(n) for n in codebook.shape)
+    if D != Dc:
+        raise ValueError(f"{who}: x has {D} columns, the codebook {Dc}")
+    if not 1 <= D <= VQ_MAX_DIM:
+        raise ValueError(f"{who}: D = {D}, 1 .. {VQ_MAX_DIM} columns are supported")
+    if not 1 <= K <= VQ_MAX_CODES:
+        raise ValueError(f"{who}: K = {K}, 1 .. {VQ_MAX_CODES} codes are supported")
+    if P >= 1 << 31:
+        raise ValueError(f"{who}: P = {P} rows do not fit int32 indices")
+    return P, D, K
+
+
+def _vq_on_device(who, **tensors):
+    """the last check in front of a launch: every tensor lives on one HIP device"""
+    dev = None
+    for name, t in tensors.items():
+        if t is None:
+            continue
+        if t.device.type != "cuda":
+            raise RuntimeError(f"{who}: {name} must live on a HIP device ('cuda'); there is no CPU path")
+        if dev is not None and t.device != dev:
+            raise ValueError(f"{who}: {name} is on {t.device}, x on {dev}")
+        dev = t.device
+    return dev
+
+
+@torch.no_grad()
+def vq_assign(x, codebook, return_error=True):
+    """(idx [P] int32, err [P] float32 or None): for every row of x [P,D] the nearest row of codebook [K,D] under SPEC M21 (a) —
+    score s(i,k) = the float32 chain s = n_k; s = fmaf(-x_id, c_kd, s) over ascending d with n_k = float32(1/2 sum_d c_kd^2) taken
+    in double, idx the smallest k of minimal score (strict <, from +inf and 0, a NaN never wins), err_i = sum_d (x_id - c_kd)^2 of
+    the chosen code as a float32 fmaf chain over the two rows.  One kernel on the f32 MFMA behind a small one that lays the
+    codebook out; no [P,K] matrix exists anywhere.  The same bits on every run.  Inputs are assumed finite: a row with a NaN gets
+    idx 0 and err NaN; a row with an infinity gets the lowest code whose score came out -inf, or 0 when none did."""
+    P, D, K = _vq_rows("vq_assign", x, codebook)
+    dev = _vq_on_device("vq_assign", x=x, codebook=codebook)
+    idx = torch.empty(P, dtype=torch.int32, device=dev)
+    err = torch.empty(P, dtype=torch.float32, device=dev) if return_error else None
+    if P == 0:
+        return idx, err
+    x, codebook = x.contiguous(), codebook.contiguous()
+    with _on_device(dev):
+        scratch = _bytes(_C.lib.msgs_vq_scratch_bytes(0, D, K), dev)
+        if _vq_probe is not None:
+            _vq_probe("msgs_vq_assign")
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _C.check(_C.lib.msgs_vq_assign(P, D, K, _ptr(x), _ptr(codebook), _ptr(idx), _ptr(err), _ptr(scratch), scratch.numel(),
+                                       stream), "msgs_vq_assign")
+    return idx, err
+
+
+@torch.no_grad()
+def vq_update(x, idx, codebook, weights=None):
+    """(new codebook [K,D] float32, mass [K] float64, count [K] int32): SPEC M21 (b) — c_k = float32(sum w_i x_i / sum w_i) over
+    the rows with idx == k, in double, summed in ascending row order within chunks of VQ_UPDATE_CHUNK consecutive members and the
+    chunk partials added in chunk order; weights [P] float32 >= 0 or None (1).  A code of mass 0 keeps its row of `codebook`.
+    Contract: every idx is in [0, K) — checked here (the member ordering reads the counts anyway), before any launch of the sum.
+    The stable sort, the counts and the offsets are torch; the weighted segmented sum is two kernels without atomics: the same
+    bits on every run and under every launch geometry.  `codebook` is not changed."""
+    P, D, K = _vq_rows("vq_update", x, codebook, weights=weights)
+    if not torch.is_tensor(idx) or idx.dtype not in (torch.int32, torch.int64) or tuple(idx.shape) != (P,):
+        raise ValueError(f"vq_update: idx must be an int32 or int64 tensor [{P}]")
+    if weights is not None and tuple(weights.shape) != (P,):
+        raise ValueError(f"vq_update: weights must be [{P}], got {tuple(weights.shape)}")
+    dev = _vq_on_device("vq_update", x=x, idx=idx, codebook=codebook, weights=weights)
+    x, codebook = x.contiguous(), codebook.contiguous()
+    weights = None if weights is None else weights.contiguous()
+    with _on_device(dev):
+        if P and (int(idx.min()) < 0 or int(idx.max()) >= K):
+            raise ValueError(f"vq_update: idx must lie in [0, {K})")
+        order = torch.sort(idx, stable=True).indices if P else torch.zeros(0, dtype=torch.int64, device=dev)
+        members = torch.bincount(idx, minlength=K) if P else torch.zeros(K, dtype=torch.int64, device=dev)
+        zero = torch.zeros(1, dtype=torch.int64, device=dev)
+        offsets = torch.cat((zero, torch.cumsum(members, 0))).to(torch.int32)
+        chunks = (members + (VQ_UPDATE_CHUNK - 1)) // VQ_UPDATE_CHUNK
+        chunk_offsets = torch.cat((zero, torch.cumsum(chunks, 0))).to(torch.int32)
+        new = torch.empty_like(codebook)
+        mass = torch.empty(K, dtype=torch.float64, device=dev)
+        count = torch.empty(K, dtype=torch.int32, device=dev)
+        scratch = _bytes(_C.lib.msgs_vq_scratch_bytes(P, D, K), dev)
+        if _vq_probe is not None:
+            _vq_probe("msgs_vq_update")
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _C.check(_C.lib.msgs_vq_update(P, D, K, _ptr(x), _ptr(weights), _ptr(order), _ptr(offsets), _ptr(chunk_offsets),
+                                       _ptr(codebook), _ptr(new), _ptr(mass), _ptr(count), _ptr(scratch), scratch.numel(), stream),
+                 "msgs_vq_update")
+    return new, mass, count
 
 
 # Contribution scores (DESIGN.md 2, M11; 4.11): what every Gaussian did to the images of one or many views, the criterion of

@@ -157,6 +157,11 @@ class TsdfMesh(C.Structure):             # msgs_tsdf_mesh_t
                 ("vertices", C.c_void_p), ("colours", C.c_void_p), ("faces", C.c_void_p)]
 
 
+# msgs_vq_* (include/msgs.h): the limits of the nearest-code search, the codes per LDS chunk of it, and the members per partial sum
+# of the centroid update (part of the update's definition)
+VQ_MAX_DIM, VQ_MAX_CODES, VQ_CODE_CHUNK, VQ_UPDATE_CHUNK = 64, 65536, 64, 256
+
+
 class Timing(C.Structure):
     _fields_ = [("ev", C.c_void_p * (2 * K_COUNT))]
 
@@ -352,6 +357,12 @@ def _load():
     lib.msgs_tsdf_count.argtypes = [C.POINTER(TsdfVolume), vp, vp, vp, vp]
     lib.msgs_tsdf_emit.restype = C.c_int
     lib.msgs_tsdf_emit.argtypes = [C.POINTER(TsdfVolume), C.POINTER(TsdfMesh), vp]
+    lib.msgs_vq_scratch_bytes.restype = sz
+    lib.msgs_vq_scratch_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int32]
+    lib.msgs_vq_assign.restype = C.c_int
+    lib.msgs_vq_assign.argtypes = [C.c_int64, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, sz, vp]
+    lib.msgs_vq_update.restype = C.c_int
+    lib.msgs_vq_update.argtypes = [C.c_int64, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
     lib.msgs_loss_scratch_bytes.restype = sz
     lib.msgs_loss_scratch_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
     lib.msgs_loss_forward.restype = C.c_int
@@ -409,6 +420,7 @@ EXPORTS = ("msgs_abi_version", "msgs_error_string", "msgs_geom_bytes", "msgs_sta
            "msgs_bilagrid_tv_scratch_bytes", "msgs_bilagrid_tv_forward", "msgs_bilagrid_tv_backward",
            "msgs_mcmc_scratch_bytes", "msgs_mcmc_prepare", "msgs_mcmc_sample", "msgs_mcmc_relocate", "msgs_mcmc_noise",
            "msgs_tsdf_mark_blocks", "msgs_tsdf_integrate", "msgs_tsdf_count", "msgs_tsdf_emit",
+           "msgs_vq_scratch_bytes", "msgs_vq_assign", "msgs_vq_update",
            "msgs_set_depth_sort", "msgs_depth_sort_stats")
 
 
