@@ -11,7 +11,6 @@
     perturbing the oracle's sums by one float32 ulp-sized relative amount (1e-7) and reading the relative movement of the
     outputs: the printed factor is the condition number the floor document talks about.
 """
-import ctypes as C
 import math
 
 import pytest
@@ -19,47 +18,12 @@ import torch
 
 import scenes
 from parity_utils import hip_render, rel_err, report
+from per_gaussian_entry import per_gaussian_hip as _per_gaussian_hip, plain_call as _plain_call
 
 pytestmark = pytest.mark.gpu
 
 K8_RTOL = 1e-6            # measured 2e-8 on dL/dmeans3D, 0.0 (bit-equal) on the other five tensors at C2 and C3
 COV_RTOL = 1e-4           # north star
-
-
-def _plain_call(seen, cam, st, bg, dev="cuda", cov=None):
-    """reference-API (raw_params = 0) marshalling of the activated tensors the oracle is fed"""
-    import diff_gaussian_rasterization as dgr
-    rs = dgr.GaussianRasterizationSettings(
-        image_height=cam.image_height, image_width=cam.image_width, tanfovx=math.tan(cam.FoVx * 0.5),
-        tanfovy=math.tan(cam.FoVy * 0.5), bg=bg.to(dev), scale_modifier=1.0,
-        viewmatrix=cam.world_view_transform.to(dev), projmatrix=cam.full_proj_transform.to(dev),
-        sh_degree=seen.sh_degree, campos=cam.camera_center.to(dev), prefiltered=False, debug=False, **st)
-    t = lambda x: x.to(dev).contiguous()
-    return dgr._Call(rs, t(seen.means3D), t(seen.shs), None, t(seen.opacities),
-                     None if cov is not None else t(seen.scales), None if cov is not None else t(seen.rotations),
-                     t(cov) if cov is not None else None, t(seen.max_pixel_sizes), t(seen.min_pixel_sizes), None, None,
-                     t(seen.base_mask))
-
-
-def _per_gaussian_hip(call, radii, geom, sums2d, with_cov=False):
-    import diff_gaussian_rasterization as dgr
-    P, K, dev = call.P, call.K, call.device
-    e = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
-    out = dict(means3D=e(P, 3), means2D=e(P, 3), shs=e(P, K, 3), opacities=e(P))
-    if with_cov:
-        out["cov3D_precomp"] = e(P, 6)
-    else:
-        out["scales"], out["rotations"] = e(P, 3), e(P, 4)
-    p = lambda k: C.c_void_p(out[k].data_ptr()) if k in out else None
-    grads = dgr._C.Grads(p("means3D"), p("means2D"), p("shs"), None, p("opacities"), p("scales"), p("rotations"),
-                         p("cov3D_precomp"), None, None, None, 0)
-    s = sums2d.to(dev).contiguous()
-    dgr._C.check(dgr._C.lib.msgs_backward_per_gaussian(
-        C.byref(call.view), C.byref(call.g), C.c_void_p(radii.data_ptr()), C.c_void_p(geom.data_ptr()), geom.numel(),
-        C.c_void_p(s.data_ptr()), C.byref(grads), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
-        "msgs_backward_per_gaussian")
-    torch.cuda.synchronize()
-    return out
 
 
 @pytest.mark.parametrize("name", ["C2", "C3"])
