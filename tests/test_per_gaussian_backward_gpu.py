@@ -15,8 +15,6 @@ tests/test_per_gaussian_truth_cpu.py::test_yardstick_is_recorded, which fails if
 The margin of 2 covers FMA contraction and another order of the same products (the convention of test_position_noise); it does
 not cover a different formula.  A tensor whose yardstick is 0 (dL_dmeans2D, dL_dcolors, dL_dopacities at weight 1: copies of
 float32-representable sums) must be exact.  Achieved ratios: profiles/per_gaussian_backward_notes.md."""
-import types
-
 import numpy as np
 import pytest
 import torch
@@ -57,14 +55,11 @@ ACHIEVED = {}        # (family, tensor) -> worst ratio over everything run so fa
 
 def _run(name, pattern, P):
     import diff_gaussian_rasterization as dgr
-    from per_gaussian_entry import per_gaussian_hip, plain_call
+    from per_gaussian_entry import family_call, per_gaussian_hip
     fam = pt.family(name)
     view, inp, sums, _ = pt.case(name, pattern, P)
-    seen = types.SimpleNamespace(sh_degree=int(view["sh_degree"]), shs=inp.get("shs"), scales=inp.get("scales"),
-                                 rotations=inp.get("rotations"), **{k: inp[k] for k in (
-                                     "means3D", "opacities", "max_pixel_sizes", "min_pixel_sizes", "base_mask")})
-    cov, colors = inp.get("cov3D_precomp"), inp.get("colors_precomp")
-    call = plain_call(seen, fam["cam"], fam["settings"], torch.zeros(3), cov=cov, scale_modifier=fam["mod"], colors=colors)
+    cov = inp.get("cov3D_precomp")
+    call = family_call(fam, inp)
     with torch.no_grad():
         _, _, _, radii, psz, (geom, _, _, _) = dgr._forward_impl(call)
     torch.cuda.synchronize()
