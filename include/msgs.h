@@ -1105,6 +1105,33 @@ int msgs_vq_update(int64_t P, int32_t D, int32_t K, const float* x, const float*
                    const int32_t* chunk_offsets, const float* codebook, float* new_codebook, double* mass, int32_t* count,
                    void* scratch, size_t scratch_bytes, void* stream);
 
+/* ---- connected components and mesh clean-up (DESIGN.md SPEC M22, 4.24) ----------------------------------------------------------
+ * All indices int32, all keys int64; sizes outside 0 <= N, E, n_keys < 2^31 and 0 <= 3 F < 2^31, an unknown mode, and a NULL
+ * pointer with a non-zero size return MSGS_ERR_INVALID_ARG and launch nothing.
+ *   msgs_graph_components  label [N]: label[x] = the smallest node of x's connected component under the E undirected edges
+ *                          (a[i], b[i]), 0 <= a, b < N (the caller's contract: an edge that breaks it is left out); self-loops
+ *                          and repeated edges are allowed.  The result is defined by the input alone, so it has the same bits on
+ *                          every run.  parent_scratch [N] int32, no clearing needed.  Three launches: identity, link (a union-find
+ *                          written by atomicMin only, whose loops wait on no other lane), flatten.  N == 0 launches nothing.
+ *   msgs_mesh_corner_keys  faces [F,3]; for corner c = 3 f + k: face_of_key[c] = f and keys[c] = (min(u,v) << 32) | max(u,v) of
+ *                          the edge from u = faces[f][k] to v = faces[f][(k+1) % 3] (MSGS_MESH_EDGE) or keys[c] = u
+ *                          (MSGS_MESH_VERTEX).  Indices are not dereferenced and not checked.  F == 0 launches nothing.
+ *   msgs_mesh_link_sorted  keys_sorted [n_keys] ascending with face_sorted [n_keys] permuted alike (values in [0, F)): the graph
+ *                          on the F faces in which face_sorted[i] and face_sorted[i+1] are joined wherever keys_sorted[i] ==
+ *                          keys_sorted[i+1]; label [F] and parent_scratch [F] as in msgs_graph_components.  The order among equal
+ *                          keys does not matter: a run of equal keys joins all its faces either way.  F == 0 launches nothing.
+ *   msgs_mesh_edge_report  counts3 [3] int64 (cleared here): the number of distinct keys that occur once, twice and more often
+ *                          in keys_sorted — over MSGS_MESH_EDGE keys the boundary, manifold and non-manifold edges.
+ * Everything on `stream`, no synchronisation; the library allocates and keeps nothing. */
+#define MSGS_MESH_EDGE 0
+#define MSGS_MESH_VERTEX 1
+int msgs_graph_components(int64_t N, int64_t E, const int32_t* a, const int32_t* b, int32_t* parent_scratch, int32_t* label,
+                          void* stream);
+int msgs_mesh_corner_keys(int64_t F, const int32_t* faces, int32_t mode, int64_t* keys, int32_t* face_of_key, void* stream);
+int msgs_mesh_link_sorted(int64_t F, int64_t n_keys, const int64_t* keys_sorted, const int32_t* face_sorted,
+                          int32_t* parent_scratch, int32_t* label, void* stream);
+int msgs_mesh_edge_report(int64_t n_keys, const int64_t* keys_sorted, int64_t* counts3, void* stream);
+
 /* ---- fused photometric loss ----------------------------------------------------------------
  * loss = (1 - lambda_dssim) * l1_loss(img, gt) + lambda_dssim * (1 - ssim(img, gt))   (/root/reference/train.py:209-211)
  * with l1_loss / ssim of /root/reference/utils/loss_utils.py:17-18,32-63 (window 11, sigma 1.5, zero padding, mean).

@@ -1645,6 +1645,41 @@ int msgs_vq_update(int64_t P, int32_t D, int32_t K, const float* x, const float*
     return MSGS_OK;
 }
 
+// ---- connected components and mesh clean-up (SPEC M22) ----
+int msgs_graph_components(int64_t N, int64_t E, const int32_t* a, const int32_t* b, int32_t* parent_scratch, int32_t* label,
+                          void* stream) {
+    if (N < 0 || E < 0 || N >= ((int64_t)1 << 31) || E >= ((int64_t)1 << 31)) return MSGS_ERR_INVALID_ARG;
+    if ((E > 0 && (!a || !b)) || (N > 0 && (!parent_scratch || !label))) return MSGS_ERR_INVALID_ARG;
+    if (N == 0) return E == 0 ? MSGS_OK : MSGS_ERR_INVALID_ARG;                     // an edge needs a node
+    HIP_TRY(launch_graph_components((int32_t)N, E, a, b, parent_scratch, label, (hipStream_t)stream));
+    return MSGS_OK;
+}
+
+static int mesh_faces_ok(int64_t F) { return F >= 0 && 3 * F < ((int64_t)1 << 31); }
+
+int msgs_mesh_corner_keys(int64_t F, const int32_t* faces, int32_t mode, int64_t* keys, int32_t* face_of_key, void* stream) {
+    if (!mesh_faces_ok(F) || (mode != MSGS_MESH_EDGE && mode != MSGS_MESH_VERTEX)) return MSGS_ERR_INVALID_ARG;
+    if (F == 0) return MSGS_OK;
+    if (!faces || !keys || !face_of_key) return MSGS_ERR_INVALID_ARG;
+    HIP_TRY(launch_mesh_corner_keys(F, faces, mode == MSGS_MESH_VERTEX, keys, face_of_key, (hipStream_t)stream));
+    return MSGS_OK;
+}
+
+int msgs_mesh_link_sorted(int64_t F, int64_t n_keys, const int64_t* keys_sorted, const int32_t* face_sorted,
+                          int32_t* parent_scratch, int32_t* label, void* stream) {
+    if (!mesh_faces_ok(F) || n_keys < 0 || n_keys >= ((int64_t)1 << 31)) return MSGS_ERR_INVALID_ARG;
+    if (F == 0) return n_keys == 0 ? MSGS_OK : MSGS_ERR_INVALID_ARG;                // a key needs a face
+    if ((n_keys > 0 && (!keys_sorted || !face_sorted)) || !parent_scratch || !label) return MSGS_ERR_INVALID_ARG;
+    HIP_TRY(launch_mesh_link_sorted((int32_t)F, n_keys, keys_sorted, face_sorted, parent_scratch, label, (hipStream_t)stream));
+    return MSGS_OK;
+}
+
+int msgs_mesh_edge_report(int64_t n_keys, const int64_t* keys_sorted, int64_t* counts3, void* stream) {
+    if (n_keys < 0 || n_keys >= ((int64_t)1 << 31) || !counts3 || (n_keys > 0 && !keys_sorted)) return MSGS_ERR_INVALID_ARG;
+    HIP_TRY(launch_mesh_edge_report(n_keys, keys_sorted, counts3, (hipStream_t)stream));
+    return MSGS_OK;
+}
+
 static int loss_args_ok(const float* img, const float* gt, int32_t C, int32_t H, int32_t W, float lambda) {
     if (!img || !gt || C < 1 || H < 1 || W < 1 || !(lambda >= 0.f && lambda <= 1.f)) return MSGS_ERR_INVALID_ARG;
     if ((int64_t)C * H * W > (int64_t)1 << 31 || C > 65535) return MSGS_ERR_TOO_MANY;

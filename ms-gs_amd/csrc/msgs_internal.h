@@ -949,6 +949,15 @@ hipError_t launch_vq_assign(int64_t P, int D, int K, const float* x, const float
 hipError_t launch_vq_update(int64_t P, int D, int K, const float* x, const float* w, const int64_t* order, const int32_t* offsets,
                             const int32_t* chunk_offsets, const float* codebook, float* new_codebook, double* mass, int32_t* count,
                             char* scratch, hipStream_t s);
+// mesh.hip — msgs_graph_components / msgs_mesh_* (SPEC M22): the wait-free union-find (init, link, flatten: three launches), the
+// corner keys of a triangle mesh and the edge report over the sorted keys (the arguments are checked in api.hip)
+hipError_t launch_graph_components(int32_t N, int64_t E, const int32_t* a, const int32_t* b, int32_t* parent, int32_t* label,
+                                   hipStream_t s);
+hipError_t launch_mesh_corner_keys(int64_t F, const int32_t* faces, bool vertex_mode, int64_t* keys, int32_t* face_of_key,
+                                   hipStream_t s);
+hipError_t launch_mesh_link_sorted(int32_t F, int64_t n_keys, const int64_t* keys_sorted, const int32_t* face_sorted,
+                                   int32_t* parent, int32_t* label, hipStream_t s);
+hipError_t launch_mesh_edge_report(int64_t n_keys, const int64_t* keys_sorted, int64_t* counts3, hipStream_t s);
 // heaviest-first launch order of the one-wave-per-tile backward from the forward's per-tile traversal lengths
 hipError_t launch_tile_order(const ViewParams& vp, const uint32_t* tile_last, uint32_t* tile_order, hipStream_t s);
 hipError_t launch_blend_lane_stats(const ViewParams& vp, const char* geom, const uint32_t* ids, const uint2* ranges,

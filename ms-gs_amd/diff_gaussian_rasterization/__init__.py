@@ -33,7 +33,8 @@ __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gau
            "gaussian_normals", "depth_to_normal", "DEPTH_NORMAL_TILE_W", "DEPTH_NORMAL_TILE_H",
            "bilateral_slice", "total_variation_loss", "BILAGRID_TILE_W", "BILAGRID_TILE_H", "BILAGRID_WINDOW_CELLS",
            "tsdf_allocate", "tsdf_integrate", "tsdf_extract", "tsdf_mark_steps", "TSDF_CAMERA_CHUNK", "TSDF_MAX_BLOCKS_PER_AXIS",
-           "TSDF_MAX_SLOTS", "vq_assign", "vq_update", "VQ_MAX_DIM", "VQ_MAX_CODES", "VQ_CODE_CHUNK", "VQ_UPDATE_CHUNK"]
+           "TSDF_MAX_SLOTS", "vq_assign", "vq_update", "VQ_MAX_DIM", "VQ_MAX_CODES", "VQ_CODE_CHUNK", "VQ_UPDATE_CHUNK",
+           "graph_components", "mesh_triangle_clusters", "mesh_edge_report"]
 
 
 class GaussianRasterizationSettings(NamedTuple):
@@ -2464,6 +2465,136 @@ def vq_update(x, idx, codebook, weights=None):
                                        _ptr(codebook), _ptr(new), _ptr(mass), _ptr(count), _ptr(scratch), scratch.numel(), stream),
                  "msgs_vq_update")
     return new, mass, count
+
+
+# Connected components and mesh clean-up (SPEC M22; 4.24): the smallest-node label of every node of a graph, the
+# connected triangle clusters of a mesh (Open3D's cluster_connected_triangles) and its edge report.  The union-find behind them is
+# written by atomicMin only and waits on nobody; its result is defined by the input alone, so it has the same bits on every run.
+# host/mesh.py builds post_process_mesh on them.  Not differentiable.
+_mesh_probe = None                 # tests: a callable (name) run in front of every msgs_graph_* / msgs_mesh_* call
+
+
+def _mesh_call(name, *args):
+    if _mesh_probe is not None:
+        _mesh_probe(name)
+    _C.check(getattr(_C.lib, name)(*args), name)
+
+
+def _mesh_index_tensor(who, name, t, shape_ok, shape_text):
+    if not torch.is_tensor(t) or t.dtype not in (torch.int32, torch.int64) or not shape_ok(t):
+        raise ValueError(f"{who}: {name} must be an int32 or int64 tensor {shape_text}")
+
+
+def _mesh_on_device(who, **tensors):
+    for name, t in tensors.items():
+        if t.device.type != "cuda":
+            raise RuntimeError(f"{who}: {name} must live on a HIP device ('cuda'); there is no CPU path")
+
+
+def _mesh_in_range(who, name, t, n):
+    """the last check in front of a launch: 0 <= t < n for every element (one host read); returns t as contiguous int32"""
+    if t.numel():
+        lo, hi = torch.stack((t.min(), t.max())).tolist()
+        if lo < 0 or hi >= n:
+            raise ValueError(f"{who}: {name} must lie in [0, {n}), got {lo} .. {hi}")
+    return t.to(torch.int32).contiguous()
+
+
+@torch.no_grad()
+def graph_components(n_nodes, a, b):
+    """label [n_nodes] int32: label[x] is the smallest node of x's connected component under the undirected edges (a[i], b[i])
+    (a, b: [E] int32 or int64 on one HIP device, 0 <= a, b < n_nodes — checked with one host read; self-loops and repeated
+    edges are allowed).  SPEC M22 (a): the result is defined by the input alone.  Three launches (identity, link, flatten);
+    without edges the labels are torch.arange and nothing is launched."""
+    N = int(n_nodes)
+    if N < 0 or N >= 1 << 31:
+        raise ValueError(f"graph_components: n_nodes = {N} is outside [0, 2^31)")
+    for name, t in (("a", a), ("b", b)):
+        _mesh_index_tensor("graph_components", name, t, lambda t: t.dim() == 1, "[E]")
+    if a.shape != b.shape or a.device != b.device:
+        raise ValueError("graph_components: a and b must have one shape and one device")
+    E, dev = int(a.shape[0]), a.device
+    if E >= 1 << 31:
+        raise ValueError(f"graph_components: E = {E} edges do not fit int32 indices")
+    _mesh_on_device("graph_components", a=a, b=b)
+    with _on_device(dev):
+        a, b = _mesh_in_range("graph_components", "a", a, N), _mesh_in_range("graph_components", "b", b, N)
+        if N == 0 or E == 0:
+            return torch.arange(N, dtype=torch.int32, device=dev)
+        parent = torch.empty(N, dtype=torch.int32, device=dev)
+        label = torch.empty(N, dtype=torch.int32, device=dev)
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _mesh_call("msgs_graph_components", N, E, _ptr(a), _ptr(b), _ptr(parent), _ptr(label), stream)
+    return label
+
+
+def _mesh_faces(who, faces, n_vertices):
+    _mesh_index_tensor(who, "faces", faces, lambda t: t.dim() == 2 and t.shape[1] == 3, "[F,3]")
+    V, F = int(n_vertices), int(faces.shape[0])
+    if V < 0 or V >= 1 << 31:
+        raise ValueError(f"{who}: n_vertices = {V} is outside [0, 2^31)")
+    if 3 * F >= 1 << 31:
+        raise ValueError(f"{who}: {F} faces: 3 F must stay below 2^31")
+    _mesh_on_device(who, faces=faces)
+    return V, F
+
+
+def _mesh_sorted_keys(who, faces, F, mode, stream):
+    """(keys_sorted [3F] int64, face_sorted [3F] int32): the corner keys of SPEC M22 (b) in ascending order"""
+    dev = faces.device
+    keys = torch.empty(3 * F, dtype=torch.int64, device=dev)
+    face_of_key = torch.empty(3 * F, dtype=torch.int32, device=dev)
+    _mesh_call("msgs_mesh_corner_keys", F, _ptr(faces), mode, _ptr(keys), _ptr(face_of_key), stream)
+    keys_sorted, order = torch.sort(keys)
+    return keys_sorted, face_of_key[order]
+
+
+@torch.no_grad()
+def mesh_triangle_clusters(faces, n_vertices, connectivity="edge"):
+    """(triangle_clusters [F] int32, cluster_n_triangles [K] int32) of faces [F,3] (int32 or int64, on a HIP device) over
+    n_vertices vertices — SPEC M22 (b).  connectivity "edge" (Open3D's rule): two faces are adjacent when they share an
+    undirected edge; "vertex": when they share a vertex.  Cluster ids run 0 .. K-1 in ascending order of each cluster's smallest
+    face index (in "edge" mode Open3D's numbering).  Indices outside [0, n_vertices) are refused with ValueError before any
+    launch (one host read); reading K is the second.  A key kernel, torch.sort, the union-find (three launches), torch.cumsum
+    and torch.bincount.  F == 0 launches nothing."""
+    if connectivity not in ("edge", "vertex"):
+        raise ValueError(f"mesh_triangle_clusters: connectivity must be 'edge' or 'vertex', not {connectivity!r}")
+    V, F = _mesh_faces("mesh_triangle_clusters", faces, n_vertices)
+    dev = faces.device
+    with _on_device(dev):
+        faces = _mesh_in_range("mesh_triangle_clusters", "faces", faces, V)
+        if F == 0:
+            return torch.zeros(0, dtype=torch.int32, device=dev), torch.zeros(0, dtype=torch.int32, device=dev)
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        mode = _C.MESH_EDGE if connectivity == "edge" else _C.MESH_VERTEX
+        keys_sorted, face_sorted = _mesh_sorted_keys("mesh_triangle_clusters", faces, F, mode, stream)
+        parent = torch.empty(F, dtype=torch.int32, device=dev)
+        label = torch.empty(F, dtype=torch.int32, device=dev)
+        _mesh_call("msgs_mesh_link_sorted", F, 3 * F, _ptr(keys_sorted), _ptr(face_sorted), _ptr(parent), _ptr(label), stream)
+        is_root = label == torch.arange(F, dtype=torch.int32, device=dev)
+        rank = torch.cumsum(is_root, 0, dtype=torch.int32) - 1             # of a root: its cluster id
+        clusters = rank[label.long()]
+        counts = torch.bincount(clusters).to(torch.int32)
+    return clusters, counts
+
+
+@torch.no_grad()
+def mesh_edge_report(faces, n_vertices):
+    """(boundary, manifold, non_manifold): the numbers of undirected edges of faces [F,3] used once, twice and more often, as
+    Python ints — SPEC M22 (c), from the sorted "edge" keys of mesh_triangle_clusters.  Every face corner counts as one use, so
+    a face with a repeated index uses one of its edges twice.  Indices are checked as there; F == 0 launches nothing."""
+    V, F = _mesh_faces("mesh_edge_report", faces, n_vertices)
+    dev = faces.device
+    with _on_device(dev):
+        faces = _mesh_in_range("mesh_edge_report", "faces", faces, V)
+        if F == 0:
+            return 0, 0, 0
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        keys_sorted, _ = _mesh_sorted_keys("mesh_edge_report", faces, F, _C.MESH_EDGE, stream)
+        counts = torch.empty(3, dtype=torch.int64, device=dev)
+        _mesh_call("msgs_mesh_edge_report", 3 * F, _ptr(keys_sorted), _ptr(counts), stream)
+        boundary, manifold, non_manifold = counts.tolist()
+    return boundary, manifold, non_manifold
 
 
 # Contribution scores (DESIGN.md 2, M11; 4.11): what every Gaussian did to the images of one or many views, the criterion of

@@ -161,6 +161,9 @@ class TsdfMesh(C.Structure):             # msgs_tsdf_mesh_t
 # of the centroid update (part of the update's definition)
 VQ_MAX_DIM, VQ_MAX_CODES, VQ_CODE_CHUNK, VQ_UPDATE_CHUNK = 64, 65536, 64, 256
 
+# msgs_mesh_* (include/msgs.h): what makes two faces of a mesh adjacent
+MESH_EDGE, MESH_VERTEX = 0, 1
+
 
 class Timing(C.Structure):
     _fields_ = [("ev", C.c_void_p * (2 * K_COUNT))]
@@ -363,6 +366,14 @@ def _load():
     lib.msgs_vq_assign.argtypes = [C.c_int64, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, sz, vp]
     lib.msgs_vq_update.restype = C.c_int
     lib.msgs_vq_update.argtypes = [C.c_int64, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    lib.msgs_graph_components.restype = C.c_int
+    lib.msgs_graph_components.argtypes = [C.c_int64, C.c_int64, vp, vp, vp, vp, vp]
+    lib.msgs_mesh_corner_keys.restype = C.c_int
+    lib.msgs_mesh_corner_keys.argtypes = [C.c_int64, vp, C.c_int32, vp, vp, vp]
+    lib.msgs_mesh_link_sorted.restype = C.c_int
+    lib.msgs_mesh_link_sorted.argtypes = [C.c_int64, C.c_int64, vp, vp, vp, vp, vp]
+    lib.msgs_mesh_edge_report.restype = C.c_int
+    lib.msgs_mesh_edge_report.argtypes = [C.c_int64, vp, vp, vp]
     lib.msgs_loss_scratch_bytes.restype = sz
     lib.msgs_loss_scratch_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
     lib.msgs_loss_forward.restype = C.c_int
@@ -421,6 +432,7 @@ EXPORTS = ("msgs_abi_version", "msgs_error_string", "msgs_geom_bytes", "msgs_sta
            "msgs_mcmc_scratch_bytes", "msgs_mcmc_prepare", "msgs_mcmc_sample", "msgs_mcmc_relocate", "msgs_mcmc_noise",
            "msgs_tsdf_mark_blocks", "msgs_tsdf_integrate", "msgs_tsdf_count", "msgs_tsdf_emit",
            "msgs_vq_scratch_bytes", "msgs_vq_assign", "msgs_vq_update",
+           "msgs_graph_components", "msgs_mesh_corner_keys", "msgs_mesh_link_sorted", "msgs_mesh_edge_report",
            "msgs_set_depth_sort", "msgs_depth_sort_stats")
 
 

@@ -5,6 +5,7 @@ ScalableTSDFVolume.integrate() and extract_triangle_mesh(), on the GPU and witho
     vol.integrate_views(cameras, pc, pipe, bg)            renders median depth and colour of every view and fuses them
     vol.integrate(depth, cameras, colour, weight)         ... or fuses maps that exist already
     vertices, colours, faces = vol.extract_mesh()
+    vertices, colours, faces = post_process_mesh(*vol.extract_mesh())     ... without floaters (host/mesh.py, M22)
     model_io.write_mesh_ply(path, vertices, faces, colours)
 
 The volume is a table of 8x8x8 blocks over `bounds` (at most 256 per axis) with a pool of the blocks near a surface.  It stores
