@@ -16,6 +16,7 @@ ABI of include/msgs.h (ms-gs_amd/csrc, loaded with ctypes by _backend.py).  PyTo
 device memory (caching allocator), streams and autograd plumbing.  There is NO fallback: importing
 this package without lib/libmsgs_hip.so raises ImportError, and calling it with CPU tensors raises.
 """
+import contextlib
 import ctypes as C
 import os
 import threading
@@ -68,15 +69,7 @@ def _opt(t):
     return t
 
 
-class _NoSwitch:
-    def __enter__(self):
-        return None
-
-    def __exit__(self, *exc):
-        return False
-
-
-_NO_SWITCH = _NoSwitch()
+_NO_SWITCH = contextlib.nullcontext()
 
 
 def _on_device(dev):
@@ -86,8 +79,63 @@ def _on_device(dev):
     return _NO_SWITCH if torch.cuda.current_device() == dev.index else torch.cuda.device(dev)
 
 
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
+def _stream(dev):
+    """dev's current stream as the void* every entry point takes last."""
+    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def _launch(probe, name, dev, *args):
+    """One launching entry point outside the step's hot path: the tests' probe first (probe(name) when not None), then
+    lib.`name`(*args, stream) on dev's current stream under _on_device(dev), the status through _C.check(rc, name).  A site
+    with several launches and torch ops between them keeps one outer `with _on_device(dev):`; the one here then switches
+    nothing."""
+    if probe is not None:
+        probe(name)
+    with _on_device(dev):
+        _C.check(getattr(_C.lib, name)(*args, _stream(dev)), name)
+
+
+_ptr = _C.ptr
+
+_HIP_ONLY = "diff_gaussian_rasterization (MI355X build): tensors must live on a HIP device"
+
+
+def _hip_only(dev):
+    if dev.type != "cuda":
+        raise RuntimeError(_HIP_ONLY)
+
+
+def _require_hip(who, anchor=None, **tensors):
+    """The last check in front of a launch: the device the tensors share (None entries are skipped); RuntimeError when one is
+    not on a HIP device, ValueError when two are on different ones.  anchor: (noun, device) of what the tensors have to sit
+    beside, such as ("the volume", its table's device); None: the first tensor given, under its keyword."""
+    noun, dev = anchor if anchor is not None else (None, None)
+    if dev is not None and dev.type != "cuda":
+        raise RuntimeError(f"{who}: {noun} must live on a HIP device ('cuda'); there is no CPU path")
+    for name, t in tensors.items():
+        if t is None:
+            continue
+        if t.device.type != "cuda":
+            raise RuntimeError(f"{who}: {name} must live on a HIP device ('cuda'); there is no CPU path")
+        if dev is None:
+            noun, dev = name, t.device
+        elif t.device != dev:
+            raise ValueError(f"{who}: {name} is on {t.device}, {noun} on {dev}")
+    return dev
+
+
+def _require_plain_f32(who, what, **tensors):
+    """every entry is a float32 tensor that does not require grad (None entries are skipped); `what`: the noun of the
+    message, the thing that is not differentiable"""
+    for name, t in tensors.items():
+        if t is None:
+            continue
+        if not torch.is_tensor(t):
+            raise ValueError(f"{who}: {name} must be a tensor")
+        if t.dtype != torch.float32:
+            raise ValueError(f"{who}: {name} must be float32, not {t.dtype}")
+        if t.requires_grad:
+            raise ValueError(f"{who}: {name} requires grad — {what} is not differentiable: pass {name}.detach()")
 
 
 def _bytes(n, device):
@@ -502,12 +550,7 @@ def _replay_forward(name, probe, call, state, *tail):
     at the price of that view's overlap), the tests' probe, then lib.`name`(replay arguments, *tail, stream) on the current
     stream of the call's device, behind the forward that left `state`"""
     geom, binning, image, D = _resolve(state)
-    dev = call.device
-    if probe is not None:
-        probe(name)
-    with _on_device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _C.check(getattr(_C.lib, name)(*_replay_args(call, call.P, geom, binning, image, D), *tail, stream), name)
+    _launch(probe, name, call.device, *_replay_args(call, call.P, geom, binning, image, D), *tail)
 
 
 def _absgrad(ctx, call, geom, binning, image, D, dL, dLd, dLa, dev, stream):
@@ -1180,8 +1223,7 @@ class _RasterizeGaussians(torch.autograd.Function):
             # which upstream's convention cannot tell apart from "not provided")
             rs = raster_settings
             dev = means3D.device
-            if dev.type != "cuda":
-                raise RuntimeError("diff_gaussian_rasterization (MI355X build): tensors must live on a HIP device")
+            _hip_only(dev)
             H, W = int(rs.image_height), int(rs.image_width)
             color = rs.bg.to(dev, torch.float32).view(3, 1, 1).expand(3, H, W).contiguous()
             ctx.empty = True
@@ -1599,11 +1641,8 @@ def sh_grad_from_views(means3D, gathered, n_views, sh_degree, scale, out_dc, out
         if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != numel or t.device != dev:
             raise ValueError(f"sh_grad_from_views: {name} must be a contiguous float32 tensor of {numel} elements on {dev}")
     base = gathered.data_ptr()
-    with _on_device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _C.check(_C.lib.msgs_sh_grad_from_views(P, int(n_views), int(sh_degree), _ptr(means3D),
-                                                C.c_void_p(base + 4 * 3 * P), row, C.c_void_p(base), row, float(scale),
-                                                _ptr(out_dc), _ptr(out_rest), stream), "msgs_sh_grad_from_views")
+    _launch(None, "msgs_sh_grad_from_views", dev, P, int(n_views), int(sh_degree), _ptr(means3D), C.c_void_p(base + 4 * 3 * P), row,
+            C.c_void_p(base), row, float(scale), _ptr(out_dc), _ptr(out_rest))
     return out_dc, out_rest
 
 
@@ -1660,18 +1699,12 @@ class _ScreenCompensation(torch.autograd.Function):
         ctx.dev = dev
         ctx.empty = P == 0
         if P == 0:
-            if dev.type != "cuda":
-                raise RuntimeError("diff_gaussian_rasterization (MI355X build): tensors must live on a HIP device")
+            _hip_only(dev)
             return torch.zeros(opacities.shape, dtype=torch.float32, device=dev)
         call = _Call(raster_settings, means3D, None, None, opacities, scales, rotations, cov3D_precomp, None, None, None, None,
                      None)
         o_eff = torch.empty(P, dtype=torch.float32, device=dev)
-        if _compensation_probe is not None:
-            _compensation_probe("msgs_screen_compensation_forward")
-        with _on_device(dev):
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            _C.check(_C.lib.msgs_screen_compensation_forward(call.view_ref, call.g_ref, _ptr(o_eff), stream),
-                     "msgs_screen_compensation_forward")
+        _launch(_compensation_probe, "msgs_screen_compensation_forward", dev, call.view_ref, call.g_ref, _ptr(o_eff))
         ctx.call = call
         ctx.features = None
         _save_inputs(ctx, means3D, opacities, scales, rotations, cov3D_precomp, viewmatrix)
@@ -1695,16 +1728,11 @@ class _ScreenCompensation(torch.autograd.Function):
         g_rot = new(P, 4) if call.rot is not None else None
         g_cov = new(P, 6) if call.cov is not None else None
         dV = new(16) if ctx.vm is not None else None
-        if _compensation_probe is not None:
-            _compensation_probe("msgs_screen_compensation_backward")
-        with _on_device(dev):
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            scratch = _bytes(_C.lib.msgs_screen_compensation_scratch_bytes(P), dev) if dV is not None else None
-            g = _f32c(grad_o_eff).reshape(-1)
-            _C.check(_C.lib.msgs_screen_compensation_backward(
-                call.view_ref, call.g_ref, _ptr(g), _ptr(g_opac), _ptr(g_means), _ptr(g_scales), _ptr(g_rot), _ptr(g_cov),
-                _ptr(dV), _ptr(scratch), scratch.numel() if scratch is not None else 0, stream),
-                "msgs_screen_compensation_backward")
+        scratch = _bytes(_C.lib.msgs_screen_compensation_scratch_bytes(P), dev) if dV is not None else None
+        g = _f32c(grad_o_eff).reshape(-1)
+        _launch(_compensation_probe, "msgs_screen_compensation_backward", dev, call.view_ref, call.g_ref, _ptr(g), _ptr(g_opac),
+                _ptr(g_means), _ptr(g_scales), _ptr(g_rot), _ptr(g_cov), _ptr(dV), _ptr(scratch),
+                scratch.numel() if scratch is not None else 0)
         if dV is not None:
             g_vm = dV.view(ctx.vm[0]).to(device=ctx.vm[2], dtype=ctx.vm[1])
         sh = ctx.shapes
@@ -1789,22 +1817,17 @@ def compute_3d_filter(means3D, cameras, rule="per_camera", variance=0.2):
     if not cameras:
         raise ValueError("compute_3d_filter: at least one camera is needed")
     dev = means3D.device
-    if dev.type != "cuda":
-        raise RuntimeError("diff_gaussian_rasterization (MI355X build): tensors must live on a HIP device")
+    _hip_only(dev)
     P, V = int(means3D.shape[0]), len(cameras)
     filt = torch.empty(P, 1, dtype=torch.float32, device=dev)
     valid = torch.empty(P, dtype=torch.bool, device=dev)
     if P == 0:
         return filt, valid
     means = _f32c(means3D.detach())
-    with _on_device(dev):
-        cams = _camera_table(cameras, dev)
-        scratch = _bytes(_C.lib.msgs_filter3d_scratch_bytes(P, V), dev)
-        if _filter3d_probe is not None:
-            _filter3d_probe("msgs_filter3d_sweep")
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _C.check(_C.lib.msgs_filter3d_sweep(P, _ptr(means), V, _ptr(cams), _C.FILTER3D_RULES[rule], float(variance), _ptr(filt),
-                                            _ptr(valid), _ptr(scratch), scratch.numel(), stream), "msgs_filter3d_sweep")
+    cams = _camera_table(cameras, dev)
+    scratch = _bytes(_C.lib.msgs_filter3d_scratch_bytes(P, V), dev)
+    _launch(_filter3d_probe, "msgs_filter3d_sweep", dev, P, _ptr(means), V, _ptr(cams), _C.FILTER3D_RULES[rule], float(variance),
+            _ptr(filt), _ptr(valid), _ptr(scratch), scratch.numel())
     return filt, valid
 
 
@@ -1822,20 +1845,15 @@ class _SmoothingFilter(torch.autograd.Function):
     @staticmethod
     def forward(ctx, scales, opacities, filter_3D, raw):
         P, dev = int(scales.shape[0]), scales.device
-        if dev.type != "cuda":
-            raise RuntimeError("diff_gaussian_rasterization (MI355X build): tensors must live on a HIP device")
+        _hip_only(dev)
         ctx.shapes, ctx.raw, ctx.P, ctx.dev = (scales.shape, opacities.shape), bool(raw), P, dev
         s_eff = torch.empty(P, 3, dtype=torch.float32, device=dev)
         o_eff = torch.empty(opacities.shape, dtype=torch.float32, device=dev)
         if P == 0:
             return s_eff, o_eff
         s, o, f = _f32c(scales.detach()), _f32c(opacities.detach()), _f32c(filter_3D.detach())
-        if _filter3d_probe is not None:
-            _filter3d_probe("msgs_smoothing_filter_forward")
-        with _on_device(dev):
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            _C.check(_C.lib.msgs_smoothing_filter_forward(P, int(ctx.raw), _ptr(s), _ptr(o), _ptr(f), _ptr(s_eff), _ptr(o_eff),
-                                                          stream), "msgs_smoothing_filter_forward")
+        _launch(_filter3d_probe, "msgs_smoothing_filter_forward", dev, P, int(ctx.raw), _ptr(s), _ptr(o), _ptr(f), _ptr(s_eff),
+                _ptr(o_eff))
         ctx.save_for_backward(s, o, f)
         return s_eff, o_eff
 
@@ -1850,12 +1868,8 @@ class _SmoothingFilter(torch.autograd.Function):
         s, o, f = ctx.saved_tensors
         gs = None if g_s_eff is None else _f32c(g_s_eff)
         go = None if g_o_eff is None else _f32c(g_o_eff)
-        if _filter3d_probe is not None:
-            _filter3d_probe("msgs_smoothing_filter_backward")
-        with _on_device(dev):
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            _C.check(_C.lib.msgs_smoothing_filter_backward(P, int(ctx.raw), _ptr(s), _ptr(o), _ptr(f), _ptr(gs), _ptr(go),
-                                                           _ptr(g_s), _ptr(g_o), stream), "msgs_smoothing_filter_backward")
+        _launch(_filter3d_probe, "msgs_smoothing_filter_backward", dev, P, int(ctx.raw), _ptr(s), _ptr(o), _ptr(f), _ptr(gs),
+                _ptr(go), _ptr(g_s), _ptr(g_o))
         return g_s, g_o, None, None
 
 
@@ -1882,7 +1896,6 @@ def smoothing_filter(scales, opacities, filter_3D, raw=False):
 # describes.  Both are small streaming kernels outside the rasterizer.
 DEPTH_NORMAL_TILE_W, DEPTH_NORMAL_TILE_H = _C.DEPTH_NORMAL_TILE_W, _C.DEPTH_NORMAL_TILE_H
 _normals_probe = None              # tests: a callable (name) run in front of every msgs_gaussian_normals_* / msgs_depth_normal_* call
-_HIP_ONLY = "diff_gaussian_rasterization (MI355X build): tensors must live on a HIP device"
 
 
 def _camera_constant(t, n, dev, name):
@@ -1897,8 +1910,7 @@ class _GaussianNormals(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, scales, rotations, viewmatrix, campos, world):
         P, dev = int(means3D.shape[0]), means3D.device
-        if dev.type != "cuda":
-            raise RuntimeError(_HIP_ONLY)
+        _hip_only(dev)
         ctx.P, ctx.dev, ctx.world, ctx.shape = P, dev, bool(world), rotations.shape
         normals = torch.empty(P, 3, dtype=torch.float32, device=dev)
         if P == 0:
@@ -1906,12 +1918,8 @@ class _GaussianNormals(torch.autograd.Function):
         m, s, r = _f32c(means3D.detach()), _f32c(scales.detach()), _f32c(rotations.detach())
         vm, cp = _camera_constant(viewmatrix, 16, dev, "viewmatrix"), _camera_constant(campos, 3, dev, "campos")
         flags = torch.empty(P, dtype=torch.uint8, device=dev)
-        if _normals_probe is not None:
-            _normals_probe("msgs_gaussian_normals_forward")
-        with _on_device(dev):
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            _C.check(_C.lib.msgs_gaussian_normals_forward(P, _ptr(m), _ptr(s), _ptr(r), _ptr(vm), _ptr(cp), int(ctx.world),
-                                                          _ptr(normals), _ptr(flags), stream), "msgs_gaussian_normals_forward")
+        _launch(_normals_probe, "msgs_gaussian_normals_forward", dev, P, _ptr(m), _ptr(s), _ptr(r), _ptr(vm), _ptr(cp),
+                int(ctx.world), _ptr(normals), _ptr(flags))
         ctx.save_for_backward(r, flags, vm)
         return normals
 
@@ -1923,12 +1931,8 @@ class _GaussianNormals(torch.autograd.Function):
         r, flags, vm = ctx.saved_tensors
         g = _f32c(g_normals)
         g_rot = torch.empty(P, 4, dtype=torch.float32, device=dev)
-        if _normals_probe is not None:
-            _normals_probe("msgs_gaussian_normals_backward")
-        with _on_device(dev):
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            _C.check(_C.lib.msgs_gaussian_normals_backward(P, _ptr(r), _ptr(flags), _ptr(vm), int(ctx.world), _ptr(g),
-                                                           _ptr(g_rot), stream), "msgs_gaussian_normals_backward")
+        _launch(_normals_probe, "msgs_gaussian_normals_backward", dev, P, _ptr(r), _ptr(flags), _ptr(vm), int(ctx.world), _ptr(g),
+                _ptr(g_rot))
         return None, None, g_rot.view(ctx.shape), None, None, None
 
 
@@ -1959,20 +1963,15 @@ class _DepthToNormal(torch.autograd.Function):
     @staticmethod
     def forward(ctx, depth, viewmatrix, W, H, tanfovx, tanfovy, world):
         dev = depth.device
-        if dev.type != "cuda":
-            raise RuntimeError(_HIP_ONLY)
+        _hip_only(dev)
         ctx.dev, ctx.world, ctx.geometry, ctx.shape = dev, bool(world), (W, H, float(tanfovx), float(tanfovy)), depth.shape
         normal = torch.empty(3, H, W, dtype=torch.float32, device=dev)
         if W * H == 0:
             return normal
         z = _f32c(depth.detach())
         vm = _camera_constant(viewmatrix, 16, dev, "viewmatrix") if world else None
-        if _normals_probe is not None:
-            _normals_probe("msgs_depth_normal_forward")
-        with _on_device(dev):
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            _C.check(_C.lib.msgs_depth_normal_forward(W, H, ctx.geometry[2], ctx.geometry[3], _ptr(z), _ptr(vm), int(ctx.world),
-                                                      _ptr(normal), stream), "msgs_depth_normal_forward")
+        _launch(_normals_probe, "msgs_depth_normal_forward", dev, W, H, ctx.geometry[2], ctx.geometry[3], _ptr(z), _ptr(vm),
+                int(ctx.world), _ptr(normal))
         ctx.save_for_backward(z, *(() if vm is None else (vm,)))
         return normal
 
@@ -1986,12 +1985,8 @@ class _DepthToNormal(torch.autograd.Function):
         vm = ctx.saved_tensors[1] if ctx.world else None
         g = _f32c(g_normal)
         g_depth = torch.empty(H, W, dtype=torch.float32, device=dev)
-        if _normals_probe is not None:
-            _normals_probe("msgs_depth_normal_backward")
-        with _on_device(dev):
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            _C.check(_C.lib.msgs_depth_normal_backward(W, H, tx, ty, _ptr(z), _ptr(vm), int(ctx.world), _ptr(g), _ptr(g_depth),
-                                                       stream), "msgs_depth_normal_backward")
+        _launch(_normals_probe, "msgs_depth_normal_backward", dev, W, H, tx, ty, _ptr(z), _ptr(vm), int(ctx.world), _ptr(g),
+                _ptr(g_depth))
         return (g_depth.view(ctx.shape),) + (None,) * 6
 
 
@@ -2047,12 +2042,7 @@ class _BilateralSlice(torch.autograd.Function):
         if W * H == 0:
             return out
         im, gr = _f32c(image.detach()), _f32c(grid.detach())
-        if _bilagrid_probe is not None:
-            _bilagrid_probe("msgs_bilagrid_slice_forward")
-        with _on_device(dev):
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            _C.check(_C.lib.msgs_bilagrid_slice_forward(W, H, GX, GY, GL, _ptr(im), _ptr(gr), _ptr(out), stream),
-                     "msgs_bilagrid_slice_forward")
+        _launch(_bilagrid_probe, "msgs_bilagrid_slice_forward", dev, W, H, GX, GY, GL, _ptr(im), _ptr(gr), _ptr(out))
         ctx.save_for_backward(im, gr)
         return out
 
@@ -2073,13 +2063,8 @@ class _BilateralSlice(torch.autograd.Function):
             nbytes = int(_C.lib.msgs_bilagrid_scratch_bytes(W, H, GX, GY, GL))
             scratch = _bytes(nbytes, dev)
         want = (_C.BILAGRID_GRAD_IMAGE if want_image else 0) | (_C.BILAGRID_GRAD_GRID if want_grid else 0)
-        if _bilagrid_probe is not None:
-            _bilagrid_probe("msgs_bilagrid_slice_backward")
-        with _on_device(dev):
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            _C.check(_C.lib.msgs_bilagrid_slice_backward(W, H, GX, GY, GL, _ptr(im), _ptr(gr), _ptr(g), want, _ptr(g_image),
-                                                         _ptr(g_grid), _ptr(scratch), nbytes, stream),
-                     "msgs_bilagrid_slice_backward")
+        _launch(_bilagrid_probe, "msgs_bilagrid_slice_backward", dev, W, H, GX, GY, GL, _ptr(im), _ptr(gr), _ptr(g), want,
+                _ptr(g_image), _ptr(g_grid), _ptr(scratch), nbytes)
         return (g_image.view(ctx.shapes[0]) if want_image else None), (g_grid if want_grid else None)
 
 
@@ -2106,8 +2091,7 @@ class _TotalVariation(torch.autograd.Function):
     @staticmethod
     def forward(ctx, grids):
         dev = grids.device
-        if dev.type != "cuda":
-            raise RuntimeError(_HIP_ONLY)
+        _hip_only(dev)
         N, _, GL, GY, GX = (int(v) for v in grids.shape)
         ctx.dev, ctx.sizes, ctx.shape = dev, (N, GX, GY, GL), grids.shape
         tv = torch.zeros(1, dtype=torch.float32, device=dev)
@@ -2116,12 +2100,7 @@ class _TotalVariation(torch.autograd.Function):
         gr = _f32c(grids.detach())
         nbytes = int(_C.lib.msgs_bilagrid_tv_scratch_bytes(gr.numel()))
         scratch = _bytes(nbytes, dev)
-        if _bilagrid_probe is not None:
-            _bilagrid_probe("msgs_bilagrid_tv_forward")
-        with _on_device(dev):
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            _C.check(_C.lib.msgs_bilagrid_tv_forward(N, GX, GY, GL, _ptr(gr), _ptr(tv), _ptr(scratch), nbytes, stream),
-                     "msgs_bilagrid_tv_forward")
+        _launch(_bilagrid_probe, "msgs_bilagrid_tv_forward", dev, N, GX, GY, GL, _ptr(gr), _ptr(tv), _ptr(scratch), nbytes)
         ctx.save_for_backward(gr)
         return tv[0]
 
@@ -2134,12 +2113,7 @@ class _TotalVariation(torch.autograd.Function):
             return g_grids
         (gr,) = ctx.saved_tensors
         up = _f32c(g_tv.detach().to(dev)).reshape(1)
-        if _bilagrid_probe is not None:
-            _bilagrid_probe("msgs_bilagrid_tv_backward")
-        with _on_device(dev):
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            _C.check(_C.lib.msgs_bilagrid_tv_backward(N, GX, GY, GL, _ptr(gr), _ptr(up), _ptr(g_grids), stream),
-                     "msgs_bilagrid_tv_backward")
+        _launch(_bilagrid_probe, "msgs_bilagrid_tv_backward", dev, N, GX, GY, GL, _ptr(gr), _ptr(up), _ptr(g_grids))
         return g_grids
 
 
@@ -2212,28 +2186,9 @@ def _tsdf_pool(volume, who):
     return v
 
 
-def _tsdf_on_device(who, dev, **tensors):
-    """the last check in front of a launch: the volume and every map live on one HIP device"""
-    if dev.type != "cuda":
-        raise RuntimeError(f"{who}: the volume must live on a HIP device ('cuda'); there is no CPU path")
-    for name, t in tensors.items():
-        if t is not None and t.device.type != "cuda":
-            raise RuntimeError(f"{who}: {name} must live on a HIP device ('cuda'); there is no CPU path")
-        if t is not None and t.device != dev:
-            raise ValueError(f"{who}: {name} is on {t.device}, the volume on {dev}")
-
-
 def _tsdf_frames(who, dev, depth, cameras, sdf_trunc, depth_trunc, colour=None, weight=None):
     """(msgs_tsdf_frames_t, the host camera table, the tensors it points to) — everything is checked before any launch"""
-    for name, t in (("depth", depth), ("colour", colour), ("weight", weight)):
-        if t is None:
-            continue
-        if not torch.is_tensor(t):
-            raise ValueError(f"{who}: {name} must be a tensor")
-        if t.dtype != torch.float32:
-            raise ValueError(f"{who}: {name} must be float32, not {t.dtype}")
-        if t.requires_grad:
-            raise ValueError(f"{who}: {name} requires grad — TSDF fusion is not differentiable: pass {name}.detach()")
+    _require_plain_f32(who, "TSDF fusion", depth=depth, colour=colour, weight=weight)
     if depth.dim() != 3:
         raise ValueError(f"{who}: depth must be [n,H,W], got {tuple(depth.shape)}")
     n, H, W = (int(x) for x in depth.shape)
@@ -2258,7 +2213,7 @@ def _tsdf_frames(who, dev, depth, cameras, sdf_trunc, depth_trunc, colour=None, 
         raise ValueError(f"{who}: {table.shape[0]} cameras for {n} depth maps")
     if n and not bool(((table[:, 18] == W) & (table[:, 19] == H)).all()):
         raise ValueError(f"{who}: every camera of a call must have the size of the depth maps, {W}x{H}")
-    _tsdf_on_device(who, dev, depth=depth, colour=colour, weight=weight)
+    _require_hip(who, ("the volume", dev), depth=depth, colour=colour, weight=weight)
     f = _C.TsdfFrames()
     f.n, f.W, f.H = n, W, H
     f.sdf_trunc, f.depth_trunc = float(sdf_trunc), float(depth_trunc)
@@ -2278,13 +2233,9 @@ def tsdf_allocate(volume, depth, cameras, sdf_trunc, depth_trunc):
     if f.n == 0:
         return marks
     steps = tsdf_mark_steps(volume.voxel_size, sdf_trunc, table)
-    with _on_device(dev):
-        cams = table.to(dev)
-        f.cameras, f.depth = cams.data_ptr(), depth.data_ptr()
-        if _tsdf_probe is not None:
-            _tsdf_probe("msgs_tsdf_mark_blocks")
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _C.check(_C.lib.msgs_tsdf_mark_blocks(C.byref(v), C.byref(f), steps, _ptr(marks), stream), "msgs_tsdf_mark_blocks")
+    cams = table.to(dev)
+    f.cameras, f.depth = cams.data_ptr(), depth.data_ptr()
+    _launch(_tsdf_probe, "msgs_tsdf_mark_blocks", dev, C.byref(v), C.byref(f), steps, _ptr(marks))
     return marks
 
 
@@ -2301,15 +2252,11 @@ def tsdf_integrate(volume, depth, cameras, sdf_trunc, depth_trunc, colour=None, 
         raise ValueError("tsdf_integrate: colour maps are needed exactly when the volume stores colour")
     if v.n_slots == 0 or f.n == 0:
         return
-    with _on_device(dev):
-        cams = table.to(dev)
-        f.cameras, f.depth = cams.data_ptr(), depth.data_ptr()
-        f.colour = None if colour is None else colour.data_ptr()
-        f.weight = None if weight is None else weight.data_ptr()
-        if _tsdf_probe is not None:
-            _tsdf_probe("msgs_tsdf_integrate")
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _C.check(_C.lib.msgs_tsdf_integrate(C.byref(v), C.byref(f), stream), "msgs_tsdf_integrate")
+    cams = table.to(dev)
+    f.cameras, f.depth = cams.data_ptr(), depth.data_ptr()
+    f.colour = None if colour is None else colour.data_ptr()
+    f.weight = None if weight is None else weight.data_ptr()
+    _launch(_tsdf_probe, "msgs_tsdf_integrate", dev, C.byref(v), C.byref(f))
 
 
 @torch.no_grad()
@@ -2321,7 +2268,7 @@ def tsdf_extract(volume):
     TSDFVolume.extract_mesh(drop_unreferenced=True)."""
     v = _tsdf_pool(volume, "tsdf_extract")
     dev = volume.table.device
-    _tsdf_on_device("tsdf_extract", dev)
+    _require_hip("tsdf_extract", ("the volume", dev))
     S = v.n_slots
     has_colour = volume.colour_sum is not None
     empty = (torch.zeros(0, 3, device=dev), torch.zeros(0, 3, device=dev) if has_colour else None,
@@ -2332,10 +2279,7 @@ def tsdf_extract(volume):
         mask = torch.empty(S * 512, dtype=torch.uint8, device=dev)
         vcount = torch.empty(S * 512, dtype=torch.int32, device=dev)
         tcount = torch.empty(S * 512, dtype=torch.int32, device=dev)
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        if _tsdf_probe is not None:
-            _tsdf_probe("msgs_tsdf_count")
-        _C.check(_C.lib.msgs_tsdf_count(C.byref(v), _ptr(mask), _ptr(vcount), _ptr(tcount), stream), "msgs_tsdf_count")
+        _launch(_tsdf_probe, "msgs_tsdf_count", dev, C.byref(v), _ptr(mask), _ptr(vcount), _ptr(tcount))
         vend, tend = torch.cumsum(vcount, 0, dtype=torch.int64), torch.cumsum(tcount, 0, dtype=torch.int64)
         V, F = (int(x) for x in torch.stack((vend[-1], tend[-1])).tolist())
         if V >= 1 << 31 or F >= 1 << 31:
@@ -2350,9 +2294,7 @@ def tsdf_extract(volume):
         m.edge_mask, m.vertex_offset, m.triangle_offset = mask.data_ptr(), voff.data_ptr(), toff.data_ptr()
         m.n_vertices, m.n_faces = V, F
         m.vertices, m.colours, m.faces = vertices.data_ptr(), None if colours is None else colours.data_ptr(), faces.data_ptr()
-        if _tsdf_probe is not None:
-            _tsdf_probe("msgs_tsdf_emit")
-        _C.check(_C.lib.msgs_tsdf_emit(C.byref(v), C.byref(m), stream), "msgs_tsdf_emit")
+        _launch(_tsdf_probe, "msgs_tsdf_emit", dev, C.byref(v), C.byref(m))
     return vertices, colours, faces
 
 
@@ -2367,15 +2309,7 @@ _vq_probe = None                   # tests: a callable (name) run in front of ev
 
 def _vq_rows(who, x, codebook, **more):
     """(P, D, K) of x [P,D] and codebook [K,D] — everything is checked before any launch; `more`: further float32 tensors"""
-    for name, t in (("x", x), ("codebook", codebook)) + tuple(more.items()):
-        if t is None:
-            continue
-        if not torch.is_tensor(t):
-            raise ValueError(f"{who}: {name} must be a tensor")
-        if t.dtype != torch.float32:
-            raise ValueError(f"{who}: {name} must be float32, not {t.dtype}")
-        if t.requires_grad:
-            raise ValueError(f"{who}: {name} requires grad — vector quantisation is not differentiable: pass {name}.detach()")
+    _require_plain_f32(who, "vector quantisation", x=x, codebook=codebook, **more)
     if x.dim() != 2 or codebook.dim() != 2:
         raise ValueError(f"{who}: x must be [P,D] and codebook [K,D], got {tuple(x.shape)} and {tuple(codebook.shape)}")
     (P, D), (K, Dc) = (int(n) for n in x.shape), (int(n) for n in codebook.shape)
@@ -2390,20 +2324,6 @@ def _vq_rows(who, x, codebook, **more):
     return P, D, K
 
 
-def _vq_on_device(who, **tensors):
-    """the last check in front of a launch: every tensor lives on one HIP device"""
-    dev = None
-    for name, t in tensors.items():
-        if t is None:
-            continue
-        if t.device.type != "cuda":
-            raise RuntimeError(f"{who}: {name} must live on a HIP device ('cuda'); there is no CPU path")
-        if dev is not None and t.device != dev:
-            raise ValueError(f"{who}: {name} is on {t.device}, x on {dev}")
-        dev = t.device
-    return dev
-
-
 @torch.no_grad()
 def vq_assign(x, codebook, return_error=True):
     """(idx [P] int32, err [P] float32 or None): for every row of x [P,D] the nearest row of codebook [K,D] under SPEC M21 (a) —
@@ -2413,19 +2333,15 @@ def vq_assign(x, codebook, return_error=True):
     codebook out; no [P,K] matrix exists anywhere.  The same bits on every run.  Inputs are assumed finite: a row with a NaN gets
     idx 0 and err NaN; a row with an infinity gets the lowest code whose score came out -inf, or 0 when none did."""
     P, D, K = _vq_rows("vq_assign", x, codebook)
-    dev = _vq_on_device("vq_assign", x=x, codebook=codebook)
+    dev = _require_hip("vq_assign", x=x, codebook=codebook)
     idx = torch.empty(P, dtype=torch.int32, device=dev)
     err = torch.empty(P, dtype=torch.float32, device=dev) if return_error else None
     if P == 0:
         return idx, err
     x, codebook = x.contiguous(), codebook.contiguous()
-    with _on_device(dev):
-        scratch = _bytes(_C.lib.msgs_vq_scratch_bytes(0, D, K), dev)
-        if _vq_probe is not None:
-            _vq_probe("msgs_vq_assign")
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _C.check(_C.lib.msgs_vq_assign(P, D, K, _ptr(x), _ptr(codebook), _ptr(idx), _ptr(err), _ptr(scratch), scratch.numel(),
-                                       stream), "msgs_vq_assign")
+    scratch = _bytes(_C.lib.msgs_vq_scratch_bytes(0, D, K), dev)
+    _launch(_vq_probe, "msgs_vq_assign", dev, P, D, K, _ptr(x), _ptr(codebook), _ptr(idx), _ptr(err), _ptr(scratch),
+            scratch.numel())
     return idx, err
 
 
@@ -2442,7 +2358,7 @@ def vq_update(x, idx, codebook, weights=None):
         raise ValueError(f"vq_update: idx must be an int32 or int64 tensor [{P}]")
     if weights is not None and tuple(weights.shape) != (P,):
         raise ValueError(f"vq_update: weights must be [{P}], got {tuple(weights.shape)}")
-    dev = _vq_on_device("vq_update", x=x, idx=idx, codebook=codebook, weights=weights)
+    dev = _require_hip("vq_update", x=x, idx=idx, codebook=codebook, weights=weights)
     x, codebook = x.contiguous(), codebook.contiguous()
     weights = None if weights is None else weights.contiguous()
     with _on_device(dev):
@@ -2458,12 +2374,8 @@ def vq_update(x, idx, codebook, weights=None):
         mass = torch.empty(K, dtype=torch.float64, device=dev)
         count = torch.empty(K, dtype=torch.int32, device=dev)
         scratch = _bytes(_C.lib.msgs_vq_scratch_bytes(P, D, K), dev)
-        if _vq_probe is not None:
-            _vq_probe("msgs_vq_update")
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _C.check(_C.lib.msgs_vq_update(P, D, K, _ptr(x), _ptr(weights), _ptr(order), _ptr(offsets), _ptr(chunk_offsets),
-                                       _ptr(codebook), _ptr(new), _ptr(mass), _ptr(count), _ptr(scratch), scratch.numel(), stream),
-                 "msgs_vq_update")
+        _launch(_vq_probe, "msgs_vq_update", dev, P, D, K, _ptr(x), _ptr(weights), _ptr(order), _ptr(offsets), _ptr(chunk_offsets),
+                _ptr(codebook), _ptr(new), _ptr(mass), _ptr(count), _ptr(scratch), scratch.numel())
     return new, mass, count
 
 
@@ -2474,21 +2386,9 @@ def vq_update(x, idx, codebook, weights=None):
 _mesh_probe = None                 # tests: a callable (name) run in front of every msgs_graph_* / msgs_mesh_* call
 
 
-def _mesh_call(name, *args):
-    if _mesh_probe is not None:
-        _mesh_probe(name)
-    _C.check(getattr(_C.lib, name)(*args), name)
-
-
 def _mesh_index_tensor(who, name, t, shape_ok, shape_text):
     if not torch.is_tensor(t) or t.dtype not in (torch.int32, torch.int64) or not shape_ok(t):
         raise ValueError(f"{who}: {name} must be an int32 or int64 tensor {shape_text}")
-
-
-def _mesh_on_device(who, **tensors):
-    for name, t in tensors.items():
-        if t.device.type != "cuda":
-            raise RuntimeError(f"{who}: {name} must live on a HIP device ('cuda'); there is no CPU path")
 
 
 def _mesh_in_range(who, name, t, n):
@@ -2516,15 +2416,14 @@ def graph_components(n_nodes, a, b):
     E, dev = int(a.shape[0]), a.device
     if E >= 1 << 31:
         raise ValueError(f"graph_components: E = {E} edges do not fit int32 indices")
-    _mesh_on_device("graph_components", a=a, b=b)
+    _require_hip("graph_components", a=a, b=b)
     with _on_device(dev):
         a, b = _mesh_in_range("graph_components", "a", a, N), _mesh_in_range("graph_components", "b", b, N)
         if N == 0 or E == 0:
             return torch.arange(N, dtype=torch.int32, device=dev)
         parent = torch.empty(N, dtype=torch.int32, device=dev)
         label = torch.empty(N, dtype=torch.int32, device=dev)
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _mesh_call("msgs_graph_components", N, E, _ptr(a), _ptr(b), _ptr(parent), _ptr(label), stream)
+        _launch(_mesh_probe, "msgs_graph_components", dev, N, E, _ptr(a), _ptr(b), _ptr(parent), _ptr(label))
     return label
 
 
@@ -2535,16 +2434,16 @@ def _mesh_faces(who, faces, n_vertices):
         raise ValueError(f"{who}: n_vertices = {V} is outside [0, 2^31)")
     if 3 * F >= 1 << 31:
         raise ValueError(f"{who}: {F} faces: 3 F must stay below 2^31")
-    _mesh_on_device(who, faces=faces)
+    _require_hip(who, faces=faces)
     return V, F
 
 
-def _mesh_sorted_keys(who, faces, F, mode, stream):
+def _mesh_sorted_keys(faces, F, mode):
     """(keys_sorted [3F] int64, face_sorted [3F] int32): the corner keys of SPEC M22 (b) in ascending order"""
     dev = faces.device
     keys = torch.empty(3 * F, dtype=torch.int64, device=dev)
     face_of_key = torch.empty(3 * F, dtype=torch.int32, device=dev)
-    _mesh_call("msgs_mesh_corner_keys", F, _ptr(faces), mode, _ptr(keys), _ptr(face_of_key), stream)
+    _launch(_mesh_probe, "msgs_mesh_corner_keys", dev, F, _ptr(faces), mode, _ptr(keys), _ptr(face_of_key))
     keys_sorted, order = torch.sort(keys)
     return keys_sorted, face_of_key[order]
 
@@ -2565,12 +2464,11 @@ def mesh_triangle_clusters(faces, n_vertices, connectivity="edge"):
         faces = _mesh_in_range("mesh_triangle_clusters", "faces", faces, V)
         if F == 0:
             return torch.zeros(0, dtype=torch.int32, device=dev), torch.zeros(0, dtype=torch.int32, device=dev)
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         mode = _C.MESH_EDGE if connectivity == "edge" else _C.MESH_VERTEX
-        keys_sorted, face_sorted = _mesh_sorted_keys("mesh_triangle_clusters", faces, F, mode, stream)
+        keys_sorted, face_sorted = _mesh_sorted_keys(faces, F, mode)
         parent = torch.empty(F, dtype=torch.int32, device=dev)
         label = torch.empty(F, dtype=torch.int32, device=dev)
-        _mesh_call("msgs_mesh_link_sorted", F, 3 * F, _ptr(keys_sorted), _ptr(face_sorted), _ptr(parent), _ptr(label), stream)
+        _launch(_mesh_probe, "msgs_mesh_link_sorted", dev, F, 3 * F, _ptr(keys_sorted), _ptr(face_sorted), _ptr(parent), _ptr(label))
         is_root = label == torch.arange(F, dtype=torch.int32, device=dev)
         rank = torch.cumsum(is_root, 0, dtype=torch.int32) - 1             # of a root: its cluster id
         clusters = rank[label.long()]
@@ -2589,10 +2487,9 @@ def mesh_edge_report(faces, n_vertices):
         faces = _mesh_in_range("mesh_edge_report", "faces", faces, V)
         if F == 0:
             return 0, 0, 0
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        keys_sorted, _ = _mesh_sorted_keys("mesh_edge_report", faces, F, _C.MESH_EDGE, stream)
+        keys_sorted, _ = _mesh_sorted_keys(faces, F, _C.MESH_EDGE)
         counts = torch.empty(3, dtype=torch.int64, device=dev)
-        _mesh_call("msgs_mesh_edge_report", 3 * F, _ptr(keys_sorted), _ptr(counts), stream)
+        _launch(_mesh_probe, "msgs_mesh_edge_report", dev, 3 * F, _ptr(keys_sorted), _ptr(counts))
         boundary, manifold, non_manifold = counts.tolist()
     return boundary, manifold, non_manifold
 
@@ -2641,12 +2538,8 @@ class ContributionAccumulator:
 
     def _add(self, call, state, pixel_weights):
         geom, binning, image, D = state
-        dev = self.device
-        with _on_device(dev):
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            _C.check(_C.lib.msgs_contrib_accumulate(*_replay_args(call, self.P, geom, binning, image, D), _ptr(pixel_weights),
-                                                    _ptr(self.buf), self.nbytes, int(self.views == 0), stream),
-                     "msgs_contrib_accumulate")
+        _launch(None, "msgs_contrib_accumulate", self.device, *_replay_args(call, self.P, geom, binning, image, D),
+                _ptr(pixel_weights), _ptr(self.buf), self.nbytes, int(self.views == 0))
         self.views += 1
 
     def scores(self):
@@ -2658,10 +2551,7 @@ class ContributionAccumulator:
         ws = torch.empty(P, dtype=torch.float32, device=dev)
         wm = torch.empty(P, dtype=torch.float32, device=dev)
         pc = torch.empty(P, dtype=torch.int64, device=dev)
-        with _on_device(dev):
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            _C.check(_C.lib.msgs_contrib_finish(P, _ptr(self.buf), self.nbytes, _ptr(ws), _ptr(wm), _ptr(pc), stream),
-                     "msgs_contrib_finish")
+        _launch(None, "msgs_contrib_finish", dev, P, _ptr(self.buf), self.nbytes, _ptr(ws), _ptr(wm), _ptr(pc))
         return ContributionScores(ws, wm, pc)
 
 
@@ -2781,10 +2671,7 @@ class GaussianRasterizer(nn.Module):
                 raise RuntimeError("markVisible: positions must live on a HIP device")
             vm, pm = _f32c(rs.viewmatrix.to(dev)), _f32c(rs.projmatrix.to(dev))
             out = torch.empty(pos.shape[0], dtype=torch.uint8, device=dev)
-            with _on_device(dev):
-                stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-                _C.check(_C.lib.msgs_mark_visible(int(pos.shape[0]), _ptr(pos), _ptr(vm), _ptr(pm), _ptr(out),
-                                                  stream), "msgs_mark_visible")
+            _launch(None, "msgs_mark_visible", dev, int(pos.shape[0]), _ptr(pos), _ptr(vm), _ptr(pm), _ptr(out))
         return out.bool()
 
     def preprocess_only(self, means3D, opacities, scales=None, rotations=None, cov3D_precomp=None,
@@ -2806,12 +2693,9 @@ class GaussianRasterizer(nn.Module):
             pixel_sizes = torch.zeros(P, dtype=torch.float32, device=dev)
             if P == 0:
                 return radii, pixel_sizes
-            lib = _C.lib
-            with _on_device(dev):
-                stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-                geom = torch.empty(int(lib.msgs_geom_bytes(P)), dtype=torch.uint8, device=dev)
-                _C.check(lib.msgs_preprocess_only(C.byref(call.view), C.byref(call.g), _ptr(radii), _ptr(pixel_sizes),
-                                                  _ptr(geom), geom.numel(), stream), "msgs_preprocess_only")
+            geom = torch.empty(int(_C.lib.msgs_geom_bytes(P)), dtype=torch.uint8, device=dev)
+            _launch(None, "msgs_preprocess_only", dev, call.view_ref, call.g_ref, _ptr(radii), _ptr(pixel_sizes), _ptr(geom),
+                    geom.numel())
         return radii, pixel_sizes
 
     def contributions(self, means3D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None,

@@ -445,6 +445,11 @@ def check(rc, where):
     raise RuntimeError(f"{where}: error {rc}: {msg}")
 
 
+def ptr(t):
+    """a tensor's device address as the void* the entry points take; None stays None (a null pointer)"""
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
 # ---- optional per-kernel timing (used by bench.py; thread-local so backward picks it up too) ----
 class KernelTimer:
     """Owns 2*K_COUNT HIP events; pass to set_timer() to have the next forward/backward record them.

@@ -28,6 +28,7 @@ import torch
 import torch.nn as nn
 
 from diff_gaussian_rasterization import _backend as _C
+from diff_gaussian_rasterization._backend import ptr as _ptr
 
 # optimizer group name -> model attribute (gaussian_model.py:235-246)
 GROUPS = (("xyz", "_xyz"), ("f_dc", "_features_dc"), ("f_rest", "_features_rest"), ("opacity", "_opacity"),
@@ -38,10 +39,6 @@ STATS = ("xyz_gradient_accum", "denom", "max_radii2D", "max_pixel_sizes", "min_p
 # row kinds of the output (include/msgs.h): kept, clone, first child, second child, grown, appended
 KEEP, CLONE, CHILD1, CHILD2, GROW, APPEND = range(6)
 _ESZ = {torch.float32: 4, torch.int64: 8, torch.bool: 1}
-
-
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
 
 
 def _rules(**by_kind):

@@ -20,10 +20,7 @@ import ctypes as C
 import torch
 
 from diff_gaussian_rasterization import _backend as _C
-
-
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
+from diff_gaussian_rasterization._backend import ptr as _ptr
 
 
 def _require_gpu_f32(t, what):

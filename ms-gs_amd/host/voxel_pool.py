@@ -28,10 +28,7 @@ from types import SimpleNamespace
 import torch
 
 from diff_gaussian_rasterization import _backend as _C
-
-
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
+from diff_gaussian_rasterization._backend import ptr as _ptr
 
 
 class VoxelGrouping:
